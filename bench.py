@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- CSR SpMV GB/s (% of HBM peak) + Jacobi-PCG iterations/s, 7-pt Poisson, fp64.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--full] [--dump-outputs DIR]
+
+A plain one-GPU run sets up, warms up, times the K steps, runs the Jacobi-PCG solve of the metric and prints the line;
+--full adds everything measured or checked beside it (counters, the other kernels, placement sweep, ceilings, clocks,
+the sss_mat / solvers / single-kernel / 1024^3 legs, CPU baselines, parity checks).  --dump-outputs DIR writes y of the
+last timed step (x is seeded, so two builds can be compared output for output).
 
 N > 1 without a torch.distributed environment: bench.py starts its own ranks (a fresh
 `python -m torch.distributed.run --nproc-per-node N` child, before anything touches the GPU)
@@ -38,9 +43,9 @@ import time  # noqa: E402
 
 import numpy as np  # noqa: E402
 
-from bench_common import (HBM_PEAK_GBPS, METRIC, PARITY_ITERS, PARITY_TOL, PMC_FILES, ROOT, W2_VARIANT, W3_VARIANT,  # noqa: E402,F401
-                          Events, _maxrel, csr_model_bytes, kernel_bytes, parity_object, pcg_vector_bytes, provenance,
-                          rel_diff, timed_launches)
+from bench_common import (DUMP_ROWS, HBM_PEAK_GBPS, METRIC, PARITY_ITERS, PARITY_TOL, PMC_FILES, ROOT, W2_VARIANT,  # noqa: E402,F401
+                          W3_VARIANT, Events, _maxrel, csr_model_bytes, dump_outputs, kernel_bytes, output_arrays,
+                          parity_object, pcg_vector_bytes, provenance, rel_diff, timed_launches)
 from bench_launch import LADDER, guarded_rank, orchestrate  # noqa: E402
 from bench_line import emit, judge_phases, predicted_iteration  # noqa: E402
 from bench_legs import (dry_strong_n1, gpu_clocks, link_topology, live_traffic, pcg_single, peer_matrix,  # noqa: E402
@@ -684,14 +689,29 @@ def main():
     ap.add_argument("--mtx", default="",
                     help="configs[4] on its own: a symmetric MatrixMarket file (e.g. SuiteSparse Emilia_923.mtx) or "
                          "standin:fem32 | standin:fem512 | standin:logspaced -- sss_mat product + Jacobi-MINRES on one "
-                         "GPU with parity against the oracle.  The default run adds the same object as `config5` when "
+                         "GPU with parity against the oracle.  The --full run adds the same object as `config5` when "
                          "the environment variable EMILIA_MTX names a file")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also measure and check everything beside the headline (hardware counters, the other "
+                         "kernels on the same operator, placement sweep, streaming ceilings, clocks, the sss_mat / "
+                         "solvers / single-kernel / 1024^3 legs, CPU baselines, parity checks, config5).  Without it a "
+                         "one-GPU run sets up, times the steps, runs the PCG solve of the metric and prints the line.  "
+                         "N > 1 runs keep their in-job legs either way")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write y of the last step as DIR/y.npy (float64); when y has more than "
+                         "%d rows, a fixed seeded sample of them, their row numbers in DIR/y_rows.npy.  N > 1: "
+                         "y_rank<r>.npy / y_rank<r>_rows.npy per rank.  Not with --mtx or --single-process (that "
+                         "timed loop keeps its vectors inside the library)" % DUMP_ROWS)
     a = ap.parse_args()
 
     if a.mtx:
+        if a.dump_outputs:
+            ap.error("--dump-outputs is not available with --mtx")
         raise SystemExit(mtx_main(a))
 
     if a.single_process:
+        if a.dump_outputs:  # psp_csr_multi_spmv_time keeps x and y inside the library: there is no y of the timed loop
+            ap.error("--dump-outputs is not available with --single-process")
         raise SystemExit(single_process_main(a))
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         argv = [t for t in sys.argv[1:]]
@@ -757,6 +777,8 @@ def run_body(a, real_stdout):
     use_dist = world > 1 or a.force_dist or scaling != "single"
     if a.test_backend:
         use_dist = True
+    # a plain one-GPU run measures the headline only; the legs beside it run with --full (N > 1: always)
+    extras = a.full or use_dist
     if a.grid:
         nx, ny, nz = (int(t) for t in a.grid.split(","))
     elif scaling == "single":
@@ -770,7 +792,7 @@ def run_body(a, real_stdout):
     # roofline.traffic from the hardware counters of this job's own runs -- child processes, and before this
     # process creates its GPU context (see live_traffic)
     pmc_live, pmc_reason = None, None
-    if world == 1 and not use_dist and not a.no_pmc:
+    if world == 1 and not use_dist and not a.no_pmc and extras:
         pmc_live, pmc_reason = live_traffic((nx, ny, nz), a.variant)
 
     if use_dist or os.environ.get("PSP_IMPORT_TORCH"):
@@ -870,19 +892,27 @@ def run_body(a, real_stdout):
     # ---- the timed region (timed_region above): W warm-up steps, then exactly K steps between barrier + synchronize
     ev = None if dry else Events(L, check, a.steps + 1)
     wall, ev_ms = timed_region(step, sync, ev, a.warmup, a.steps)
+    if a.dump_outputs:  # y of the last timed step, before any leg below reuses the vectors
+        if use_dist:
+            yh = y.detach().cpu().numpy() if hasattr(y, "detach") else np.asarray(y)
+            dump_outputs(a.dump_outputs, output_arrays(yh, "y" if world == 1 else "y_rank%d" % rank, DUMP_ROWS // world))
+        else:
+            dump_outputs(a.dump_outputs, output_arrays(yb.download()))
+    med_ms = None
     if dry:
         med_ms = ev_ms
         kernel, kinfo = "test-backend", {}
     else:
         # per-launch median of the same K launches (SURVEY 8d protocol), outside the timed region
-        _, med_ms = timed_launches(step, sync, ev, a.steps)
+        if extras:
+            _, med_ms = timed_launches(step, sync, ev, a.steps)
         kernel, kinfo = Aloc.kernel_info()
     kbytes_loc = kernel_bytes(kernel, kinfo, n_loc, nnz_loc)
 
     # ---- beside it (N = 1; bench_legs.py): the other SpMV kernels on the SAME operator, the placement sweep, the
     # streaming ceilings of this job.  Reported only -- none of them feeds `value` / `roofline.achieved`.
     kernels = placement = ceiling = None
-    if not use_dist and not a.no_kernels:
+    if not use_dist and not a.no_kernels and extras:
         ctx = {"L": L, "check": check, "dev": dev, "A": A, "xb": xb, "yb": yb, "n": n_loc, "nnz": nnz_loc, "step": step,
                "sync": sync, "ev": ev, "steps": a.steps, "kbytes": kbytes_loc}
         if a.variant < 0:
@@ -892,7 +922,7 @@ def run_body(a, real_stdout):
             ceiling = stream_ceiling_leg(ctx)
 
     clocks = None
-    if not a.no_clocks and not dry:
+    if not a.no_clocks and not dry and extras:
         # every rank keeps its GPU busy for ~1 s (N > 1: the steps exchange halos, so all ranks take part);
         # rank 0 reads the clocks meanwhile
         for _ in range(600):
@@ -962,28 +992,28 @@ def run_body(a, real_stdout):
     # ---- beside it (N = 1; bench_legs.py): the same operator as an sss_mat (examples/poisson_test.py solves with
     # S = L.to_sss()): y = S x from the strict lower triangle only, and Jacobi-PCG on it
     sss = None
-    if not use_dist and not a.no_sss:
+    if not use_dist and not a.no_sss and extras:
         sss = sss_leg({"L": L, "check": check, "dev": dev, "xb": xb, "yb": yb, "n": n_loc, "sync": sync, "ev": ev,
                        "steps": a.steps, "grid": (nx, ny, nz), "pcg_iters": k})
 
     # ---- beside it (N = 1; bench_legs.py): the reference's other Krylov solvers on the same operator
     solvers = None
-    if not use_dist and not dry and not a.no_solvers:
+    if not use_dist and not dry and not a.no_solvers and extras:
         try:
             solvers = solvers_leg({"dev": dev, "A": A, "n": n_loc, "kbytes": kbytes_loc})
         except Exception as e:  # noqa: BLE001 - a reported extra, never fatal
             solvers = {"error": str(e)[:200]}
 
-    # ---- beside it (N = 1 default run; bench_legs.py): the single-kernel loops at configs[0]'s size and at 10^6 points
+    # ---- beside it (N = 1 --full run; bench_legs.py): the single-kernel loops at configs[0]'s size and at 10^6 points
     single_kernel = None
-    if not use_dist and not dry and not a.grid and not a.no_solvers:
+    if not use_dist and not dry and not a.grid and not a.no_solvers and extras:
         try:
             single_kernel = single_kernel_leg(L, check, dev)
         except Exception as e:  # noqa: BLE001 - a reported extra, never fatal
             single_kernel = {"error": str(e)[:200]}
 
-    # ---- N = 1 default run: the 1-GPU end of the strong-scaling target (1024^3 on this GPU)
-    if not use_dist and not a.grid and not a.no_strong_n1:
+    # ---- N = 1 --full run: the 1-GPU end of the strong-scaling target (1024^3 on this GPU)
+    if not use_dist and not a.grid and not a.no_strong_n1 and extras:
         A.close()
         xb.free()
         yb.free()
@@ -1177,7 +1207,7 @@ def run_body(a, real_stdout):
                                                "not follow it).  Placement in device memory decides; user space cannot choose it"}
         if clocks is not None:
             out["gpu_clocks_under_load"] = clocks
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and not a.no_cpu_baseline and extras:
             base, ref, parity = cpu_baseline(dev=dev, published=not a.grid)
             if "published_table" in base:
                 out["published_table"] = base.pop("published_table")
@@ -1240,7 +1270,7 @@ def run_body(a, real_stdout):
                     "note": "non-reference: pysparse's product is single-threaded (no OpenMP, GIL held); every y[i] has the "
                             "one-thread bits (%s)" % mt["same_bits_as_one_thread"],
                     "gpu_over_all_cores": out["effective_csr_model_GBps"] / mt["spmv_GBps"]}
-        if world == 1 and not use_dist and os.environ.get("EMILIA_MTX"):
+        if world == 1 and not use_dist and os.environ.get("EMILIA_MTX") and extras:
             try:  # configs[4] on the user's file, beside the headline (its own failure never costs the line)
                 out["config5"] = mtx_leg(os.environ["EMILIA_MTX"])
             except Exception as e:  # noqa: BLE001

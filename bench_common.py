@@ -107,6 +107,25 @@ def parity_object(n1, nr, what):
                                                                                n1["info_iter"] == nr["info_iter"])}
 
 
+DUMP_ROWS = 1 << 21  # rows of y --dump-outputs keeps at most: 16 MB of values + 16 MB of row numbers (one GPU)
+
+
+def output_arrays(y, name="y", rows=DUMP_ROWS):
+    """what --dump-outputs writes for one product y = A x: y itself, or, when it is longer than `rows`, y at a fixed
+    sample of rows (seeded, sorted, the same for every run of the same size) and those rows as float64"""
+    y = np.asarray(y, dtype=np.float64)
+    if y.size <= rows:
+        return {name: y}
+    idx = np.unique(np.random.default_rng(20240607).integers(0, y.size, rows))
+    return {name: y[idx], name + "_rows": idx.astype(np.float64)}
+
+
+def dump_outputs(dirname, arrays):
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def provenance(L):
     """which sources the library that ran was built from (tests/test_capi_symbols.py holds the two equal)"""
     out = {"build_id": L.psp_build_id().decode()}

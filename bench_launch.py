@@ -89,10 +89,12 @@ def _run_stage(cmd, env, timeout_s, log):
 
 def _err_tail(err, keep=14):
     """the lines of a failed stage's stderr worth keeping: the exception lines of the ranks (`SomeError: message`, the
-    first few -- the root cause comes first -- and the last), injected-failure notes, then the end of the stream"""
+    first few -- the root cause comes first -- and the last), RCCL's own error lines, injected-failure notes, then the end
+    of the stream.  The ranks share the stream, so one rank's exception line can arrive cut in two by another's; RCCL's
+    `NCCL error in: ...` line, which follows it on a line of its own, still names the failure then."""
     import re
     lines = [l for l in err.strip().splitlines() if l.strip()]
-    pat = re.compile(r"\b\w*(Error|Exception)\b: \S")
+    pat = re.compile(r"\b\w*(Error|Exception)\b: \S|\bNCCL error\b")
     hits = [l.strip()[:300] for k, l in enumerate(lines)
             if (pat.search(l) or "injected failure" in l or (k and lines[k - 1].strip() == "Last error:"))  # (RCCL's own reason)
             and "ChildFailedError" not in l and "error_file" not in l]

@@ -42,7 +42,7 @@ CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 @pytest.mark.gpu
 def test_bench_json_contract_small_grid():
-    d = run_bench("--grid", "96,96,96", "--steps", "5", "--warmup", "2", "--pcg-iters", "8", "--no-cpu-baseline",
+    d = run_bench("--full", "--grid", "96,96,96", "--steps", "5", "--warmup", "2", "--pcg-iters", "8", "--no-cpu-baseline",
                   "--no-clocks")
     for k in CONTRACT:
         assert k in d, k
@@ -95,6 +95,42 @@ def test_bench_json_contract_small_grid():
     c = d["device_ceiling_same_run"]
     assert c["read_only_dot"]["bytes"] == 16 * n and c["read2_write1"]["bytes"] == 24 * n
     assert c["read_only_dot"]["GBps"] > 0 and c["read2_write1"]["GBps"] > 0
+
+
+EXTRAS = ("kernels_same_operator", "placement_sweep", "device_ceiling_same_run", "gpu_clocks_under_load", "sss_mat",
+          "solvers", "single_kernel_loops", "strong_n1", "cpu_baseline", "parity_check", "published_table", "config5")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_what_they_computed(tmp_path, oracle):
+    """without --full a one-GPU run sets up, times exactly K steps, solves the metric's PCG and prints the line -- no leg
+    beside it; --dump-outputs writes y of the last step: at this size a fixed sample of rows, each one bit for bit the
+    oracle's product of the seeded x, and the same rows and bits in a second run"""
+    import numpy as np
+    grid = (132, 130, 128)  # 2.2e6 rows: more than bench_common.DUMP_ROWS, so y is sampled
+    dumps = []
+    for k in range(2):
+        dd = tmp_path / ("run%d" % k)
+        d = run_bench("--grid", ",".join(map(str, grid)), "--steps", "7", "--warmup", "2", "--pcg-iters", "8",
+                      "--dump-outputs", str(dd))
+        for key in CONTRACT:
+            assert key in d, key
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["metric"].startswith("CSR SpMV GB/s") and d["unit"] == "GB/s" and d["dtype"] == "f64"
+        assert d["pcg_check"]["info"] == -1 and d["pcg_check"]["iter"] == 9 and d["pcg_iters_per_s"] > 0
+        assert not [key for key in EXTRAS if key in d], [key for key in EXTRAS if key in d]
+        assert sorted(os.listdir(dd)) == ["y.npy", "y_rows.npy"]
+        dumps.append((np.load(dd / "y.npy"), np.load(dd / "y_rows.npy")))
+    (y, rows), (y2, rows2) = dumps
+    assert y.dtype == rows.dtype == np.float64 and y.shape == rows.shape and 1 << 20 < y.size <= 1 << 21
+    assert np.array_equal(y, y2) and np.array_equal(rows, rows2)
+    idx = rows.astype(np.int64)
+    assert np.array_equal(idx, rows) and np.all(np.diff(idx) > 0)
+    A = oracle.poisson_csr(*grid)
+    n = A.shape[0]
+    y_ref = np.empty(n)
+    A.matvec(np.random.default_rng(0).standard_normal(n), y_ref)
+    assert idx[-1] < n and np.array_equal(y, y_ref[idx])
 
 
 @pytest.mark.gpu
@@ -158,6 +194,80 @@ def test_bench_cpu_baseline_objects_small_sample():
     if ref is not None:  # oracle/_ref is built where /root/reference exists
         assert ref["kind"] == "reference" and ref["cores"] == 1 and ref["value"] > 0
         assert ref["iterates_match_port"] and ref["iterates_max_rel_diff"] <= ref["iterates_tolerance"]
+
+
+def test_bench_dump_outputs_of_the_ranks_dry_run(tmp_path):
+    """--dump-outputs on the N > 1 path (launcher + row-range driver over gloo, oracle-backed): every rank writes its
+    rows of y from the last timed step, which are the unpartitioned product of the same seeded x slabs"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    dd = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--grid", "12,10,8",
+                          "--steps", "3", "--warmup", "1", "--pcg-iters", "5", "--no-cpu-baseline",
+                          "--test-backend", "tests.dist_oracle_backend:bench_factory", "--dump-outputs", str(dd)],
+                         capture_output=True, text=True, cwd=ROOT, env=env, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert parse(out.stdout)["steps"] == 3
+    assert sorted(os.listdir(dd)) == ["y_rank0.npy", "y_rank1.npy"]
+    sys.path.insert(0, ROOT)
+    from oracle import oracle as O
+    A = O.poisson_csr(12, 10, 8)
+    n = A.shape[0]
+    x = np.concatenate([np.random.default_rng(r).standard_normal(n // 2) for r in range(2)])
+    y_ref = np.empty(n)
+    A.matvec(x, y_ref)
+    y = np.concatenate([np.load(dd / ("y_rank%d.npy" % r)) for r in range(2)])
+    assert y.dtype == np.float64 and np.array_equal(y, y_ref)
+
+
+@pytest.mark.parametrize("mode", [["--single-process", "--gpus", "2"], ["--mtx", "standin:fem32"]])
+def test_bench_dump_outputs_is_refused_where_the_timed_loop_keeps_its_vectors(tmp_path, mode):
+    """--single-process times its product inside the library and --mtx is its own leg: neither has a y of the timed
+    steps to write, so --dump-outputs is refused before anything is set up, and nothing is written"""
+    dd = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + mode + ["--dump-outputs", str(dd)],
+                         capture_output=True, text=True, cwd=ROOT, timeout=120)
+    assert out.returncode == 2 and "--dump-outputs is not available with " + mode[0] in out.stderr, out.stderr[-2000:]
+    assert not dd.exists()
+
+
+def test_bench_ladder_tail_names_rccl_when_the_ranks_lines_interleave():
+    """two ranks share the stage's stderr: when both ranks' `DistBackendError: NCCL error ...` lines arrive cut in two
+    by each other's tracebacks, RCCL's own `NCCL error in:` line still names the failure in the kept tail -- also when
+    torch.distributed.run ends the stream with its own traceback and failure summary, as it does"""
+    sys.path.insert(0, ROOT)
+    from bench_launch import _err_tail
+    rank = ["NCCL error in: NCCLUtils.cpp:93, invalid usage (run with NCCL_DEBUG=WARN for details), NCCL version 2.26.6",
+            "ncclInvalidUsage: This usually reflects invalid usage of NCCL library.", "Last error:",
+            "Duplicate GPU detected : rank %d and rank %d both on CUDA device 5a000"]
+    frames = ["  File \"bench.py\", line 709, in main", "    return run_body(a, real_stdout)",
+              "  File \"distributed_c10d.py\", line 2202, in _new_process_group_helper",
+              "    eager_backend.eager_connect_single_device(device_id)"]
+    launcher = ["[W ProcessGroupNCCL.cpp:1553] Warning: WARNING: destroy_process_group() was not called before program exit",
+                "[W ProcessGroupNCCL.cpp:1553] Warning: WARNING: destroy_process_group() was not called before program exit",
+                "W torch/distributed/elastic/multiprocessing/api.py:1010] Sending process 1455 closing signal SIGTERM",
+                "E torch/distributed/elastic/multiprocessing/api.py:984] failed (exitcode: 1) local_rank: 0 (pid: 1454)",
+                "Traceback (most recent call last):",
+                "  File \"runpy.py\", line 196, in _run_module_as_main", "    return _run_code(code, main_globals, None,",
+                "  File \"torch/distributed/run.py\", line 995, in <module>", "    main()",
+                "  File \"torch/distributed/run.py\", line 982, in run", "    elastic_launch(",
+                "  File \"torch/distributed/launcher/api.py\", line 317, in launch_agent", "    raise ChildFailedError(",
+                "torch.distributed.elastic.multiprocessing.errors.ChildFailedError: ", "=" * 60, "bench.py FAILED",
+                "-" * 60, "Failures:", "[1]:", "  time      : 2026-01-01_00:00:00", "  host      : localhost",
+                "  rank      : 1 (local_rank: 1)", "  exitcode  : -15 (pid: 1455)", "  error_file: <N/A>",
+                "  traceback : Signal 15 (SIGTERM) received by PID 1455", "-" * 60, "Root Cause (first observed failure):",
+                "[0]:", "  time      : 2026-01-01_00:00:00", "  host      : localhost", "  rank      : 0 (local_rank: 0)",
+                "  exitcode  : 1 (pid: 1454)", "  error_file: <N/A>",
+                "  traceback : To enable traceback see: https://pytorch.org/docs/stable/elastic/errors.html", "=" * 60]
+    err = "\n".join(["Traceback (most recent call last):"] * 2 + frames[:2]
+                    + ["torch.distributed    .return run_body(a, real_stdout)DistBackendError", ":" + frames[0]]
+                    + [l % (0, 1) if "%" in l else l for l in rank] + frames[1:]
+                    + ["torch.distributed    .    eager_backend.eager_connect_single_device(device_id)DistBackendError",
+                       ": x"]
+                    + [l % (1, 0) if "%" in l else l for l in rank] + launcher)
+    tail = _err_tail(err)
+    assert any(l.startswith("NCCL error in:") for l in tail), tail
+    assert any(l.startswith("Duplicate GPU detected") for l in tail), tail
 
 
 def test_bench_launches_its_own_ranks_dry_run():

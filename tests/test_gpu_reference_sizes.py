@@ -22,7 +22,7 @@ compiled reference at 512^3 / k = 3), hence the wider bar against it; the GPU's 
 were measured 1.3e-13 apart there (BENCH_r04), so 4x keeps ~200x head-room while an error of 1e-10 in a fused update
 fails.  The long leg drives the COMPILED pcg.c / minres.c through k = 20 iterations at 512^3 with row-parallel operator
 callbacks (same bits per row; the kernels are the reference's code) so that drift, not just the first steps, is
-compared.  The short comparisons ride in every default bench.py run as `parity_check`."""
+compared.  The short comparisons ride in every `bench.py --full` run as `parity_check`."""
 import os
 import sys
 

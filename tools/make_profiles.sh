@@ -6,9 +6,9 @@ set -u
 R=${1:-r1}; OUT=gpurun_out/profiles_$R; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 # (1) the bench line itself
-timeout 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 # (2) kernel trace + stats of the SAME command (no CPU baseline leg: it launches no kernels)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --no-cpu-baseline > $OUT/trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --no-cpu-baseline > $OUT/trace.log 2>&1
 cp $OUT/trace/*/*kernel_stats.csv $OUT/bench_kernel_stats.csv 2>/dev/null
 # (3) PMC passes on the SpMV kernel alone (separate passes; FETCH_SIZE and WRITE_SIZE do not fit one)
 i=1

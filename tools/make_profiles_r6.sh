@@ -7,8 +7,8 @@
 set -u
 OUT=gpurun_out/profiles_r6; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout 600 python3 bench.py --side-file $OUT/r6_bench_side.json > $OUT/r6_bench.json 2> $OUT/bench.err
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --no-cpu-baseline --no-clocks --no-strong-n1 --no-pmc --no-solvers --side-file $OUT/r6_bench_traced_side.json > $OUT/r6_bench_traced.json 2> $OUT/trace.log
+timeout 600 python3 bench.py --full --side-file $OUT/r6_bench_side.json > $OUT/r6_bench.json 2> $OUT/bench.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --no-cpu-baseline --no-clocks --no-strong-n1 --no-pmc --no-solvers --side-file $OUT/r6_bench_traced_side.json > $OUT/r6_bench_traced.json 2> $OUT/trace.log
 cp $OUT/trace/*/*kernel_stats.csv $OUT/r6_bench_kernel_stats.csv 2>/dev/null
 rm -rf $OUT/trace
 for kv in "w4:-1" "w6:8405186"; do
