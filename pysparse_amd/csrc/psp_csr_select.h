@@ -487,63 +487,6 @@ int csr_spmv_pfx_launch(const psp_csr *A, const double *r, const double *dinv, c
   return PSP_OK;
 }
 
-// q = A (z + beta p_old) with p_new written on the way (csr_spmv_w4_pf); *available = 0 when the
-// operator has no w4 layout (the caller then runs pupdate + csr_spmv_launch)
-int csr_spmv_pfused_launch(const psp_csr *A, const double *r, const double *dinv, const double *p_old,
-                           double *p_new, double *q, double beta, bool first, double *partials, int *nparts,
-                           const PcgDev *dstate, int *available) {
-  *available = 0;
-  // OFF by default: measured at 512^3 it changes nothing (296 / 298 iterations/s with, 291 / 299
-  // without, alternating processes) -- the 8 bytes per row of DRAM traffic it saves are paid
-  // back by reading two arrays instead of one at every neighbour position.  PSP_PCG_PFUSED=1 enables.
-  static const bool on = [] {
-    const char *e = psp::tuning_env("PSP_PCG_PFUSED");
-    return e ? atoi(e) != 0 : false;
-  }();
-  Variant v = decode_variant(A->variant);
-  if (!on || !v.w4 || A->nparts || A->sym_owner || A->nrows != A->ncols || A->nrows < 2) return PSP_OK;
-  psp::CsrExtra *ex;
-  PSP_TRY(ensure_w4(A, &ex));
-  if (ex->dia_state != 1 || ex->dia_no > 8) return PSP_OK;  // register budget: up to 8 offsets
-  const int stripe = w4_stripe(A, v);
-  const int nblk = (A->nrows + kDiaRows - 1) / kDiaRows;
-  const int grid = w4_grid(nblk, stripe);
-  double *pbuf = partials;
-  if (partials && grid > kMaxParts) {
-    PSP_TRY(ensure_big_partials(ex, grid));
-    pbuf = ex->big_partials;
-  }
-  double dc = 0.0;
-  const int pre = !dinv ? 0 : (dinv_constant(dinv, A->nrows, &dc) ? 2 : 1);
-#define PSP_PF(NO, PRE)                                                                             \
-  hipLaunchKernelGGL((csr_spmv_w4_pf<NO, PRE>), dim3(grid), dim3(256), 0, stream(), A->nrows, stripe, \
-                     ex->dia_offs, ex->dia_val, ex->dia_mask, r, dinv, dc, p_old, p_new, q, beta,     \
-                     first ? 1 : 0, pbuf, dstate)
-#define PSP_PF_NO(NO)                                                                               \
-  case NO:                                                                                          \
-    if (pre == 0) PSP_PF(NO, 0);                                                                    \
-    else if (pre == 1) PSP_PF(NO, 1);                                                               \
-    else PSP_PF(NO, 2);                                                                             \
-    break
-  switch (ex->dia_no) {
-    PSP_PF_NO(1); PSP_PF_NO(2); PSP_PF_NO(3); PSP_PF_NO(4); PSP_PF_NO(5); PSP_PF_NO(6); PSP_PF_NO(7); PSP_PF_NO(8);
-    default:
-      return PSP_OK;
-  }
-#undef PSP_PF_NO
-#undef PSP_PF
-  PSP_LAUNCH_CHECK();
-  int np = grid;
-  if (pbuf != partials) {
-    np = kFold;
-    hipLaunchKernelGGL(fold_partials_kernel, dim3(np / 16), dim3(256), 0, stream(), pbuf, grid, partials, np);
-    PSP_LAUNCH_CHECK();
-  }
-  if (nparts) *nparts = np;
-  *available = 1;
-  return PSP_OK;
-}
-
 bool csr_spmv_has_skip(const psp_csr *A) {
   if (A->nparts) {
     for (int p = 0; p < A->nparts; ++p)

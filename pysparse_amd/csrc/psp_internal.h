@@ -105,7 +105,6 @@ class HandleLock {
 #define PSP_API_GUARD psp::HandleLock psp_api_guard_
 #define PSP_API_GUARD_H(...) psp::HandleLock psp_api_guard_({__VA_ARGS__})
 hipStream_t stream();
-hipStream_t swap_stream(hipStream_t s);  // returns the previous stream (graph capture needs a non-null one)
 // Delay injection (round 5; psp_runtime.hip "shake").  The multi-device drivers order their streams by events only; an
 // ordering edge that is missing shows as a wrong vector only when the timing happens to open the window (round 4 found
 // one such race once in ~15 suite runs).  Under PSP_TUNING=1 a test arms the facility (psp_debug_shake or
@@ -520,11 +519,6 @@ inline psp_csr *op_native_csr(const psp_op *op) {
 }
 int csr_spmv_launch(const psp_csr *A, const double *x, double *y, const double *dotv,
                     double *partials, int *nparts, const int *skip = nullptr);
-// PCG: p_new = z + beta p_old and q = A p_new (+ p_new.q partials) in one pass over a w4 operator;
-// *available = 0 when A has no such layout (nothing was launched)
-int csr_spmv_pfused_launch(const psp_csr *A, const double *r, const double *dinv, const double *p_old,
-                           double *p_new, double *q, double beta, bool first, double *partials, int *nparts,
-                           const PcgDev *dstate, int *available);
 // the lazy PCG loop's product on a w4 operator: the pending x update + stagnation scan of the previous iteration, p_new,
 // q = A p_new and the p_new.q partials in one pass (psp_csr.hip csr_spmv_w4_pf<.., XU>); *available = 0 otherwise
 int csr_spmv_pfx_launch(const psp_csr *A, const double *r, const double *dinv, const double *p_old, double *p_new,

@@ -209,12 +209,6 @@ hipStream_t stream() {
   }
   return tl.stream;
 }
-hipStream_t swap_stream(hipStream_t s) {
-  hipStream_t old = stream();
-  tl.stream = s;
-  tl.stream_given = true;
-  return old;
-}
 
 int ensure_device() {
   if (cpu_mode())

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <type_traits>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -267,15 +268,125 @@ int op_apply(const psp_op *op, const double *x_dev, double *y_dev) {
 
 }  // namespace psp
 
+// ====================================================================== device-resident scalars
+//
+// The batched loops (PCG eager / lazy, MINRES, cgs / bicgstab / qmrs) keep their scalars in a state struct on the device.
+// The block that finishes a reduction also takes the scalar step that waits for it (one launch instead of a finishing
+// kernel + a one-thread kernel; the summation order is reduce_block's, so the values are the ones the separate kernels
+// produced), and a `status` word turns every later launch into a no-op once the loop has ended.  The host enqueues a
+// batch of iterations, then reads the state once.
+
+// Step: `State` (PcgDev / MinresDev / KryDev); kVals: values per reduction, 0 = the launcher's `nvals`; kTwo: a second
+// reduction of one value; Out: restrict-qualified unless the reduced values land in the state itself;
+// `static __device__ void run(State *, const double *v0, const double *v1, double *hist)`, taken by thread 0 on the
+// reduced values
+template <class S, int VALS = 0, bool TWO = false, bool IN_STATE = false>
+struct StepOf {
+  using State = S;
+  static constexpr int kVals = TWO ? 1 : VALS;
+  static constexpr bool kTwo = TWO;
+  using Out = std::conditional_t<IN_STATE, double *, double *__restrict__>;
+};
+
+template <class Step>
+__global__ __launch_bounds__(kReduceBlock) void finish_step_kernel(const double *__restrict__ src0, int count0, int nvals,
+                                                                   int stride0, int raw0, typename Step::Out out0,
+                                                                   const double *__restrict__ src1, int count1,
+                                                                   int stride1, int raw1, typename Step::Out out1,
+                                                                   typename Step::State *st, double *__restrict__ hist) {
+  if (st->status) return;  // loop already over: nothing to reduce either
+  __shared__ double sh[kOneBlockGroups];
+  reduce_block(src0, count0, Step::kVals ? Step::kVals : nvals, stride0, raw0 != 0, out0, sh);
+  if constexpr (Step::kTwo) reduce_block(src1, count1, 1, stride1, raw1 != 0, out1, sh);
+  if (threadIdx.x == 0) Step::run(st, out0, out1, hist);
+}
+
+// the group fold (when there are more partials than one block takes) + the finishing block with the step
+template <class Step>
+static int reduce_then(const double *partials, int nparts, int nvals, double *out, typename Step::State *st,
+                       double *hist = nullptr, int fslot = 0) {
+  const double *src;
+  int count, stride;
+  bool raw;
+  PSP_TRY(fold_stage(partials, nparts, nvals, &src, &count, &stride, &raw, fslot));
+  hipLaunchKernelGGL((finish_step_kernel<Step>), dim3(1), dim3(kReduceBlock), 0, stream(), src, count, nvals, stride,
+                     raw ? 1 : 0, out, nullptr, 0, 0, 0, nullptr, st, hist);
+  PSP_LAUNCH_CHECK();
+  return PSP_OK;
+}
+
+// two single-value reductions (their partial sums in different arrays, of different length) and the step that needs
+// both, in ONE finishing launch
+template <class Step>
+static int reduce2_then(const double *p0, int n0, double *out0, const double *p1, int n1, double *out1,
+                        typename Step::State *st, int fslot0, int fslot1) {
+  const double *const parts[2] = {p0, p1};
+  const int np[2] = {n0, n1}, fslot[2] = {fslot0, fslot1};
+  const double *src[2];
+  int count[2], stride[2];
+  bool raw[2];
+  PSP_TRY(fold_stage2(parts, np, fslot, src, count, stride, raw));
+  hipLaunchKernelGGL((finish_step_kernel<Step>), dim3(1), dim3(kReduceBlock), 0, stream(), src[0], count[0], 1,
+                     stride[0], raw[0] ? 1 : 0, out0, src[1], count[1], stride[1], raw[1] ? 1 : 0, out1, st, nullptr);
+  PSP_LAUNCH_CHECK();
+  return PSP_OK;
+}
+
+// A batched loop's state: the thread's state slab on the device (psp_internal.h: nothing to allocate or free), its
+// pinned host mirror, and the optional residual history on the device
+template <class T>
+struct LoopState {
+  T *dev = nullptr, *host = nullptr;
+  double *hist = nullptr;
+  LoopState() = default;
+  LoopState(const LoopState &) = delete;
+  LoopState &operator=(const LoopState &) = delete;
+  ~LoopState() {
+    if (hist) (void)hipFree(hist);
+  }
+  // binds the slab and zeroes the mirror; hist_len > 0: a history of that many slots, NaN until the loop writes them
+  int init(size_t hist_len = 0) {
+    static_assert(sizeof(T) <= kStateBytes, "state slab");
+    Workspace *w;
+    PSP_TRY(workspace(&w));
+    dev = static_cast<T *>(w->state_dev);
+    host = static_cast<T *>(w->state_host);
+    if (hist_len) {
+      const hipError_t e = hipMalloc((void **)&hist, sizeof(double) * hist_len);
+      if (e != hipSuccess) {
+        hist = nullptr;
+        return fail(PSP_ENOMEM, "solver history (%zu doubles): %s", hist_len, hipGetErrorString(e));
+      }
+      PSP_HIP(hipMemsetAsync(hist, 0xff, sizeof(double) * hist_len, stream()));  // NaN
+    }
+    memset(host, 0, sizeof(T));
+    return PSP_OK;
+  }
+  int upload() {
+    PSP_HIP(hipMemcpyAsync(dev, host, sizeof(T), hipMemcpyHostToDevice, stream()));
+    return PSP_OK;
+  }
+  int fetch() {
+    PSP_HIP(hipGetLastError());
+    PSP_HIP(hipMemcpyAsync(host, dev, sizeof(T), hipMemcpyDeviceToHost, stream()));
+    PSP_HIP(hipStreamSynchronize(stream()));
+    return PSP_OK;
+  }
+  // history slots 1 .. cnt to h[1 .. cnt]
+  int fetch_hist(double *h, int cnt) {
+    if (cnt >= 1) PSP_HIP(hipMemcpy(h + 1, hist + 1, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
+    return PSP_OK;
+  }
+};
+
 // ====================================================================== PCG
 
 // ---------------------------------------------------------------------- asynchronous PCG
 //
 // Same algorithm and the same kernels as pcg_device's fused path, but alpha, beta and the
-// exit tests of pcg.c:100-162 are evaluated by one-thread kernels on the device, and a
-// `status` word turns every later launch into a no-op once the loop has ended.  The host
-// enqueues kBatch iterations, then reads the 96-byte state once: two host round trips per
-// ITERATION become one per BATCH (matters when an iteration is shorter than ~1 ms).
+// exit tests of pcg.c:100-162 are evaluated on the device by the block that finishes each
+// reduction.  The host enqueues kBatch iterations, then reads the 96-byte state once: two host
+// round trips per ITERATION become one per BATCH (matters when an iteration is shorter than ~1 ms).
 
 __device__ __forceinline__ void pcg_finish(PcgDev *st, int code, int iter) {
   st->status = 1;
@@ -329,19 +440,12 @@ __device__ __forceinline__ void pcg_scalar_xr(PcgDev *st, const double *__restri
   }
 }
 
-// The scalar recurrences ride in the block that finishes the reduction they depend on (one launch
-// instead of finish_kernel + a one-thread kernel; the summation order is reduce_block's, so the values
-// are the ones the separate kernels produced).
-enum PcgScalarOp { kOpPq = 0, kOpXr = 1, kOpLazyX = 2, kOpLazyPq = 3, kOpLazyR = 4 };
-
-template <int OP>
-__global__ __launch_bounds__(kReduceBlock) void pcg_finish_scalar_kernel(const double *__restrict__ src, int count,
-                                                                         int nvals, int stride, int raw,
-                                                                         double *__restrict__ out, PcgDev *st,
-                                                                         double *__restrict__ hist);
-template <int OP>
-static int pcg_reduce_then(const double *partials, int nparts, int nvals, double *out_dev, PcgDev *st,
-                           double *hist_dev);
+struct PcgPq : StepOf<PcgDev> {
+  static __device__ void run(PcgDev *st, const double *v, const double *, double *) { pcg_scalar_pq(st, v); }
+};
+struct PcgXr : StepOf<PcgDev> {
+  static __device__ void run(PcgDev *st, const double *v, const double *, double *hist) { pcg_scalar_xr(st, v, hist); }
+};
 
 static int pcg_async_enabled() {
   static const int on = [] {
@@ -351,153 +455,51 @@ static int pcg_async_enabled() {
   return on;
 }
 
-// hipGraph replay of the batches is implemented but OFF by default: measured on MI355X it does
-// not beat direct launches here (poisson2d(300): 33.7 vs 30.7 us/iteration; 512^3: 199 vs 210
-// iterations/s) and capture + instantiate costs ~5 ms per solve.  PSP_PCG_GRAPH=1 enables it.
-static int pcg_graph_enabled() {
-  static const int on = [] {
-    const char *e = psp::tuning_env("PSP_PCG_GRAPH");
-    return e ? atoi(e) : 0;
-  }();
-  return on;
+// the state at the head of iteration 1 (both batched loops)
+static int pcg_state_begin(LoopState<PcgDev> &S, double n2b, double tolb, double normr0, double rho0, int maxit,
+                           bool hist) {
+  PSP_TRY(S.init(hist ? (size_t)maxit + 1 : 0));
+  PcgDev *h = S.host;
+  h->rho = rho0;
+  h->rho1 = 1.0;
+  h->normr = normr0;
+  h->tolb = tolb;
+  h->n2b = n2b;
+  h->it = 1;
+  h->maxit = maxit;
+  return S.upload();
 }
 
-// one batch = kBatch iterations' worth of launches on the library stream; every kernel takes
-// its scalars (and the iteration number) from the device state, so all batches are identical
-// p / p2: the direction vector ping-pongs between two buffers when the p-update is folded into
-// the SpMV (csr_spmv_w4_pf reads p_old while it writes p_new); *p is always the current one
-static int pcg_enqueue_batch(psp_csr *Acsr, const double *dinv, int n, double *x, double *r, double **pp,
-                             double **pp2, double *q, PcgDev *st, double *hist_dev, int batch) {
+// runs iterations 1..maxit; on entry r = b - A x, rho0 = r.z != 0, normr0 > tolb.  Every kernel takes its scalars (and
+// the iteration number) from the device state, so all batches are identical.
+static int pcg_async_loop(psp_csr *Acsr, const double *dinv, int n, double *x, double *r, double *p, double *q,
+                          double n2b, double tolb, double normr0, double rho0, int maxit, int *info, int *iter,
+                          double *relres, double *hist) {
+  constexpr int kBatch = 16;
   Workspace *w;
   PSP_TRY(workspace(&w));
-  int np;
-  for (int i = 0; i < batch; ++i) {
-    int fusedp = 0;
-    PSP_TRY(csr_spmv_pfused_launch(Acsr, r, dinv, *pp, *pp2, q, 0.0, false, w->partials, &np, st, &fusedp));
-    if (fusedp) {
-      std::swap(*pp, *pp2);
-    } else {
-      PSP_TRY(k_pupdate(n, r, dinv, 0.0, false, *pp, st));
-      PSP_TRY(csr_spmv_launch(Acsr, *pp, q, *pp, w->partials, &np, &st->status));
+  LoopState<PcgDev> S;
+  PSP_TRY(pcg_state_begin(S, n2b, tolb, normr0, rho0, maxit, hist != nullptr));
+  PcgDev *st = S.dev;
+  int enqueued = 0, np = 0;  // iterations launched so far (never more than maxit: a no-op launch of a 512^3 grid still
+                             // costs ~55 us)
+  do {
+    const int batch = std::max(1, std::min(kBatch, maxit - enqueued));
+    for (int i = 0; i < batch; ++i) {
+      PSP_TRY(k_pupdate(n, r, dinv, 0.0, false, p, st));
+      PSP_TRY(csr_spmv_launch(Acsr, p, q, p, w->partials, &np, &st->status));
+      PSP_TRY(reduce_then<PcgPq>(w->partials, np, 1, w->scal_dev, st));
+      PSP_TRY(k_xr_update(n, 0.0, p, q, dinv, x, r, w->partials, &np, st));
+      PSP_TRY(reduce_then<PcgXr>(w->partials, np, 3, w->scal_dev + 4, st, S.hist));
     }
-    double *p = *pp;
-    PSP_TRY(pcg_reduce_then<kOpPq>(w->partials, np, 1, w->scal_dev, st, nullptr));
-    PSP_TRY(k_xr_update(n, 0.0, p, q, dinv, x, r, w->partials, &np, st));
-    PSP_TRY(pcg_reduce_then<kOpXr>(w->partials, np, 3, w->scal_dev + 4, st, hist_dev));
-  }
-  PSP_LAUNCH_CHECK();
+    enqueued += batch;
+    PSP_TRY(S.fetch());
+  } while (!S.host->status);
+  *info = S.host->info;
+  *iter = S.host->iter;
+  *relres = S.host->relres;
+  if (hist) PSP_TRY(S.fetch_hist(hist, std::min(S.host->iter, maxit)));
   return PSP_OK;
-}
-
-// runs iterations 1..maxit; on entry r = b - A x, rho0 = r.z != 0, normr0 > tolb.
-// The first batch is launched directly (it also performs the lazy table builds of the SpMV);
-// when more batches are needed the batch is captured ONCE into a hipGraph and replayed.
-static int pcg_async_loop(psp_csr *Acsr, const double *dinv, int n, double *x, double *r, double *p,
-                          double *p2, double *q, double n2b, double tolb, double normr0, double rho0, int maxit,
-                          int *info, int *iter, double *relres, double *hist) {
-  constexpr int kBatch = 16;
-  PcgDev *st = nullptr;
-  PcgDev *hst = nullptr;
-  double *hist_dev = nullptr;
-  hipStream_t own = nullptr, prev = nullptr;
-  bool swapped = false;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  int enqueued = 0;  // iterations launched so far (never more than maxit: a no-op launch of a
-                     // 512^3 grid still costs ~55 us)
-  static_assert(sizeof(PcgDev) <= kStateBytes, "state slab");
-  Workspace *wst;
-  PSP_TRY(workspace(&wst));
-  st = static_cast<PcgDev *>(wst->state_dev);  // the thread's state slab (psp_internal.h): nothing to allocate or free
-  hst = static_cast<PcgDev *>(wst->state_host);
-  hipError_t e = hipSuccess;
-  if (hist) e = hipMalloc((void **)&hist_dev, sizeof(double) * ((size_t)maxit + 1));
-  if (e != hipSuccess) {
-    return fail(PSP_ENOMEM, "pcg: state allocation failed: %s", hipGetErrorString(e));
-  }
-  int rc = PSP_OK;
-#define PCG_TRY(call)            \
-  do {                           \
-    rc = (call);                 \
-    if (rc != PSP_OK) goto done; \
-  } while (0)
-#define PCG_HIP(call)                                                \
-  do {                                                               \
-    hipError_t e_ = (call);                                          \
-    if (e_ != hipSuccess) {                                          \
-      rc = fail(PSP_ENODEV, "%s: %s", #call, hipGetErrorString(e_)); \
-      goto done;                                                     \
-    }                                                                \
-  } while (0)
-  if (hist_dev) PCG_HIP(hipMemsetAsync(hist_dev, 0xff, sizeof(double) * ((size_t)maxit + 1), stream()));  // NaN
-  memset(hst, 0, sizeof(PcgDev));
-  hst->rho = rho0;
-  hst->rho1 = 1.0;
-  hst->normr = normr0;
-  hst->tolb = tolb;
-  hst->n2b = n2b;
-  hst->it = 1;
-  hst->maxit = maxit;
-  PCG_HIP(hipMemcpyAsync(st, hst, sizeof(PcgDev), hipMemcpyHostToDevice, stream()));
-  enqueued = std::min(kBatch, maxit);
-  PCG_TRY(pcg_enqueue_batch(Acsr, dinv, n, x, r, &p, &p2, q, st, hist_dev, enqueued));
-  PCG_HIP(hipMemcpyAsync(hst, st, sizeof(PcgDev), hipMemcpyDeviceToHost, stream()));
-  PCG_HIP(hipStreamSynchronize(stream()));
-  if (!hst->status) {
-    // more batches: replay a captured graph (capture needs a non-null stream)
-    bool use_graph = pcg_graph_enabled() != 0;
-    if (use_graph) {
-      if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) == hipSuccess) {
-        prev = swap_stream(own);
-        swapped = true;
-        if (hipStreamBeginCapture(own, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-          const int brc = pcg_enqueue_batch(Acsr, dinv, n, x, r, &p, &p2, q, st, hist_dev, kBatch);
-          const hipError_t ce = hipStreamEndCapture(own, &graph);
-          if (brc != PSP_OK || ce != hipSuccess || graph == nullptr ||
-              hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-            exec = nullptr;
-          }
-        }
-        if (exec == nullptr) {  // capture not possible here: fall back to direct launches
-          (void)hipGetLastError();
-          swap_stream(prev);
-          swapped = false;
-        }
-      }
-      use_graph = exec != nullptr;
-    }
-    while (!hst->status) {
-      if (use_graph) {
-        PCG_HIP(hipGraphLaunch(exec, stream()));
-      } else {
-        const int batch = std::max(1, std::min(kBatch, maxit - enqueued));
-        PCG_TRY(pcg_enqueue_batch(Acsr, dinv, n, x, r, &p, &p2, q, st, hist_dev, batch));
-        enqueued += batch;
-      }
-      PCG_HIP(hipMemcpyAsync(hst, st, sizeof(PcgDev), hipMemcpyDeviceToHost, stream()));
-      PCG_HIP(hipStreamSynchronize(stream()));
-    }
-  }
-  *info = hst->info;
-  *iter = hst->iter;
-  *relres = hst->relres;
-  if (hist) {
-    const int cnt = std::min(hst->iter, maxit);
-    if (cnt >= 1)
-      PCG_HIP(hipMemcpy(hist + 1, hist_dev + 1, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-  }
-done:
-#undef PCG_TRY
-#undef PCG_HIP
-  if (swapped) {
-    (void)hipStreamSynchronize(own);
-    swap_stream(prev);
-  }
-  if (exec) (void)hipGraphExecDestroy(exec);
-  if (graph) (void)hipGraphDestroy(graph);
-  if (own) (void)hipStreamDestroy(own);
-  if (hist_dev) (void)hipFree(hist_dev);
-  return rc;
 }
 
 // ---------------------------------------------------------------------- lazy x-update loop
@@ -574,71 +576,20 @@ __device__ __forceinline__ void pcg_lazy_scalar_r(PcgDev *st, const double *__re
   }
 }
 
-template <int OP>
-__global__ __launch_bounds__(kReduceBlock) void pcg_finish_scalar_kernel(const double *__restrict__ src, int count,
-                                                                         int nvals, int stride, int raw,
-                                                                         double *__restrict__ out, PcgDev *st,
-                                                                         double *__restrict__ hist) {
-  if (st->status) return;  // loop already over: nothing to reduce either
-  __shared__ double sh[kOneBlockGroups];
-  reduce_block(src, count, nvals, stride, raw != 0, out, sh);
-  if (threadIdx.x == 0) {
-    if constexpr (OP == kOpPq) pcg_scalar_pq(st, out);
-    if constexpr (OP == kOpXr) pcg_scalar_xr(st, out, hist);
-    if constexpr (OP == kOpLazyX) pcg_lazy_scalar_x(st, out);
-    if constexpr (OP == kOpLazyPq) pcg_lazy_scalar_pq(st, out);
-    if constexpr (OP == kOpLazyR) pcg_lazy_scalar_r(st, out, hist);
+// the scan of the px pass (v0: nonstag, one value) and p.q of the product (v1) reduced by ONE launch behind the product;
+// thread 0 then takes pcg_lazy_scalar_x's branches and, if the loop goes on, pcg_lazy_scalar_pq's -- the order the
+// reference takes them in (and the order pcg_dist_scalar_xpq_kernel of the row-block drivers uses)
+struct PcgLazyXPq : StepOf<PcgDev, 1, true> {
+  static __device__ void run(PcgDev *st, const double *v0, const double *v1, double *) {
+    pcg_lazy_scalar_x(st, v0);
+    pcg_lazy_scalar_pq(st, v1);
   }
-}
+};
+struct PcgLazyR : StepOf<PcgDev> {
+  static __device__ void run(PcgDev *st, const double *v, const double *, double *hist) { pcg_lazy_scalar_r(st, v, hist); }
+};
 
-// lazy loop: the scan of the px pass (`x`: nonstag, one value) and p.q of the product (`q`) reduced by ONE launch behind
-// the product; thread 0 then takes pcg_lazy_scalar_x's branches and, if the loop goes on, pcg_lazy_scalar_pq's -- the
-// order the separate launches run them in (and the order pcg_dist_scalar_xpq_kernel of the row-block drivers uses)
-__global__ __launch_bounds__(kReduceBlock) void pcg_finish_xpq_kernel(const double *__restrict__ src_x, int count_x,
-                                                                      int stride_x, int raw_x,
-                                                                      const double *__restrict__ src_q, int count_q,
-                                                                      int stride_q, int raw_q, double *__restrict__ out_x,
-                                                                      double *__restrict__ out_q, PcgDev *st) {
-  if (st->status) return;
-  __shared__ double sh[kOneBlockGroups];
-  reduce_block(src_x, count_x, 1, stride_x, raw_x != 0, out_x, sh);
-  reduce_block(src_q, count_q, 1, stride_q, raw_q != 0, out_q, sh);
-  if (threadIdx.x == 0) {
-    pcg_lazy_scalar_x(st, out_x);
-    pcg_lazy_scalar_pq(st, out_q);
-  }
-}
-
-// the group fold (when there are more partials than one block takes) + the finishing block with scalar update OP
-template <int OP>
-static int pcg_reduce_then(const double *partials, int nparts, int nvals, double *out_dev, PcgDev *st,
-                           double *hist_dev) {
-  const double *src;
-  int count, stride;
-  bool raw;
-  PSP_TRY(fold_stage(partials, nparts, nvals, &src, &count, &stride, &raw));
-  hipLaunchKernelGGL((pcg_finish_scalar_kernel<OP>), dim3(1), dim3(kReduceBlock), 0, stream(), src, count, nvals,
-                     stride, raw ? 1 : 0, out_dev, st, hist_dev);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
-}
-
-static int pcg_reduce_xpq(Workspace *w, const double *parts_x, int np_x, const double *parts_q, int np_q, double *out_x,
-                          double *out_q, PcgDev *st) {
-  const double *const parts[2] = {parts_x, parts_q};
-  const int np[2] = {np_x, np_q}, fslot[2] = {2, 0};
-  const double *src[2];
-  int count[2], stride[2];
-  bool raw[2];
-  (void)w;
-  PSP_TRY(fold_stage2(parts, np, fslot, src, count, stride, raw));
-  hipLaunchKernelGGL(pcg_finish_xpq_kernel, dim3(1), dim3(kReduceBlock), 0, stream(), src[0], count[0], stride[0],
-                     raw[0] ? 1 : 0, src[1], count[1], stride[1], raw[1] ? 1 : 0, out_x, out_q, st);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
-}
-
-static int pcg_lazy_enabled() {  // read per solve (tools/reduce_ab.py alternates it inside one process)
+static int pcg_lazy_enabled() {  // read per solve (tools/lazy_ab.py alternates it inside one process)
   const char *e = psp::tuning_env("PSP_PCG_LAZYX");
   return e ? atoi(e) : 1;
 }
@@ -655,98 +606,53 @@ static int pcg_lazypf_mode(int n) {
   return e ? atoi(e) : (n >= (1 << 21) ? 1 : 0);
 }
 
+// *folded: whether the folded form ran -- it needs an index-free layout of <= 8 offsets, which iteration 1 finds out
 static int pcg_async_loop_lazy(psp_csr *Acsr, const double *dinv, int n, double *x, double *r, double *p, double *p2,
                                double *q, double n2b, double tolb, double normr0, double rho0, int maxit,
-                               int *info, int *iter, double *relres, double *hist) {
+                               int *info, int *iter, double *relres, double *hist, bool *folded) {
   constexpr int kBatch = 16;
   double *const P[2] = {p, p2};  // folded form: iteration e reads p_{e-1} from P[(e-1) & 1] and writes p_e to P[e & 1]
   int usepf = (p2 && pcg_lazypf_mode(n)) ? 1 : 0;
+  *folded = false;
   Workspace *w;
   PSP_TRY(workspace(&w));
-  PcgDev *st = nullptr, *hst = nullptr;
-  double *hist_dev = nullptr;
-  static_assert(sizeof(PcgDev) <= kStateBytes, "state slab");
-  Workspace *wst;
-  PSP_TRY(workspace(&wst));
-  st = static_cast<PcgDev *>(wst->state_dev);  // the thread's state slab (psp_internal.h): nothing to allocate or free
-  hst = static_cast<PcgDev *>(wst->state_host);
-  hipError_t e = hipSuccess;
-  if (hist) e = hipMalloc((void **)&hist_dev, sizeof(double) * ((size_t)maxit + 1));
-  if (e != hipSuccess) {
-    return fail(PSP_ENOMEM, "pcg: state allocation failed: %s", hipGetErrorString(e));
-  }
-  int rc = PSP_OK;
+  LoopState<PcgDev> S;
+  PSP_TRY(pcg_state_begin(S, n2b, tolb, normr0, rho0, maxit, hist != nullptr));
+  PcgDev *st = S.dev;
   int enqueued = 0, np = 0;
   double *stag_parts = w->partials + 2 * (size_t)kMaxParts;  // slot 2: the scan's partials
-  const bool merge_xpq = [] {  // read per solve: tools/reduce_ab.py alternates it inside one process
-    const char *e = psp::tuning_env("PSP_PCG_MERGE_XPQ");
-    return e ? atoi(e) != 0 : true;
-  }();
-#define PCG_TRY(call)            \
-  do {                           \
-    rc = (call);                 \
-    if (rc != PSP_OK) goto done; \
-  } while (0)
-#define PCG_HIP(call)                                                \
-  do {                                                               \
-    hipError_t e_ = (call);                                          \
-    if (e_ != hipSuccess) {                                          \
-      rc = fail(PSP_ENODEV, "%s: %s", #call, hipGetErrorString(e_)); \
-      goto done;                                                     \
-    }                                                                \
-  } while (0)
-  if (hist_dev) PCG_HIP(hipMemsetAsync(hist_dev, 0xff, sizeof(double) * ((size_t)maxit + 1), stream()));
-  memset(hst, 0, sizeof(PcgDev));
-  hst->rho = rho0;
-  hst->rho1 = 1.0;
-  hst->normr = normr0;
-  hst->tolb = tolb;
-  hst->n2b = n2b;
-  hst->it = 1;
-  hst->maxit = maxit;
-  PCG_HIP(hipMemcpyAsync(st, hst, sizeof(PcgDev), hipMemcpyHostToDevice, stream()));
   do {
     const int batch = std::max(1, std::min(kBatch, maxit - enqueued));
     for (int i = 0; i < batch; ++i) {
       // round 4: the scan of the px pass is reduced TOGETHER with p.q, behind the product (one launch for both up to
       // n = 2^25, the group fold + one beyond) -- 5 launches per iteration instead of 9 (7 beyond 2^25).  The product
       // then also runs in the one iteration that the scan ends (-5) or that starts with rho == 0 / beta == 0: its q is
-      // not used.  Same scalar steps in the same order on the same reduced values: the same bits
-      // (PSP_PCG_MERGE_XPQ=0 keeps the scan's reduction in front of the product: A/B and test_pcg_loop_variants_agree).
+      // not used.  Same scalar steps in the same order on the same reduced values: the same bits.
       int np_x = 0;
       if (usepf) {
         const int e = enqueued + i + 1;
-        int av = 0;
-        PCG_TRY(csr_spmv_pfx_launch(Acsr, r, dinv, P[(e - 1) & 1], P[e & 1], q, x, w->partials, &np, st, &av));
-        if (av) {
-          PCG_TRY(pcg_reduce_xpq(w, stag_parts, np, w->partials, np, w->scal_dev + 8, w->scal_dev, st));
-          PCG_TRY(k_r_update(n, 0.0, q, dinv, r, w->partials, &np, st));
-          PCG_TRY(pcg_reduce_then<kOpLazyR>(w->partials, np, 2, w->scal_dev + 4, st, hist_dev));
-          continue;
-        }
-        usepf = 0;  // no index-free layout (decided by the operator: this is iteration 1, p = P[0] is untouched)
+        PSP_TRY(csr_spmv_pfx_launch(Acsr, r, dinv, P[(e - 1) & 1], P[e & 1], q, x, w->partials, &np, st, &usepf));
+        np_x = np;  // no index-free layout: usepf = 0, decided by the operator in iteration 1 (p = P[0] is untouched)
       }
-      PCG_TRY(k_px_update(n, r, dinv, p, x, w->partials, &np_x, st));
-      if (!merge_xpq) PCG_TRY(pcg_reduce_then<kOpLazyX>(stag_parts, np_x, 1, w->scal_dev + 8, st, nullptr));
-      PCG_TRY(csr_spmv_launch(Acsr, p, q, p, w->partials, &np, &st->status));
-      if (merge_xpq)
-        PCG_TRY(pcg_reduce_xpq(w, stag_parts, np_x, w->partials, np, w->scal_dev + 8, w->scal_dev, st));
-      else
-        PCG_TRY(pcg_reduce_then<kOpLazyPq>(w->partials, np, 1, w->scal_dev, st, nullptr));
-      PCG_TRY(k_r_update(n, 0.0, q, dinv, r, w->partials, &np, st));
-      PCG_TRY(pcg_reduce_then<kOpLazyR>(w->partials, np, 2, w->scal_dev + 4, st, hist_dev));
+      if (!usepf) {
+        PSP_TRY(k_px_update(n, r, dinv, p, x, w->partials, &np_x, st));
+        PSP_TRY(csr_spmv_launch(Acsr, p, q, p, w->partials, &np, &st->status));
+      }
+      PSP_TRY(reduce2_then<PcgLazyXPq>(stag_parts, np_x, w->scal_dev + 8, w->partials, np, w->scal_dev, st, 2, 0));
+      PSP_TRY(k_r_update(n, 0.0, q, dinv, r, w->partials, &np, st));
+      PSP_TRY(reduce_then<PcgLazyR>(w->partials, np, 2, w->scal_dev + 4, st, S.hist));
     }
-    PCG_HIP(hipGetLastError());
     enqueued += batch;
-    PCG_HIP(hipMemcpyAsync(hst, st, sizeof(PcgDev), hipMemcpyDeviceToHost, stream()));
-    PCG_HIP(hipStreamSynchronize(stream()));
-  } while (!hst->status);
+    PSP_TRY(S.fetch());
+  } while (!S.host->status);
+  *folded = usepf != 0;
+  PcgDev *hst = S.host;
   if (usepf) p = P[hst->it & 1];  // the direction of the iteration the loop ended in
   if (hst->xpend) {  // the x update (and scan) of the last iteration
     double s[1];
-    PCG_TRY(k_x_update(n, hst->alpha_x, p, x, w->partials, &np, nullptr));
-    PCG_TRY(finish_partials(stag_parts, np, 1, w->scal_dev + 8));
-    PCG_TRY(fetch_scalars(w->scal_dev + 8, 1, s));
+    PSP_TRY(k_x_update(n, hst->alpha_x, p, x, w->partials, &np, nullptr));
+    PSP_TRY(finish_partials(stag_parts, np, 1, w->scal_dev + 8));
+    PSP_TRY(fetch_scalars(w->scal_dev + 8, 1, s));
     if (hst->pend_maxit) {
       const bool stag = hst->stag0 || s[0] == 0.0;
       hst->info = stag ? -5 : -1;               // pcg.c:159-165
@@ -757,16 +663,8 @@ static int pcg_async_loop_lazy(psp_csr *Acsr, const double *dinv, int n, double 
   *info = hst->info;
   *iter = hst->iter;
   *relres = hst->relres;
-  if (hist) {
-    const int cnt = std::min(hst->iter, maxit);
-    if (cnt >= 1)
-      PCG_HIP(hipMemcpy(hist + 1, hist_dev + 1, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-  }
-done:
-#undef PCG_TRY
-#undef PCG_HIP
-  if (hist_dev) (void)hipFree(hist_dev);
-  return rc;
+  if (hist) PSP_TRY(S.fetch_hist(hist, std::min(hst->iter, maxit)));
+  return PSP_OK;
 }
 
 // Acsr_forced != nullptr: the caller has moved the system into the numbering of a renumbered copy of A
@@ -816,7 +714,7 @@ static int pcg_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_force
   psp_csr *Acsr = Acsr_forced ? Acsr_forced : op_native_csr(A);
   const double *dinv = Acsr_forced ? dinv_forced : fused_dinv(K);
   const bool fused = Acsr != nullptr && (Acsr_forced || K == nullptr || dinv != nullptr);
-  double *p2 = nullptr;  // second direction buffer of the p-update-in-SpMV path (csr_spmv_w4_pf)
+  double *p2 = nullptr;  // second direction buffer of the lazy loop's folded product (csr_spmv_w4_pf)
   PSP_TRY(mem.alloc(n, &r));
   if (fused) {
     // q = A p is THE product of an iteration: q takes the output role, p (and its twin p2) the input role (psp_place.hip)
@@ -913,17 +811,18 @@ static int pcg_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_force
     const int lazy_mode = pcg_lazy_enabled();
     // launches per iteration: a reduction is one launch up to 4096 partial sums (n <= 2^21), group fold + finish beyond
     const int rl = n > (1 << 21) ? 2 : 0;
-    if ((lazy_mode == 2 || (lazy_mode == 1 && (n < (1 << 24) || n >= 3 * (1 << 23)))) && !pcg_graph_enabled()) {
+    if (lazy_mode == 2 || (lazy_mode == 1 && (n < (1 << 24) || n >= 3 * (1 << 23)))) {
       // bytes per row beside the product: px_update 40 (r, p, x read; p, x written) + r_update 24 (q, r read; r written);
-      // folded form: the product forms p and x itself (x read and written, p written: 32 - 8 for the p it reads anyway)
-      const bool pf = p2 && pcg_lazypf_mode(n);
+      // folded form: the product forms p and x itself (x read and written, p written: 32 - 8 for the p it reads anyway).
+      // Noted once the loop has found out which of the two it ran.
+      bool pf = false;
+      const int rc = pcg_async_loop_lazy(Acsr, dinv, n, x, r, p, p2, q, n2b, tolb, normr, rho_next, maxit, info, iter,
+                                         relres, hist, &pf);
       note_solve(pf ? "pcg_lazy_pf" : "pcg_lazy", (pf ? 4 : 5) + rl, (pf ? 56 : 64) + 16 * dstream, dstream);
-      return pcg_async_loop_lazy(Acsr, dinv, n, x, r, p, p2, q, n2b, tolb, normr, rho_next, maxit, info, iter,
-                                 relres, hist);
+      return rc;
     }
     note_solve("pcg_eager", 6 + rl, 72 + 16 * dstream, dstream);
-    return pcg_async_loop(Acsr, dinv, n, x, r, p, p2, q, n2b, tolb, normr, rho_next, maxit, info, iter,
-                          relres, hist);
+    return pcg_async_loop(Acsr, dinv, n, x, r, p, q, n2b, tolb, normr, rho_next, maxit, info, iter, relres, hist);
   }
   note_solve("pcg_host_scalars", -1, -1, dstream);
 
@@ -957,18 +856,10 @@ static int pcg_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_force
         break;
       }
     }
-    int fusedp = 0;
-    if (fused)  // p = z (+ beta p) and q = A p in one pass where the operator has the w4 layout
-      PSP_TRY(csr_spmv_pfused_launch(Acsr, r, dinv, p, p2, q, beta, it == 1, w->partials, &np, nullptr, &fusedp));
-    if (fusedp) {
-      std::swap(p, p2);
-    } else {
-      PSP_TRY(k_pupdate(n, zsrc, zdinv, it == 1 ? 0.0 : beta, it == 1, p));  // pcg.c:106, :113-114
-    }
+    PSP_TRY(k_pupdate(n, zsrc, zdinv, it == 1 ? 0.0 : beta, it == 1, p));  // pcg.c:106, :113-114
 
     // q = A p, pq = p.q (pcg.c:116-117)
-    if (fusedp) {
-    } else if (Acsr) {
+    if (Acsr) {
       PSP_TRY(csr_spmv_launch(Acsr, p, q, p, w->partials, &np));
     } else {
       PSP_TRY(op_apply(A, p, q));
@@ -1155,30 +1046,14 @@ __device__ __forceinline__ void minres_scalar_beta(MinresDev *st, const double *
   }
 }
 
-template <int OP>
-__global__ __launch_bounds__(kReduceBlock) void minres_finish_scalar_kernel(const double *__restrict__ src, int count,
-                                                                            int stride, int raw, double *__restrict__ out,
-                                                                            MinresDev *st, double *__restrict__ hist) {
-  if (st->status) return;
-  __shared__ double sh[kOneBlockGroups];
-  reduce_block(src, count, 1, stride, raw != 0, out, sh);
-  if (threadIdx.x == 0) {
-    if constexpr (OP == kMrAlpha) minres_scalar_alpha(st, out);
-    if constexpr (OP == kMrBeta) minres_scalar_beta(st, out, hist);
+struct MinresAlpha : StepOf<MinresDev, 1> {
+  static __device__ void run(MinresDev *st, const double *v, const double *, double *) { minres_scalar_alpha(st, v); }
+};
+struct MinresBeta : StepOf<MinresDev, 1> {
+  static __device__ void run(MinresDev *st, const double *v, const double *, double *hist) {
+    minres_scalar_beta(st, v, hist);
   }
-}
-
-template <int OP>
-static int minres_reduce_then(const double *partials, int nparts, double *out_dev, MinresDev *st, double *hist_dev) {
-  const double *src;
-  int count, stride;
-  bool raw;
-  PSP_TRY(fold_stage(partials, nparts, 1, &src, &count, &stride, &raw));
-  hipLaunchKernelGGL((minres_finish_scalar_kernel<OP>), dim3(1), dim3(kReduceBlock), 0, stream(), src, count, stride,
-                     raw ? 1 : 0, out_dev, st, hist_dev);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
-}
+};
 
 static int minres_async_enabled() {
   static const int on = [] {
@@ -1197,38 +1072,9 @@ static int minres_async_loop(psp_csr *Acsr, const double *dinv, bool hasK, int n
   constexpr int kBatch = 16;
   Workspace *w;
   PSP_TRY(workspace(&w));
-  MinresDev *st = nullptr, *hst = nullptr;
-  double *hist_dev = nullptr;
-  static_assert(sizeof(MinresDev) <= kStateBytes, "state slab");
-  st = static_cast<MinresDev *>(w->state_dev);  // the thread's state slab (psp_internal.h)
-  hst = static_cast<MinresDev *>(w->state_host);
-  hipError_t e = hipSuccess;
-  if (hist) e = hipMalloc((void **)&hist_dev, sizeof(double) * ((size_t)it_max + 1));
-  if (e != hipSuccess) {
-    return fail(PSP_ENOMEM, "minres: state allocation failed: %s", hipGetErrorString(e));
-  }
-  if (hist_dev) (void)hipMemsetAsync(hist_dev, 0xff, sizeof(double) * ((size_t)it_max + 1), stream());  // NaN, like the PCG loops
-  int rc = PSP_OK;
-  int enqueued = 0, np = 0;
-#define MR_TRY(call)             \
-  do {                           \
-    rc = (call);                 \
-    if (rc != PSP_OK) goto done; \
-  } while (0)
-#define MR_HIP(call)                                                 \
-  do {                                                               \
-    hipError_t e_ = (call);                                          \
-    if (e_ != hipSuccess) {                                          \
-      rc = fail(PSP_ENODEV, "%s: %s", #call, hipGetErrorString(e_)); \
-      goto done;                                                     \
-    }                                                                \
-  } while (0)
-  bool v_ready = false;
-  const bool wx_vnext = [] {  // PSP_MINRES_WXV (tuning switch, read per solve): 0 keeps v = y / beta a pass of its own
-    const char *e = psp::tuning_env("PSP_MINRES_WXV");
-    return e ? atoi(e) != 0 : true;
-  }();
-  memset(hst, 0, sizeof(MinresDev));
+  LoopState<MinresDev> S;
+  PSP_TRY(S.init(hist ? (size_t)it_max + 1 : 0));
+  MinresDev *st = S.dev, *hst = S.host;
   hst->beta = beta0;
   hst->beta_old = 1.0;
   hst->c = 1.0;
@@ -1242,7 +1088,9 @@ static int minres_async_loop(psp_csr *Acsr, const double *dinv, bool hasK, int n
   hst->iter = 1;
   hst->it_max = it_max;
   hst->info = -1;
-  MR_HIP(hipMemcpyAsync(st, hst, sizeof(MinresDev), hipMemcpyHostToDevice, stream()));
+  PSP_TRY(S.upload());
+  int enqueued = 0, np = 0;
+  bool v_ready = false;
   do {
     const int batch = std::max(1, std::min(kBatch, it_max - enqueued));
     for (int i = 0; i < batch; ++i) {
@@ -1250,50 +1098,40 @@ static int minres_async_loop(psp_csr *Acsr, const double *dinv, bool hasK, int n
       const double *vsrc = hasK ? y : v_hat;  // unnormalised Lanczos vector of this iteration
       int scaled = 0;
       if (!hasK || y2)
-        MR_TRY(csr_spmv_scaled_launch(Acsr, vsrc, 1.0, av, w->partials, &np, &scaled, &st->skip, &st->beta));
+        PSP_TRY(csr_spmv_scaled_launch(Acsr, vsrc, 1.0, av, w->partials, &np, &scaled, &st->skip, &st->beta));
       if (!scaled) {
         // v = y / beta: a pass of its own in the first iteration only -- afterwards the previous iteration's w / x update
         // has written it (k_minres_wx_vnext below)
-        if (!v_ready) MR_TRY(k_scale_div(n, vsrc, 1.0, v, st));
-        MR_TRY(csr_spmv_launch(Acsr, v, av, v, w->partials, &np, &st->skip));
+        if (!v_ready) PSP_TRY(k_scale_div(n, vsrc, 1.0, v, st));
+        PSP_TRY(csr_spmv_launch(Acsr, v, av, v, w->partials, &np, &st->skip));
       }
-      MR_TRY(minres_reduce_then<kMrAlpha>(w->partials, np, w->scal_dev, st, nullptr));
+      PSP_TRY(reduce_then<MinresAlpha>(w->partials, np, 1, w->scal_dev, st));
       // v_hat = Av - c1 v_hat - c2 v_hat_old; y = K v_hat; beta^2 = v_hat . y (:131-143)
       double *ynew = (scaled && hasK) ? y2 : y;
-      MR_TRY(k_lanczos(n, av, 0.0, 0.0, v_hat, v_hat_old, dinv, ynew, w->partials, &np, st));
+      PSP_TRY(k_lanczos(n, av, 0.0, 0.0, v_hat, v_hat_old, dinv, ynew, w->partials, &np, st));
       std::swap(v_hat, v_hat_old);
       if (scaled && hasK) std::swap(y, y2);
-      MR_TRY(minres_reduce_then<kMrBeta>(w->partials, np, w->scal_dev + 4, st, hist_dev));
+      PSP_TRY(reduce_then<MinresBeta>(w->partials, np, 1, w->scal_dev + 4, st, S.hist));
       // w, x update (:172-180); the new w lands in w_old's buffer
-      if (!scaled && wx_vnext) {
+      if (!scaled) {
         // the unnormalised vector of the NEXT iteration: y (with a preconditioner: the Lanczos pass just wrote it) or the
         // new v_hat (the names were swapped above)
-        MR_TRY(k_minres_wx_vnext(n, v, hasK ? y : v_hat, wv, w_old, x, st));
+        PSP_TRY(k_minres_wx_vnext(n, v, hasK ? y : v_hat, wv, w_old, x, st));
         v_ready = true;
       } else {
-        MR_TRY(k_minres_wx(n, scaled ? vsrc : v, 0.0, 0.0, 0.0, 0.0, wv, w_old, x, scaled != 0, 1.0, st));
+        PSP_TRY(k_minres_wx(n, vsrc, 0.0, 0.0, 0.0, 0.0, wv, w_old, x, true, 1.0, st));
       }
       std::swap(wv, w_old);
     }
-    MR_HIP(hipGetLastError());
     enqueued += batch;
-    MR_HIP(hipMemcpyAsync(hst, st, sizeof(MinresDev), hipMemcpyDeviceToHost, stream()));
-    MR_HIP(hipStreamSynchronize(stream()));
+    PSP_TRY(S.fetch());
   } while (!hst->status && !hst->stop);
   *info = hst->info;
   *iter = hst->iter;
   if (hst->info == 0 || hst->info == -1) *relres = hst->relres;  // untouched on -3 / -6, as in the reference
-  if (hist) {
-    // -3 / -6 end the running iteration before its history slot is written: that slot keeps the caller's fill
-    const int cnt = std::min(hst->iter, it_max) - ((hst->info == -3 || hst->info == -6) ? 1 : 0);
-    if (cnt >= 1)
-      MR_HIP(hipMemcpy(hist + 1, hist_dev + 1, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-  }
-done:
-#undef MR_TRY
-#undef MR_HIP
-  if (hist_dev) (void)hipFree(hist_dev);
-  return rc;
+  // -3 / -6 end the running iteration before its history slot is written: that slot keeps the caller's fill
+  if (hist) PSP_TRY(S.fetch_hist(hist, std::min(hst->iter, it_max) - ((hst->info == -3 || hst->info == -6) ? 1 : 0)));
+  return PSP_OK;
 }
 
 static int minres_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_forced, const double *dinv_forced,
@@ -1614,7 +1452,7 @@ int apply_or_copy(const psp_op *K, long n, const double *x, double *y) {
 // Round 5 (VERDICT r4 "Next" #5).  The fused loops below (native matrix + None / jacobi(1)) used to read every reduced
 // value back to the host -- through mapped memory and polling since round 4, but still one GPU-idle round trip per
 // reduction: 2 (cgs), 4 (bicgstab), 4 (qmrs) per iteration, ~12 us each at 1024^2.  Now the recurrences of cgs.c /
-// bicgstab.c / qmrs.c are evaluated by the thread that finishes each reduction (kry_finish_kernel<OP>: reduce_block's
+// bicgstab.c / qmrs.c are evaluated by the thread that finishes each reduction (KryStep<OP>: reduce_block's
 // canonical order, so the reduced values are the ones the host used to get; then the same expressions in the same order,
 // IEEE double, -ffp-contract=off on both sides), the vector kernels take their coefficients from the KryDev state
 // (KryArg) and do nothing once its status is set, and the host enqueues kKryBatch iterations between two reads of the
@@ -1626,7 +1464,7 @@ constexpr int kKryBatch = 8;
 
 enum KryOp {
   kCgsD, kCgsR,
-  kBicgD1, kBicgTs, kBicgTt, kBicgXr,
+  kBicgD1, kBicgTt, kBicgXr,
   kQmrsDelta0, kQmrsEps, kQmrsRho, kQmrsDelta,
 };
 // cgs registers
@@ -1670,13 +1508,9 @@ __device__ __forceinline__ void qmrs_head(KryDev *S) {
   S->r[QM_CC] = S->r[QM_XI1] * (S->r[QM_DELTA] / S->r[QM_EPS0]);
 }
 
+// the recurrences that follow the reduction(s) of OP, on the registers the reduction wrote
 template <int OP>
-__global__ __launch_bounds__(kReduceBlock) void kry_finish_kernel(const double *__restrict__ src, int count, int nvals,
-                                                                  int stride, int raw, KryDev *S, int out_base) {
-  if (S->status) return;
-  __shared__ double sh[kOneBlockGroups];
-  reduce_block(src, count, nvals, stride, raw != 0, S->r + out_base, sh);
-  if (threadIdx.x != 0) return;
+__device__ __forceinline__ void kry_step(KryDev *S) {
   double *r = S->r;
   if constexpr (OP == kCgsD) {  // cgs.c: alpha = rho / (v . r0)
     r[CG_ALPHA] = r[CG_RHO] / r[CG_D];
@@ -1692,7 +1526,6 @@ __global__ __launch_bounds__(kReduceBlock) void kry_finish_kernel(const double *
     }
   }
   if constexpr (OP == kBicgD1) r[BI_ALPHA] = r[BI_RHO1] / r[BI_D1];  // alpha = rho / (rhat . v)
-  if constexpr (OP == kBicgTs) {}                                    // t . s lands in r[BI_D1]
   if constexpr (OP == kBicgTt) r[BI_OMEGA] = r[BI_D1] / r[BI_D2];    // omega = (t . s) / (t . t)
   if constexpr (OP == kBicgXr) {  // res, the omega == 0 return, the loop test, then the next iteration's head
     const double res = sqrt(r[BI_RR]);
@@ -1755,69 +1588,10 @@ __global__ __launch_bounds__(kReduceBlock) void kry_finish_kernel(const double *
   }
 }
 
+// kBicgTt: t . s (the product's epilogue) and t . t (a pass of its own) in ONE finishing launch, then omega
 template <int OP>
-int kry_reduce_then(const double *partials, int nparts, int nvals, KryDev *S, int out_base, int fslot = 0) {
-  const double *src;
-  int count, stride;
-  bool raw;
-  PSP_TRY(fold_stage(partials, nparts, nvals, &src, &count, &stride, &raw, fslot));
-  hipLaunchKernelGGL((kry_finish_kernel<OP>), dim3(1), dim3(kReduceBlock), 0, stream(), src, count, nvals, stride,
-                     raw ? 1 : 0, S, out_base);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
-}
-
-// two single-value reductions (their partial sums in different arrays, of different length) and the step that needs both,
-// in ONE finishing launch -- bicgstab: t . s (the product's epilogue) and t . t (a pass of its own), then omega
-template <int OP>
-__global__ __launch_bounds__(kReduceBlock) void kry_finish2_kernel(const double *__restrict__ src0, int count0, int stride0,
-                                                                   int raw0, int out0, const double *__restrict__ src1,
-                                                                   int count1, int stride1, int raw1, int out1, KryDev *S) {
-  if (S->status) return;
-  __shared__ double sh[kOneBlockGroups];
-  reduce_block(src0, count0, 1, stride0, raw0 != 0, S->r + out0, sh);
-  reduce_block(src1, count1, 1, stride1, raw1 != 0, S->r + out1, sh);
-  if (threadIdx.x != 0) return;
-  double *r = S->r;
-  if constexpr (OP == kBicgTt) r[BI_OMEGA] = r[BI_D1] / r[BI_D2];  // omega = (t . s) / (t . t)
-}
-
-template <int OP>
-int kry_reduce2_then(const double *p0, int n0, int out0, const double *p1, int n1, int out1, KryDev *S) {
-  const double *parts[2] = {p0, p1};
-  const int np[2] = {n0, n1}, fslot[2] = {0, 1};
-  const double *src[2];
-  int count[2], stride[2];
-  bool raw[2];
-  PSP_TRY(fold_stage2(parts, np, fslot, src, count, stride, raw));
-  hipLaunchKernelGGL((kry_finish2_kernel<OP>), dim3(1), dim3(kReduceBlock), 0, stream(), src[0], count[0], stride[0],
-                     raw[0] ? 1 : 0, out0, src[1], count[1], stride[1], raw[1] ? 1 : 0, out1, S);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
-}
-
-// the state on the device + its pinned host mirror
-struct KryState {
-  KryDev *dev = nullptr, *host = nullptr;  // in the thread's state slab (psp_internal.h)
-  int init() {
-    static_assert(sizeof(KryDev) <= kStateBytes, "state slab");
-    Workspace *w;
-    PSP_TRY(workspace(&w));
-    dev = static_cast<KryDev *>(w->state_dev);
-    host = static_cast<KryDev *>(w->state_host);
-    memset(host, 0, sizeof(KryDev));
-    return PSP_OK;
-  }
-  int upload() {
-    PSP_HIP(hipMemcpyAsync(dev, host, sizeof(KryDev), hipMemcpyHostToDevice, stream()));
-    return PSP_OK;
-  }
-  int fetch() {
-    PSP_HIP(hipGetLastError());
-    PSP_HIP(hipMemcpyAsync(host, dev, sizeof(KryDev), hipMemcpyDeviceToHost, stream()));
-    PSP_HIP(hipStreamSynchronize(stream()));
-    return PSP_OK;
-  }
+struct KryStep : StepOf<KryDev, 0, OP == kBicgTt, true> {
+  static __device__ void run(KryDev *S, const double *, const double *, double *) { kry_step<OP>(S); }
 };
 
 bool kry_devscal_enabled() {  // read per solve (A/B inside one process)
@@ -1870,7 +1644,7 @@ static int cgs_device(const psp_op *A, const psp_op *K, int n, double *x, const 
     double sc[2];
     int np;
     if (kry_devscal_enabled() && maxit >= 1 && csr_spmv_has_skip(Acsr)) {
-      KryState st;
+      LoopState<KryDev> st;
       PSP_TRY(st.init());
       st.host->r[CG_RHO] = rho;
       st.host->r[CG_THR] = bnrm_sq * tol_sq;
@@ -1880,11 +1654,11 @@ static int cgs_device(const psp_op *A, const psp_op *K, int n, double *x, const 
       do {
         for (int k = 0; k < kKryBatch; ++k) {
           PSP_TRY(csr_spmv_launch(Acsr, kp, v, r0, w->partials, &np, &S->status));
-          PSP_TRY(kry_reduce_then<kCgsD>(w->partials, np, 1, S, CG_D));
+          PSP_TRY(reduce_then<KryStep<kCgsD>>(w->partials, np, 1, S->r + CG_D, S));
           PSP_TRY(k_cgs_q(n, u, v, x, q, tmp2, dinv, 0.0, KryArg{S, CG_ALPHA}));
           PSP_TRY(csr_spmv_launch(Acsr, tmp2, tmp, nullptr, nullptr, nullptr, &S->status));
           PSP_TRY(k_cgs_r(n, r, tmp, r0, 0.0, w->partials, &np, KryArg{S, CG_ALPHA}));
-          PSP_TRY(kry_reduce_then<kCgsR>(w->partials, np, 2, S, CG_RES));
+          PSP_TRY(reduce_then<KryStep<kCgsR>>(w->partials, np, 2, S->r + CG_RES, S));
           PSP_TRY(k_cgs_p(n, r, q, p, u, kp, dinv, 0.0, KryArg{S, CG_BETA}));
         }
         PSP_TRY(st.fetch());
@@ -1998,7 +1772,7 @@ static int bicgstab_device(const psp_op *A, const psp_op *K, int n, double *x, c
     if (kry_devscal_enabled() && maxit >= 1 && csr_spmv_has_skip(Acsr)) {
       *iter = 1;
       if (rho_im1 == 0.0) return PSP_OK;  // the first iteration's head, on the host
-      KryState st;
+      LoopState<KryDev> st;
       PSP_TRY(st.init());
       st.host->r[BI_RHO1] = rho_im1;
       st.host->r[BI_RES0] = res0;
@@ -2012,15 +1786,16 @@ static int bicgstab_device(const psp_op *A, const psp_op *K, int n, double *x, c
         for (int k = 0; k < kKryBatch; ++k) {
           PSP_TRY(k_bicg_p(n, r, v, p, ph, dinv, 0.0, 0.0, false, KryArg{S, BI_BETA, BI_OMEGA}));  // first: S->iter == 1
           PSP_TRY(csr_spmv_launch(Acsr, ph, v, rhat, w->partials, &np, &S->status));
-          PSP_TRY(kry_reduce_then<kBicgD1>(w->partials, np, 1, S, BI_D1));
+          PSP_TRY(reduce_then<KryStep<kBicgD1>>(w->partials, np, 1, S->r + BI_D1, S));
           PSP_TRY(k_bicg_s(n, r, v, s, sh, dinv, 0.0, KryArg{S, BI_ALPHA}));
           PSP_TRY(csr_spmv_launch(Acsr, sh, t, s, w->partials, &np, &S->status));
           // t . t into the second array of partial sums (runs once more after the loop has ended: its result is ignored);
           // ONE finishing launch for t . s, t . t and omega
           PSP_TRY(k_dot(n, t, t, w->partials + kMaxParts, &np2));
-          PSP_TRY(kry_reduce2_then<kBicgTt>(w->partials, np, BI_D1, w->partials + kMaxParts, np2, BI_D2, S));
+          PSP_TRY(reduce2_then<KryStep<kBicgTt>>(w->partials, np, S->r + BI_D1, w->partials + kMaxParts, np2,
+                                                 S->r + BI_D2, S, 0, 1));
           PSP_TRY(k_bicg_xr(n, x, ph, sh, s, t, r, rhat, 0.0, 0.0, w->partials, &np, KryArg{S, BI_ALPHA, BI_OMEGA}));
-          PSP_TRY(kry_reduce_then<kBicgXr>(w->partials, np, 2, S, BI_RR));
+          PSP_TRY(reduce_then<KryStep<kBicgXr>>(w->partials, np, 2, S->r + BI_RR, S));
         }
         PSP_TRY(st.fetch());
       } while (!st.host->status);
@@ -2129,7 +1904,7 @@ static int qmrs_device(const psp_op *A, const psp_op *K, int n, double *x, const
     int np;
     bool have_delta = false;
     if (kry_devscal_enabled() && csr_spmv_has_skip(Acsr)) {
-      KryState st;
+      LoopState<KryDev> st;
       PSP_TRY(st.init());
       double *R = st.host->r;
       R[QM_RHO0] = rho0;
@@ -2147,16 +1922,16 @@ static int qmrs_device(const psp_op *A, const psp_op *K, int n, double *x, const
       KryDev *S = st.dev;
       // K v1 . v1 of the first iteration, then its head (the later ones get theirs from the d / x pass)
       PSP_TRY(k_qmrs_kv(n, v1, kv, dinv, w->partials, &np));
-      PSP_TRY(kry_reduce_then<kQmrsDelta0>(w->partials, np, 1, S, QM_OUT));
+      PSP_TRY(reduce_then<KryStep<kQmrsDelta0>>(w->partials, np, 1, S->r + QM_OUT, S));
       do {
         for (int k = 0; k < kKryBatch; ++k) {
           PSP_TRY(k_qmrs_pg(n, v1, kv, p, g, 0.0, KryArg{S, QM_CC}));
           PSP_TRY(csr_spmv_launch(Acsr, g, t, g, w->partials, &np, &S->status));
-          PSP_TRY(kry_reduce_then<kQmrsEps>(w->partials, np, 1, S, QM_OUT));
+          PSP_TRY(reduce_then<KryStep<kQmrsEps>>(w->partials, np, 1, S->r + QM_OUT, S));
           PSP_TRY(k_qmrs_v(n, t, v1, 0.0, w->partials, &np, KryArg{S, QM_BETA}));
-          PSP_TRY(kry_reduce_then<kQmrsRho>(w->partials, np, 1, S, QM_OUT));
+          PSP_TRY(reduce_then<KryStep<kQmrsRho>>(w->partials, np, 1, S->r + QM_OUT, S));
           PSP_TRY(k_qmrs_dx(n, p, d, x, v1, kv, dinv, 0.0, 0.0, 0.0, w->partials, &np, KryArg{S, QM_ETA0, QM_CC2, QM_RHO1INV}));
-          PSP_TRY(kry_reduce_then<kQmrsDelta>(w->partials, np, 1, S, QM_OUT));
+          PSP_TRY(reduce_then<KryStep<kQmrsDelta>>(w->partials, np, 1, S->r + QM_OUT, S));
         }
         PSP_TRY(st.fetch());
       } while (!st.host->status);
@@ -2291,10 +2066,10 @@ static int gmres_device(const psp_op *A, const psp_op *K, int n, double *x, cons
   std::vector<double> H((size_t)dim * m1), s(m1), cs(dim), sn(dim), hhost((size_t)dim + 2);
   double *hdev = nullptr;  // h[0..i] and ||w||^2 of the current column, on the device
   PSP_TRY(mem.alloc((size_t)dim + 2, &hdev));
-  // PSP_GMRES_CHAIN (A/B; read per solve): 0 one read-back per Gram-Schmidt step, 1 the chain with a finishing launch per
-  // step (round 4), 2 (default) the finishing reduction folded into the next step's kernel where a step is launch-bound
+  // PSP_GMRES_CHAIN (tuning switch, read per solve): 1 the Gram-Schmidt chain with a finishing launch per step (round 4;
+  // the form beyond 2^20 rows), 2 (default) the finishing reduction folded into the next step's kernel where a step is
+  // launch-bound
   const char *chain_env = psp::tuning_env("PSP_GMRES_CHAIN");
-  const bool mgs_chain = !chain_env || atoi(chain_env) != 0;
   const bool mgs_fold = (!chain_env || atoi(chain_env) == 2) && vec_grid(*w, n) <= 2048;  // n <= 2^20
 #define GH(i, j) (H[(size_t)(j) * m1 + (i)])
   int i, j, k, iter = 0;
@@ -2323,50 +2098,28 @@ static int gmres_device(const psp_op *A, const psp_op *K, int n, double *x, cons
       PSP_TRY(apply_or_copy(K, n, V[i], W[i]));
       PSP_TRY(op_apply(A, W[i], V[i + 1]));
       // modified Gram-Schmidt (gmres.c:110-116): the axpy of step k and the dot of step k + 1 (at the end: the norm)
-      // share one pass over V[i + 1]
-      static const bool mgs_fused = [] {
-        const char *e = psp::tuning_env("PSP_GMRES_FUSED");  // 0: one dot and one axpy kernel per step (A/B)
-        return e ? atoi(e) != 0 : true;
-      }();
-      if (mgs_fused && mgs_chain) {
-        // the whole Gram-Schmidt chain of the column enqueued at once (round 4): step k's axpy takes h[k] from where step
-        // k - 1's reduction left it on the device; the host reads h[0..i] and the norm's square in ONE go at the end
-        // (one scalar read-back per inner iteration instead of i + 2) -- the same operations on the same values
-        int np;
-        PSP_TRY(k_dot(n, V[i + 1], V[0], w->partials, &np));
-        if (mgs_fold) {
-          // round 5: step k adds the partial sums of step k - 1 itself (every workgroup, reduce_block: the finishing block's
-          // bits) -- i + 3 launches for the column instead of 2 i + 4
-          double *P[2] = {w->partials, w->partials + kMaxParts};
-          for (k = 0; k <= i; k++)
-            PSP_TRY(k_axpy_dot_chain(n, P[k & 1], np, hdev + k, V[k], V[i + 1], k < i ? V[k + 1] : nullptr, P[(k + 1) & 1], &np));
-          PSP_TRY(finish_partials(P[(i + 1) & 1], np, 1, hdev + i + 1));
-        } else {
-          PSP_TRY(finish_partials(w->partials, np, 1, hdev));
-          for (k = 0; k <= i; k++) {
-            PSP_TRY(k_axpy_dot(n, 0.0, V[k], V[i + 1], k < i ? V[k + 1] : nullptr, w->partials, &np, hdev + k));
-            PSP_TRY(finish_partials(w->partials, np, 1, hdev + k + 1));
-          }
-        }
-        for (k = 0; k < i + 2; k += 16) PSP_TRY(fetch_scalars(hdev + k, std::min(16, i + 2 - k), hhost.data() + k));
-        for (k = 0; k <= i; k++) GH(k, i) = hhost[k];
-        d = hhost[i + 1];
-      } else if (mgs_fused) {
-        PSP_TRY(B.dot(V[i + 1], V[0], &d));
-        for (k = 0; k <= i; k++) {
-          GH(k, i) = d;
-          int np;
-          PSP_TRY(k_axpy_dot(n, -GH(k, i), V[k], V[i + 1], k < i ? V[k + 1] : nullptr, w->partials, &np));
-          PSP_TRY(reduce_fetch(w, np, 1, &d));
-        }
+      // share one pass over V[i + 1].  The whole chain of the column is enqueued at once (round 4): step k's axpy takes
+      // h[k] from where step k - 1's reduction left it on the device; the host reads h[0..i] and the norm's square in ONE
+      // go at the end (one scalar read-back per inner iteration instead of i + 2) -- the same operations on the same values
+      int np;
+      PSP_TRY(k_dot(n, V[i + 1], V[0], w->partials, &np));
+      if (mgs_fold) {
+        // round 5: step k adds the partial sums of step k - 1 itself (every workgroup, reduce_block: the finishing block's
+        // bits) -- i + 3 launches for the column instead of 2 i + 4
+        double *P[2] = {w->partials, w->partials + kMaxParts};
+        for (k = 0; k <= i; k++)
+          PSP_TRY(k_axpy_dot_chain(n, P[k & 1], np, hdev + k, V[k], V[i + 1], k < i ? V[k + 1] : nullptr, P[(k + 1) & 1], &np));
+        PSP_TRY(finish_partials(P[(i + 1) & 1], np, 1, hdev + i + 1));
       } else {
+        PSP_TRY(finish_partials(w->partials, np, 1, hdev));
         for (k = 0; k <= i; k++) {
-          PSP_TRY(B.dot(V[i + 1], V[k], &d));
-          GH(k, i) = d;
-          PSP_TRY(B.axpy(-GH(k, i), V[k], V[i + 1]));
+          PSP_TRY(k_axpy_dot(n, 0.0, V[k], V[i + 1], k < i ? V[k + 1] : nullptr, w->partials, &np, hdev + k));
+          PSP_TRY(finish_partials(w->partials, np, 1, hdev + k + 1));
         }
-        PSP_TRY(B.dot(V[i + 1], V[i + 1], &d));
       }
+      for (k = 0; k < i + 2; k += 16) PSP_TRY(fetch_scalars(hdev + k, std::min(16, i + 2 - k), hhost.data() + k));
+      for (k = 0; k <= i; k++) GH(k, i) = hhost[k];
+      d = hhost[i + 1];
       GH(i + 1, i) = sqrt(d);
       PSP_TRY(k_scal(n, 1.0 / GH(i + 1, i), V[i + 1]));
       for (k = 0; k < i; k++) app_rot(&GH(k, i), &GH(k + 1, i), cs[k], sn[k]);

@@ -389,8 +389,7 @@ def test_minres_poisson_vs_oracle(oracle, p2d):
 
 
 def test_pcg_loop_variants_agree(golden, p2d, monkeypatch):
-    """host-scalar loop (PSP_PCG_ASYNC=0), device-scalar loop (default), its hipGraph replay
-    (PSP_PCG_GRAPH=1), the p-update folded into the SpMV (PSP_PCG_PFUSED=1, both loops), the dinv
+    """host-scalar loop (PSP_PCG_ASYNC=0), device-scalar loop (default), the dinv
     stream kept (PSP_DINV_CONST=0) and the lazy x update (PSP_PCG_LAZYX=2 forces it at this size; it is
     the default from 2^25 unknowns on: x update folded into the next p-update pass) are the same algorithm: identical info / iteration counts / iterates."""
     import subprocess
@@ -403,9 +402,7 @@ def test_pcg_loop_variants_agree(golden, p2d, monkeypatch):
         "print(json.dumps([r[0], r[1], r[2], float(x[0]), float(x[n // 2]), float(np.nansum(r[3]))]))"
     ) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
-    for env in ({"PSP_PCG_ASYNC": "0"}, {}, {"PSP_PCG_GRAPH": "1"}, {"PSP_PCG_PFUSED": "1"},
-                {"PSP_PCG_PFUSED": "1", "PSP_PCG_ASYNC": "0"}, {"PSP_DINV_CONST": "0"},
-                {"PSP_DINV_CONST": "0", "PSP_PCG_PFUSED": "1"}, {"PSP_PCG_LAZYX": "2"},
+    for env in ({"PSP_PCG_ASYNC": "0"}, {}, {"PSP_DINV_CONST": "0"}, {"PSP_PCG_LAZYX": "2"},
                 {"PSP_PCG_LAZYX": "2", "PSP_DINV_CONST": "0"},
                 # round 5: the lazy loop with p update AND pending x update folded into the product (csr_spmv_w4_pf<XU>)
                 {"PSP_PCG_LAZYX": "2", "PSP_PCG_LAZYPF": "1"}, {"PSP_PCG_LAZYX": "2", "PSP_PCG_LAZYPF": "0"},
@@ -420,6 +417,44 @@ def test_pcg_loop_variants_agree(golden, p2d, monkeypatch):
     for o in outs:
         assert (o[0], o[1]) == (0, cases["G2"]["iter"])
     assert all(o == outs[0] for o in outs)  # bitwise: same products, same reduction order
+
+
+def test_last_solve_info_names_the_lazy_pcg_loop_that_ran():
+    """From 2^21 rows the lazy PCG loop folds the p update and the pending x update into the product (pcg_lazy_pf) where
+    the operator allows it: an index-free layout of <= 8 offsets, which the loop finds out in its first iteration.
+    psp_last_solve_info must name the loop that ran -- a 9-point stencil on 1449^2 points (index-free, 9 offsets) runs
+    the plain lazy loop, with its launch and byte counts; the 5-point stencil of the same grid runs the folded one."""
+    from pysparse_amd import device as dev
+    m = 1449
+    n = m * m
+    assert n >= 1 << 21
+    rows = np.arange(n, dtype=np.int32)
+    gi, gj = np.divmod(rows, m)
+    cols = np.full((n, 9), -1, dtype=np.int32)
+    for t, (di, dj) in enumerate((a, c) for a in (-1, 0, 1) for c in (-1, 0, 1)):  # increasing offsets di * m + dj
+        ok = (gi + di >= 0) & (gi + di < m) & (gj + dj >= 0) & (gj + dj < m)
+        cols[ok, t] = rows[ok] + di * m + dj
+    mask = cols >= 0
+    col = cols[mask]
+    val = np.where(col == np.repeat(rows, mask.sum(axis=1)), 8.0, -1.0)
+    ind = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int32)
+    nine = dev.DeviceCSR.from_arrays((n, n), ind, col, val)
+    b = np.ones(n)
+    got = {}
+    dev.set_single_kernel_loops(False)  # launch-per-phase loops only
+    try:
+        for name, D in (("nine", nine), ("five", dev.DeviceCSR.poisson(m, m))):
+            x = np.zeros(n)
+            dev.pcg(D, b, x, 0.0, 3, dev.DeviceJacobi(D))
+            got[name] = dev.last_solve_info()
+    finally:
+        dev.set_single_kernel_loops(True)
+    loop, info = got["nine"]  # a reduction beyond 2^21 rows: group fold + finishing block (2 launches more)
+    assert loop == "pcg_lazy" and info["launches"] == 5 + 2, got
+    assert info["vec_bytes_per_row"] == 64 + 16 * info["dinv_streamed"], got
+    loop, info = got["five"]
+    assert loop == "pcg_lazy_pf" and info["launches"] == 4 + 2, got
+    assert info["vec_bytes_per_row"] == 56 + 16 * info["dinv_streamed"], got
 
 
 def test_minres_loop_variants_agree(oracle):
