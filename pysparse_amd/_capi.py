@@ -39,6 +39,7 @@ psp_k_jacobi psp_pcgstate_create psp_pcgstate_destroy psp_pcgstate_init psp_pcgs
 psp_kd_px_update psp_kd_csr_matvec_overlap psp_kd_pcg_scalar_xpq psp_kd_r_update psp_kd_pcg_scalar_r
 psp_minresstate_create psp_minresstate_destroy psp_minresstate_init psp_minresstate_fetch psp_minresstate_hist
 psp_kd_minres_scale psp_kd_minres_matvec psp_kd_minres_lanczos psp_kd_minres_scalar psp_kd_minres_wx
+psp_bv_tdot psp_bv_gemv psp_bv_rotate psp_jdsym psp_op_apply_host psp_debug_ritz psp_debug_lu_factor psp_debug_lu_solve
 """.split()
 
 
@@ -56,6 +57,21 @@ class MinresStatus(C.Structure):
 
 WAIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)
 HOST_APPLY_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
+LINSOLVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double),
+                          C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                          C.POINTER(C.c_double))
+LIN_PCG, LIN_MINRES, LIN_CGS, LIN_BICGSTAB, LIN_QMRS, LIN_GMRES, LIN_CALLBACK = range(7)
+
+
+class JdsymParams(C.Structure):
+    """psp_jdsym_params_t"""
+    _fields_ = [("kmax", C.c_int), ("jmax", C.c_int), ("jmin", C.c_int), ("itmax", C.c_int), ("blksize", C.c_int),
+                ("blkwise", C.c_int), ("optype", C.c_int), ("linitmax", C.c_int), ("strategy", C.c_int),
+                ("clvl", C.c_int), ("tau", C.c_double), ("jdtol", C.c_double), ("eps_tr", C.c_double),
+                ("toldecay", C.c_double), ("linsolver", C.c_int), ("linsolve", LINSOLVE_FN),
+                ("linsolve_ctx", C.c_void_p), ("projector", HOST_APPLY_FN), ("projector_ctx", C.c_void_p),
+                ("V0_host", C.c_void_p), ("v0_cols", C.c_int), ("v0_row_stride", C.c_ssize_t),
+                ("v0_col_stride", C.c_ssize_t)]
 
 
 class PspError(RuntimeError):
@@ -168,6 +184,12 @@ def _declare(L):
         "psp_last_solve_info": [C.c_char_p, i, C.POINTER(i)], "psp_set_single_kernel_loops": [i],
         "psp_csr_release_arrays": [vp], "psp_csr_prepare": [vp, C.c_longlong], "psp_sss_prepare": [vp, C.c_longlong],
         "psp_csr_setup_info": [vp, C.POINTER(d)], "psp_sss_setup_info": [vp, C.POINTER(d)],
+        "psp_bv_tdot": [i, i, vp, i64, vp, vp], "psp_bv_gemv": [i, i, vp, i64, vp, d, d, vp],
+        "psp_bv_rotate": [i, i, vp, i64, vp, i, i, i, i],
+        "psp_jdsym": [vp, vp, vp, i, C.POINTER(JdsymParams), pi, vp, vp, pi, pi],
+        "psp_op_apply_host": [vp, vp, vp],
+        "psp_debug_ritz": [i, vp, i, d, i, vp, vp, i], "psp_debug_lu_factor": [i, vp, i, vp],
+        "psp_debug_lu_solve": [i, vp, i, vp, vp],
     }
     for name, argtypes in sig.items():
         f = getattr(L, name)

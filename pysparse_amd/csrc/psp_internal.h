@@ -402,7 +402,15 @@ struct psp_sss {
   bool host = false;  // PSP_DEVICE=cpu: ind / col / val / diag are host arrays (psp_cpu.hip)
 };
 
-enum psp_op_kind { PSP_OP_CSR = 1, PSP_OP_SSS = 2, PSP_OP_JACOBI = 3, PSP_OP_CALLBACK = 4, PSP_OP_SSOR = 5 };
+enum psp_op_kind {
+  PSP_OP_CSR = 1,
+  PSP_OP_SSS = 2,
+  PSP_OP_JACOBI = 3,
+  PSP_OP_CALLBACK = 4,
+  PSP_OP_SSOR = 5,
+  PSP_OP_CORREQ = 6  // the projected operator / preconditioner of jdsym's correction equation (psp_jdsym.hip)
+};
+struct psp_correq;
 
 struct psp_op {
   int kind = 0;
@@ -415,6 +423,27 @@ struct psp_op {
   void *ctx = nullptr;
   // pinned staging for callback operators
   double *hx = nullptr, *hy = nullptr;
+  // PSP_OP_CORREQ: the correction-equation system and which half of it this operator applies (0 matvec, 1 precon)
+  psp_correq *ce = nullptr;
+  int ce_precon = 0;
+};
+
+// The correction equation of Jacobi-Davidson as a composite device operator (correq.c:4-23): A, M and K are the caller's
+// operators (M, K may be absent), Q / Qm / Y the converged vectors, M Q and K^-1 M Q as column-major device blocks of
+// leading dimension n, Hlu / Hpiv the factors of H = Qm' Y (host: psp_jdsym.hip factors them; device: what the kernel of
+// the small solve reads).  op_apply requires y != x, so the operator owns two work vectors; h holds the k coefficients
+// of a projection on the device between the block dot product and the block update (no host round trip).
+struct psp_correq {
+  int n = 0, k = 0, kmax = 0, optype = 0;
+  double theta = 0.0;
+  const psp_op *A = nullptr, *M = nullptr, *K = nullptr;
+  double *Q = nullptr, *Qm = nullptr, *Y = nullptr;
+  double *Hlu_host = nullptr;
+  int *Hpiv_host = nullptr;
+  double *Hlu_dev = nullptr;
+  int *Hpiv_dev = nullptr;
+  double *w1 = nullptr, *w2 = nullptr;
+  double *h = nullptr;
 };
 
 struct psp_jacobi {
@@ -433,6 +462,12 @@ namespace psp {
 // the matrix / preconditioner behind it and, for a jacobi, the matrix its extra sweeps multiply with
 inline void op_lock_add(HandleLock &L, const psp_op *op) {
   if (!op || op->kind == 0) return;
+  if (op->kind == PSP_OP_CORREQ && op->ce) {  // the handles behind A, M and K
+    op_lock_add(L, op->ce->A);
+    op_lock_add(L, op->ce->M);
+    op_lock_add(L, op->ce->K);
+    return;
+  }
   L.add(op);
   L.add(op->csr);
   L.add(op->sss);
@@ -510,6 +545,17 @@ struct KryArg {
 };
 // y = op(x) on device vectors; y must not alias x
 int op_apply(const psp_op *op, const double *x_dev, double *y_dev);
+// psp_jdsym.hip: the eight cases of correq.c:137-236
+int correq_apply(const psp_op *op, const double *x_dev, double *y_dev);
+// psp_bvec.hip: tall-skinny block-vector kernels (column c of an n x m block at V + c*ld, ld >= n); h lives on the device
+int bv_tdot(long n, int m, const double *V, long ld, const double *x, double *h_dev);
+int bv_gemv(long n, int m, const double *V, long ld, const double *h_dev, double alpha, double beta, double *y);
+int bv_rotate(long n, int j, double *V, long ld, const double *U_host, int ldu, int u0, int jn, int dst0);
+void bv_trim();  // psp_trim: the calling thread's partial-sum and U buffers
+// psp_solvers.hip: the six Krylov loops at their device-pointer level, no locking, no argument checks (psp_jdsym.hip calls
+// them on the correction equation with the handles already locked); which = PSP_LIN_*
+int krylov_dev(int which, const psp_op *A, const psp_op *K, int n, double *x_dev, const double *b_dev, double tol, int maxit,
+               int *info, int *iter, double *relres);
 // the csr that a native operator multiplies with (csr, or sss->full); nullptr otherwise
 inline psp_csr *op_native_csr(const psp_op *op) {
   if (!op) return nullptr;

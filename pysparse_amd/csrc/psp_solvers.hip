@@ -251,6 +251,8 @@ int op_apply(const psp_op *op, const double *x_dev, double *y_dev) {
       return jacobi_apply_dev(op->jac, x_dev, y_dev);
     case PSP_OP_SSOR:
       return ssor_apply_dev(op->ssor, x_dev, y_dev);
+    case PSP_OP_CORREQ:
+      return correq_apply(op, x_dev, y_dev);
     case PSP_OP_CALLBACK: {
       // SpMatrix_Matvec / SpMatrix_Precon (spmatrixmodule.c:169-248): the callee sees host
       // arrays, so bridge the device vectors through pinned staging buffers
@@ -2453,6 +2455,28 @@ int psp_kd_minres_wx(const psp_minresstate_t *s, int n, const double *v_dev, con
 
 }  // extern "C"
 
+// the device-pointer level of all six loops for callers inside the library (psp_jdsym.hip: the correction equation)
+namespace psp {
+int krylov_dev(int which, const psp_op *A, const psp_op *K, int n, double *x_dev, const double *b_dev, double tol, int maxit,
+               int *info, int *iter, double *relres) {
+  switch (which) {
+    case PSP_LIN_PCG:
+      return pcg_device(A, K, n, x_dev, b_dev, tol, maxit, info, iter, relres, nullptr);
+    case PSP_LIN_MINRES:
+      return minres_device(A, K, n, x_dev, b_dev, tol, maxit, info, iter, relres, nullptr);
+    case PSP_LIN_CGS:
+      return cgs_device(A, K, n, x_dev, b_dev, tol, maxit, info, iter, relres);
+    case PSP_LIN_BICGSTAB:
+      return bicgstab_device(A, K, n, x_dev, b_dev, tol, maxit, info, iter, relres);
+    case PSP_LIN_QMRS:
+      return qmrs_device(A, K, n, x_dev, b_dev, tol, maxit, info, iter, relres);
+    case PSP_LIN_GMRES:
+      return gmres_device(A, K, n, x_dev, b_dev, tol, maxit, 20, info, iter, relres);  // dim = 20: the krylov module's default
+  }
+  return fail(PSP_EINVAL, "unknown linear solver %d", which);
+}
+}  // namespace psp
+
 // ====================================================================== C ABI
 
 // multi-device operands (psp_multi.hip): *multi = the row-partitioned matrix behind A (nullptr: an ordinary operand
@@ -2488,6 +2512,7 @@ extern "C" {
 int psp_trim(void) {
   g_pool.trim();
   host_stage_trim();
+  bv_trim();
   return PSP_OK;
 }
 
