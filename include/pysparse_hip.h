@@ -440,6 +440,41 @@ int psp_bv_gemv(int n, int m, const double *V_dev, int64_t ld, const double *h_d
                 double *y_dev);
 int psp_bv_rotate(int n, int j, double *V_dev, int64_t ld, const double *U_host, int ldu, int u0, int jn, int dst0);
 
+/* ------------------------------------------------------------------ products and PCG on blocks of vectors
+ * Y[:, c] = A X[:, c] for c < k with the matrix streamed once per group of up to eight columns (psp_spmm.hip).  Blocks
+ * are column-major like the psp_bv_* ones: column c of X starts at X + c*ldx (ldx >= ncols), column c of Y at
+ * Y + c*ldy (ldy >= nrows); rows beyond the matrix order and columns >= k are never written.  Column c has the BITS of
+ * psp_csr_matvec / psp_sss_matvec on X[:, c] (every kernel adds a row's products left to right).  Handles whose product
+ * is csr_spmv_w4 (<= 9 offsets; psp_csr_poisson_big and psp_csr_release_arrays handles included) run the index-free block
+ * kernel csr_spmm_w4, every other handle that still has its CSR arrays runs csr_spmm_rows; an sss_mat multiplies through
+ * its expanded mirror.  PSP_EINVAL: a multi-device matrix, a matrix stored in parts, a released handle with more than 9
+ * offsets, X and Y overlapping, k < 1, a leading dimension below the vector length.  PSP_DEVICE=cpu: PSP_ENODEV.
+ * The *_dev forms enqueue on the calling thread's stream and return without synchronising.
+ * psp_op_apply_block_dev: the same for any operator -- csr / sss as above, jacobi with steps = 1 one scaling kernel, every
+ * other kind (ssor, host callback, jacobi with more steps) column by column. */
+int psp_csr_matmat(psp_csr_t *A, int k, const double *X_host, long ldx, double *Y_host, long ldy);
+int psp_csr_matmat_dev(psp_csr_t *A, int k, const double *X_dev, long ldx, double *Y_dev, long ldy);
+int psp_sss_matmat(psp_sss_t *S, int k, const double *X_host, long ldx, double *Y_host, long ldy);
+int psp_sss_matmat_dev(psp_sss_t *S, int k, const double *X_dev, long ldx, double *Y_dev, long ldy);
+int psp_op_apply_block_dev(const psp_op_t *op, int k, const double *X_dev, long ldx, double *Y_dev, long ldy);
+
+/* info[c], iter[c], relres[c] = pcg(A, B[:, c], X[:, c], tol, maxit[, K]) for c < k, the k recurrences advanced by ONE
+ * loop (psp_batch.hip): q = A p is one block product, the vector updates take per-column alpha / beta, the dot products
+ * of all columns finish in one reduction.  Column c ends with the info / iter / relres and the x of psp_pcg run alone on it
+ * -- bit for bit: the partial sums are formed and added in the order of the loop the single solve runs (launch per phase,
+ * or the one-kernel loop of small systems; beside the brick loop of 3-D grids of middle size: to rounding, as that loop
+ * itself agrees with the others) -- and is frozen from then on: nothing
+ * of it is written again while the loop goes on for the others.  The loop always runs in the stored numbering of A: on an
+ * irregular handle whose single solves go through the renumbered copy the two differ at rounding level, like the two
+ * numberings themselves.  Launches and host read-backs per iteration do not grow with k when A is native with an
+ * index-free product and K is absent or a jacobi with steps = 1 (psp_last_solve_info names "pcg_batch"); other products
+ * and preconditioners are applied column by column inside the same loop.  A multi-device matrix gives PSP_EINVAL,
+ * PSP_DEVICE=cpu PSP_ENODEV.  ldx, ldb >= n. */
+int psp_pcg_batch(const psp_op_t *A, const psp_op_t *K, int n, int k, double *X_host, long ldx, const double *B_host,
+                  long ldb, double tol, int maxit, int *info, int *iter, double *relres);
+int psp_pcg_batch_dev(const psp_op_t *A, const psp_op_t *K, int n, int k, double *X_dev, long ldx, const double *B_dev,
+                      long ldb, double tol, int maxit, int *info, int *iter, double *relres);
+
 /* -------------------------------------------------------------------- jdsym
  * kconv, lambda, Q, it, it_inner = jdsym(A, M, K, kmax, tau, jdtol, itmax, linsolver, ...): the Jacobi-Davidson
  * eigensolver for A x = lambda M x, A and M symmetric, M positive definite or absent (jdsym.c:207-621, wrapper

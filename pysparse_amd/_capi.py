@@ -40,6 +40,7 @@ psp_kd_px_update psp_kd_csr_matvec_overlap psp_kd_pcg_scalar_xpq psp_kd_r_update
 psp_minresstate_create psp_minresstate_destroy psp_minresstate_init psp_minresstate_fetch psp_minresstate_hist
 psp_kd_minres_scale psp_kd_minres_matvec psp_kd_minres_lanczos psp_kd_minres_scalar psp_kd_minres_wx
 psp_bv_tdot psp_bv_gemv psp_bv_rotate psp_jdsym psp_op_apply_host psp_debug_ritz psp_debug_lu_factor psp_debug_lu_solve
+psp_csr_matmat psp_csr_matmat_dev psp_sss_matmat psp_sss_matmat_dev psp_op_apply_block_dev psp_pcg_batch psp_pcg_batch_dev
 """.split()
 
 
@@ -190,6 +191,11 @@ def _declare(L):
         "psp_op_apply_host": [vp, vp, vp],
         "psp_debug_ritz": [i, vp, i, d, i, vp, vp, i], "psp_debug_lu_factor": [i, vp, i, vp],
         "psp_debug_lu_solve": [i, vp, i, vp, vp],
+        "psp_csr_matmat": [vp, i, vp, C.c_long, vp, C.c_long], "psp_csr_matmat_dev": [vp, i, vp, C.c_long, vp, C.c_long],
+        "psp_sss_matmat": [vp, i, vp, C.c_long, vp, C.c_long], "psp_sss_matmat_dev": [vp, i, vp, C.c_long, vp, C.c_long],
+        "psp_op_apply_block_dev": [vp, i, vp, C.c_long, vp, C.c_long],
+        "psp_pcg_batch": [vp, vp, i, i, vp, C.c_long, vp, C.c_long, d, i, pi, pi, pd],
+        "psp_pcg_batch_dev": [vp, vp, i, i, vp, C.c_long, vp, C.c_long, d, i, pi, pi, pd],
     }
     for name, argtypes in sig.items():
         f = getattr(L, name)

@@ -175,11 +175,14 @@ static long reorder_after() {
   return v;
 }
 
+// set around a product that must stay in the stored numbering (csr_spmv_launch_stored)
+static thread_local bool tl_stored_only = false;
+
 static int pick_scattered(const psp_csr *A, ChunkTable *t, psp::CsrExtra **ex_out, int *mode, bool count = false) {
   *mode = 0;
   if (t->nb != 0 || t->max_blocks <= 0) return PSP_OK;
   const int var = A->variant < 0 ? 0 : A->variant;
-  if (((var >> 27) & 1) == 0) {
+  if (((var >> 27) & 1) == 0 && !tl_stored_only) {
     psp::CsrExtra *exr;
     bool due;
     {
@@ -863,6 +866,15 @@ int csr_spmv_launch(const psp_csr *A, const double *x, double *y, const double *
   PSP_LAUNCH_CHECK();
   if (nparts) *nparts = grid;
   return PSP_OK;
+}
+
+int csr_spmv_launch_stored(const psp_csr *A, const double *x, double *y, const double *dotv, double *partials,
+                           int *nparts, const int *skip) {
+  const bool was = tl_stored_only;
+  tl_stored_only = true;
+  const int rc = csr_spmv_launch(A, x, y, dotv, partials, nparts, skip);
+  tl_stored_only = was;
+  return rc;
 }
 
 // ---- SpMV split around a halo exchange (multi-GPU): the chunks whose rows lie inside

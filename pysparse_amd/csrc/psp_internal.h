@@ -545,6 +545,24 @@ struct KryArg {
 };
 // y = op(x) on device vectors; y must not alias x
 int op_apply(const psp_op *op, const double *x_dev, double *y_dev);
+// psp_spmm.hip: Y[:, c] = op(X[:, c]), c < k, on column-major device blocks (column c at X + c*ldx / Y + c*ldy); Y must not
+// overlap X.  Native csr / sss: the block product kernels; jacobi with steps == 1: one scaling kernel; every other kind:
+// op_apply column by column -- so the result is defined for every operator, with the bits of op_apply on each column
+int op_apply_block(const psp_op *op, int k, const double *X, long ldx, double *Y, long ldy);
+// the block product at its device-pointer level.  skip: per-column flags on the device (nullptr: every column); a column
+// whose flag is not 0 is neither computed nor written.  partials != nullptr: the X[:, c] . Y[:, c] partial sums of column c at
+// partials + c*pstride in the order of the single-vector product's fused dot; *nparts = their count per column, or 0 when
+// this handle's product leaves them in an order the block kernels do not reproduce (nothing written)
+int csr_spmm_check(const char *what, const psp_csr *A);
+int csr_spmm_launch(const psp_csr *A, int k, const double *X, long ldx, double *Y, long ldy, const int *skip,
+                    double *partials, long pstride, int *nparts);
+int jacobi_block_dev(const psp_jacobi *K, int k, const double *X, long ldx, double *Y, long ldy);
+int robust_norm2(int n, const double *v, double sq, double *out);  // psp_solvers.hip
+// csr_spmv_launch in the stored numbering: the renumbered copy of an irregular handle is neither used nor built, and the
+// product does not count towards the threshold that builds it (the batched PCG loop)
+int csr_spmv_launch_stored(const psp_csr *A, const double *x, double *y, const double *dotv, double *partials, int *nparts,
+                           const int *skip = nullptr);
+void batch_trim();  // psp_batch.hip: the calling thread's partial-sum buffer of the batched PCG loop (psp_trim)
 // psp_jdsym.hip: the eight cases of correq.c:137-236
 int correq_apply(const psp_op *op, const double *x_dev, double *y_dev);
 // psp_bvec.hip: tall-skinny block-vector kernels (column c of an n x m block at V + c*ld, ld >= n); h lives on the device

@@ -705,6 +705,15 @@ static int robust_nrm2(Workspace *w, int n, const double *v, double sq, double *
   return PSP_OK;
 }
 
+namespace psp {
+// psp_batch.hip: ||v|| from its sum of squares `sq` the way every solve here forms it
+int robust_norm2(int n, const double *v, double sq, double *out) {
+  Workspace *w;
+  PSP_TRY(workspace(&w));
+  return robust_nrm2(w, n, v, sq, out);
+}
+}  // namespace psp
+
 static int pcg_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_forced, const double *dinv_forced,
                            int n, double *x, const double *b, double tol, int maxit, int *info, int *iter,
                            double *relres, double *hist) {
@@ -2513,6 +2522,7 @@ int psp_trim(void) {
   g_pool.trim();
   host_stage_trim();
   bv_trim();
+  batch_trim();
   return PSP_OK;
 }
 

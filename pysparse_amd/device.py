@@ -24,6 +24,35 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _block(a, rows, what, k=None, writable=False):
+    """(array, leading dimension) of a 2-D float64 block with `rows` rows for the column-major C ABI.  Any strides are
+    accepted: a block whose columns are contiguous (Fortran order, or a column slice of one) is passed as it is, anything
+    else through a column-major copy (the second value of the returned pair tells the caller to copy back)."""
+    if not isinstance(a, np.ndarray):
+        raise TypeError("%s must be a 2-dimensional double array" % what)
+    if a.ndim != 2 or a.dtype != np.float64 or a.shape[0] != rows or a.shape[1] < 1 or (k is not None and a.shape[1] != k):
+        raise ValueError("%s must be a 2-dimensional double array of appropriate size." % what)
+    if writable and not a.flags.writeable:
+        raise ValueError("%s is read-only" % what)
+    es = a.itemsize
+    direct = (a.strides[0] == es or rows == 1) and (a.shape[1] == 1 or (a.strides[1] % es == 0 and a.strides[1] // es >= rows))
+    if direct and rows >= 1:
+        ld = a.strides[1] // es if a.shape[1] > 1 else max(rows, 1)
+        return a, ld, False
+    return np.asfortranarray(a), max(rows, 1), True
+
+
+def _matmat(fn, h, shape, X, Y):
+    nrows, ncols = shape
+    xb, ldx, _ = _block(X, ncols, "arg 1")
+    yb, ldy, copy_back = _block(Y, nrows, "arg 2", k=X.shape[1], writable=True)
+    if copy_back:
+        yb = np.empty((nrows, X.shape[1]), dtype=np.float64, order="F")
+    check(fn(h, int(X.shape[1]), _ptr(xb), ldx, _ptr(yb), ldy))
+    if copy_back:
+        Y[...] = yb
+
+
 class DeviceBuffer:
     """n doubles (or raw bytes) of HBM."""
 
@@ -184,6 +213,14 @@ class DeviceCSR:
         es = x.itemsize
         check(lib().psp_csr_matvec_stride(self._h, _ptr(x), x.strides[0] // es, _ptr(y), y.strides[0] // es))
 
+    def matmat(self, X, Y):
+        """Y[:, c] = A X[:, c] for every column: X (ncols, k), Y (nrows, k), 2-D float64 with any strides.  One block
+        product (psp_csr_matmat); column c has the bits of matvec on X[:, c]."""
+        _matmat(lib().psp_csr_matmat, self._h, self.shape, X, Y)
+
+    def matmat_dev(self, k, x_ptr, ldx, y_ptr, ldy):
+        check(lib().psp_csr_matmat_dev(self._h, int(k), x_ptr, int(ldx), y_ptr, int(ldy)))
+
     def matvec_transp(self, x, y):
         _f64(x, self.shape[0], "arg 1")
         _f64(y, self.shape[1], "arg 2")
@@ -294,6 +331,13 @@ class DeviceSSS:
         check(lib().psp_sss_matvec_stride(self._h, _ptr(x), x.strides[0] // es, _ptr(y), y.strides[0] // es))
 
     matvec_transp = matvec  # sss_mat.c:108
+
+    def matmat(self, X, Y):
+        """Y[:, c] = A X[:, c] for every column (psp_sss_matmat): X, Y (n, k), 2-D float64 with any strides."""
+        _matmat(lib().psp_sss_matmat, self._h, (self.n, self.n), X, Y)
+
+    def matmat_dev(self, k, x_ptr, ldx, y_ptr, ldy):
+        check(lib().psp_sss_matmat_dev(self._h, int(k), x_ptr, int(ldx), y_ptr, int(ldy)))
 
     def matvec_dev(self, x_ptr, y_ptr):
         check(lib().psp_sss_matvec_dev(self._h, x_ptr, y_ptr))
@@ -531,6 +575,42 @@ def pcg(A, b, x, tol, maxit, K=None, hist=False):
 def minres(A, b, x, tol, maxit, K=None, hist=False):
     """info, iter, relres = minres(A, b, x, tol, maxit[, K]) -- itsolversmodule.c:217-305."""
     return _solve(lib().psp_minres, A, b, x, tol, maxit, K, hist)
+
+
+def pcg_batch(A, B, X, tol, maxit, K=None):
+    """info, iter, relres = pcg_batch(A, B, X, tol, maxit[, K]): pcg for the k columns of B at once (psp_pcg_batch), three
+    arrays of length k.  B and X are (n, k) float64 blocks with any strides; X holds the initial guesses and is updated
+    in place.  Column c ends exactly as pcg(A, B[:, c], X[:, c], tol, maxit, K) would.  A and K: what pcg accepts; a
+    matrix on a device list raises ValueError."""
+    n = int(A.shape[0])
+    if not isinstance(B, np.ndarray) or not isinstance(X, np.ndarray):
+        raise TypeError("B and X must be 2-dimensional double arrays")
+    if B.ndim != 2 or X.ndim != 2 or B.shape != X.shape or B.shape[0] != n or B.shape[1] < 1:
+        raise ValueError("incompatible operand shapes")
+    if B.dtype != np.float64 or X.dtype != np.float64:
+        raise ValueError("B and X must be double arrays")
+    if not X.flags.writeable:
+        raise ValueError("X is read-only")
+    k = int(B.shape[1])
+    aop = _Op(A, "matvec")
+    kop = _Op(K, "precon") if K is not None else None
+    bb, ldb, _ = _block(B, n, "B")
+    xb, ldx, copy_back = _block(X, n, "X", k=k, writable=True)
+    info = np.zeros(k, dtype=np.intc)
+    it = np.zeros(k, dtype=np.intc)
+    rr = np.zeros(k, dtype=np.float64)
+    rc = lib().psp_pcg_batch(aop._h, kop._h if kop else None, n, k, _ptr(xb), ldx, _ptr(bb), ldb, float(tol), int(maxit),
+                             info.ctypes.data_as(C.POINTER(C.c_int)), it.ctypes.data_as(C.POINTER(C.c_int)),
+                             rr.ctypes.data_as(C.POINTER(C.c_double)))
+    for op in (aop, kop):
+        if op is not None and op.exc is not None:
+            raise op.exc
+    if rc == -1 and "multi-device" in lib().psp_last_error().decode():  # PSP_EINVAL
+        raise ValueError("pcg_batch is not available on a multi-device matrix")
+    check(rc)
+    if copy_back:
+        X[...] = xb
+    return info, it, rr
 
 
 def _solve_more(name, A, b, x, tol, maxit, K, dim=None):

@@ -134,6 +134,90 @@ static PyObject *ItSolvers_gmres(PyObject *self, PyObject *args) {
   return res;
 }
 
+/* info, iter, relres = pcg_batch(A, B, X, tol, maxit[, K]): pcg for the k columns of B in one loop (psp_pcg_batch; no
+ * analogue in the reference).  B and X are (n, k) double arrays with any strides; they are staged as column-major blocks
+ * and X is written back in place.  Three arrays of length k are returned.  Arguments are validated before any device
+ * call; a matrix on a device list raises ValueError. */
+static PyObject *ItSolvers_pcg_batch(PyObject *self, PyObject *args) {
+  PyObject *amat, *bo, *xo, *precon = Py_None;
+  PyArrayObject *bf = NULL, *xf = NULL, *info = NULL, *iter = NULL, *relres = NULL;
+  double tol;
+  int maxit, n = 0, nk = 0, rc, k;
+  PyOpRef aref, kref;
+  PyObject *result = NULL;
+  int have_a = 0, have_k = 0;
+  npy_intp kk;
+
+  if (!PyArg_ParseTuple(args, "OOOdi|O", &amat, &bo, &xo, &tol, &maxit, &precon)) return NULL;
+  if (!PyArray_Check(bo) || !PyArray_Check(xo)) {
+    PyErr_SetString(PyExc_TypeError, "B and X must be 2-dimensional double arrays");
+    return NULL;
+  }
+  if (PyArray_TYPE((PyArrayObject *)bo) != NPY_DOUBLE || PyArray_TYPE((PyArrayObject *)xo) != NPY_DOUBLE) {
+    PyErr_SetString(PyExc_ValueError, "B and X must be double arrays");
+    return NULL;
+  }
+  if (!PyArray_ISWRITEABLE((PyArrayObject *)xo)) {
+    PyErr_SetString(PyExc_ValueError, "X must be writeable.");
+    return NULL;
+  }
+  if (pyop_acquire(amat, 0, &aref, &n)) return NULL;
+  have_a = 1;
+  if (n <= 0) {
+    PyErr_SetString(PyExc_ValueError, "invalid matrix shape");
+    goto done;
+  }
+  if (PyArray_NDIM((PyArrayObject *)bo) != 2 || PyArray_NDIM((PyArrayObject *)xo) != 2 ||
+      PyArray_DIM((PyArrayObject *)bo, 0) != n || PyArray_DIM((PyArrayObject *)xo, 0) != n ||
+      PyArray_DIM((PyArrayObject *)bo, 1) != PyArray_DIM((PyArrayObject *)xo, 1) ||
+      PyArray_DIM((PyArrayObject *)bo, 1) < 1 || PyArray_DIM((PyArrayObject *)bo, 1) > 0x7fffffff) {
+    PyErr_SetString(PyExc_ValueError, "incompatible operand shapes");
+    goto done;
+  }
+  k = (int)PyArray_DIM((PyArrayObject *)bo, 1);
+  if (precon != Py_None) {
+    if (pyop_acquire(precon, 1, &kref, &nk)) goto done;
+    have_k = 1;
+    if (nk != n) {
+      PyErr_SetString(PyExc_ValueError, "incompatible operand shapes");
+      goto done;
+    }
+  }
+  /* column-major copies (the arrays themselves when they already are column-major) */
+  bf = (PyArrayObject *)PyArray_FromArray((PyArrayObject *)bo, NULL, NPY_ARRAY_F_CONTIGUOUS | NPY_ARRAY_ALIGNED);
+  xf = (PyArrayObject *)PyArray_FromArray((PyArrayObject *)xo, NULL,
+                                          NPY_ARRAY_F_CONTIGUOUS | NPY_ARRAY_ALIGNED | NPY_ARRAY_WRITEABLE);
+  kk = k;
+  info = (PyArrayObject *)PyArray_ZEROS(1, &kk, NPY_INT, 0);
+  iter = (PyArrayObject *)PyArray_ZEROS(1, &kk, NPY_INT, 0);
+  relres = (PyArrayObject *)PyArray_ZEROS(1, &kk, NPY_DOUBLE, 0);
+  if (!bf || !xf || !info || !iter || !relres) goto done;
+
+  Py_BEGIN_ALLOW_THREADS
+  rc = psp_pcg_batch(aref.op, have_k ? kref.op : NULL, n, k, (double *)PyArray_DATA(xf), n,
+                     (const double *)PyArray_DATA(bf), n, tol, maxit, (int *)PyArray_DATA(info),
+                     (int *)PyArray_DATA(iter), (double *)PyArray_DATA(relres));
+  Py_END_ALLOW_THREADS
+  if (PyErr_Occurred()) goto done; /* a callback raised */
+  if (rc != PSP_OK) {
+    PyErr_SetString(rc == PSP_ENOMEM ? PyExc_MemoryError
+                                     : (rc == PSP_EINVAL ? PyExc_ValueError : PyExc_RuntimeError),
+                    psp_last_error());
+    goto done;
+  }
+  if ((PyObject *)xf != xo && PyArray_CopyInto((PyArrayObject *)xo, xf) < 0) goto done;
+  result = Py_BuildValue("(OOO)", (PyObject *)info, (PyObject *)iter, (PyObject *)relres);
+done:
+  if (have_k) pyop_release(&kref);
+  if (have_a) pyop_release(&aref);
+  Py_XDECREF(bf);
+  Py_XDECREF(xf);
+  Py_XDECREF(info);
+  Py_XDECREF(iter);
+  Py_XDECREF(relres);
+  return result;
+}
+
 static PyMethodDef krylov_methods[] = {
     {"cgs", ItSolvers_cgs, METH_VARARGS,
      "info, iter, relres = cgs(A, b, x, tol, maxit[, K])\n\nConjugate Gradient Squared method."},
@@ -145,6 +229,8 @@ static PyMethodDef krylov_methods[] = {
      "info, iter, relres = gmres(A, b, x, tol, maxit[, K[, dim]])\n\nGMRES(dim) of Saad and Schultz."},
     {"pcg", ItSolvers_pcg, METH_VARARGS,
      "info, iter, relres = pcg(A, b, x, tol, maxit[, K])\n\nPreconditioned Conjugate Gradient method."},
+    {"pcg_batch", ItSolvers_pcg_batch, METH_VARARGS,
+     "info, iter, relres = pcg_batch(A, B, X, tol, maxit[, K])\n\nPCG for the k columns of B in one loop; three arrays of length k."},
     {"minres", ItSolvers_minres, METH_VARARGS,
      "info, iter, relres = minres(A, b, x, tol, maxit[, K])\n\nMinimal Residual method."},
     {NULL, NULL, 0, NULL}};

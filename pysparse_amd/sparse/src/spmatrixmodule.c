@@ -73,6 +73,64 @@ static int parse_arr_arr_stride(PyObject *args, PyArrayObject **xp, PyArrayObjec
 
 #define ELEM_STRIDE(a) ((ptrdiff_t)(PyArray_STRIDE((a), 0) / (npy_intp)sizeof(double)))
 
+/* a.matmat(X, Y): Y[:, c] := a * X[:, c] for every column (psp_csr_matmat / psp_sss_matmat; no analogue in the reference).
+ * X is (n1, k), Y is (n2, k), 2-D double arrays with any strides: they are staged as column-major blocks and Y is written
+ * back in place.  Errors in the style of parse_arr_arr_stride, raised before any device call. */
+typedef int (*matmat_fn)(void *, int, const double *, long, double *, long);
+
+static int parse_blocks(PyObject *args, PyArrayObject **xp, PyArrayObject **yp, npy_intp n1, npy_intp n2) {
+  if (!PyArg_ParseTuple(args, "O!O!", &PyArray_Type, xp, &PyArray_Type, yp)) return -1;
+  if (PyArray_NDIM(*xp) != 2 || PyArray_TYPE(*xp) != NPY_DOUBLE || PyArray_DIM(*xp, 0) != n1 ||
+      PyArray_DIM(*xp, 1) < 1 || PyArray_DIM(*xp, 1) > 0x7fffffff) {
+    PyErr_SetString(PyExc_ValueError, "arg 1 must be a 2-dimensional double array of appropriate size.");
+    return -1;
+  }
+  if (PyArray_NDIM(*yp) != 2 || PyArray_TYPE(*yp) != NPY_DOUBLE || PyArray_DIM(*yp, 0) != n2 ||
+      PyArray_DIM(*yp, 1) != PyArray_DIM(*xp, 1)) {
+    PyErr_SetString(PyExc_ValueError, "arg 2 must be a 2-dimensional double array of appropriate size.");
+    return -1;
+  }
+  if (!PyArray_ISWRITEABLE(*yp)) {
+    PyErr_SetString(PyExc_ValueError, "arg 2 must be writeable.");
+    return -1;
+  }
+  return 0;
+}
+
+static PyObject *block_matmat(PyArrayObject *xp, PyArrayObject *yp, matmat_fn fn, void *handle) {
+  PyArrayObject *xf = NULL, *yf = NULL;
+  PyObject *result = NULL;
+  const npy_intp n1 = PyArray_DIM(xp, 0), n2 = PyArray_DIM(yp, 0);
+  npy_intp dims[2];
+  int rc;
+  const int k = (int)PyArray_DIM(xp, 1);
+  xf = (PyArrayObject *)PyArray_FromArray(xp, NULL, NPY_ARRAY_F_CONTIGUOUS | NPY_ARRAY_ALIGNED);
+  if (PyArray_ISFARRAY(yp)) {
+    yf = yp;
+    Py_INCREF(yf);
+  } else {
+    dims[0] = n2;
+    dims[1] = k;
+    yf = (PyArrayObject *)PyArray_EMPTY(2, dims, NPY_DOUBLE, 1);
+  }
+  if (!xf || !yf) goto done;
+  Py_BEGIN_ALLOW_THREADS
+  rc = fn(handle, k, (const double *)PyArray_DATA(xf), (long)(n1 > 0 ? n1 : 1), (double *)PyArray_DATA(yf),
+          (long)(n2 > 0 ? n2 : 1));
+  Py_END_ALLOW_THREADS
+  if (rc != PSP_OK) {
+    psp_raise(rc);
+    goto done;
+  }
+  if (yf != yp && PyArray_CopyInto(yp, yf) < 0) goto done;
+  result = Py_None;
+  Py_INCREF(result);
+done:
+  Py_XDECREF(xf);
+  Py_XDECREF(yf);
+  return result;
+}
+
 /* ------------------------------------------------------------------ C API shims */
 
 /* spmatrixmodule.c:86-104 */
@@ -680,6 +738,13 @@ static PyObject *LLMat_matvec(LLMatObject *self, PyObject *args) {
   Py_RETURN_NONE;
 }
 
+static PyObject *LLMat_matmat(LLMatObject *self, PyObject *args) {
+  PyArrayObject *xp, *yp;
+  if (parse_blocks(args, &xp, &yp, self->dim[1], self->dim[0])) return NULL;
+  if (ll_ensure_mirror(self)) return NULL;
+  return block_matmat(xp, yp, (matmat_fn)psp_csr_matmat, self->mirror);
+}
+
 static PyObject *LLMat_matvec_transp(LLMatObject *self, PyObject *args) {
   PyArrayObject *xp, *yp;
   int rc;
@@ -857,6 +922,7 @@ static PyObject *LLMat_repr(LLMatObject *a) {
 static PyMethodDef LLMat_methods[] = {
     {"matvec", (PyCFunction)LLMat_matvec, METH_VARARGS, "a.matvec(x, y): y := a * x (on the GPU)"},
     {"matvec_transp", (PyCFunction)LLMat_matvec_transp, METH_VARARGS, "a.matvec_transp(x, y): y := a^T * x"},
+    {"matmat", (PyCFunction)LLMat_matmat, METH_VARARGS, "a.matmat(X, Y): Y[:, c] := a * X[:, c] for every column (on the GPU)"},
     {"to_csr", (PyCFunction)(void (*)(void))LLMat_to_csr, METH_VARARGS | METH_KEYWORDS,
      "A.to_csr(): new csr_mat from the data of A; A.to_csr(devices=[0, 1, ...]): its rows on several GPUs"},
     {"to_sss", (PyCFunction)LLMat_to_sss, METH_VARARGS, "a.to_sss(): new sss_mat from the lower triangle of a"},
@@ -909,6 +975,12 @@ static PyObject *CSRMat_matvec(CSRMatObject *self, PyObject *args) {
   Py_END_ALLOW_THREADS
   if (rc != PSP_OK) return psp_raise(rc);
   Py_RETURN_NONE;
+}
+
+static PyObject *CSRMat_matmat(CSRMatObject *self, PyObject *args) {
+  PyArrayObject *xp, *yp;
+  if (parse_blocks(args, &xp, &yp, self->dim[1], self->dim[0])) return NULL;
+  return block_matmat(xp, yp, (matmat_fn)psp_csr_matmat, self->dev);
 }
 
 static PyObject *CSRMat_matvec_transp(CSRMatObject *self, PyObject *args) {
@@ -1036,6 +1108,7 @@ static PyObject *CSRMat_str(CSRMatObject *a) {
 static PyMethodDef CSRMat_methods[] = {
     {"matvec", (PyCFunction)CSRMat_matvec, METH_VARARGS, "a.matvec(x, y): y := a * x"},
     {"matvec_transp", (PyCFunction)CSRMat_matvec_transp, METH_VARARGS, "a.matvec_transp(x, y): y := a^T * x"},
+    {"matmat", (PyCFunction)CSRMat_matmat, METH_VARARGS, "a.matmat(X, Y): Y[:, c] := a * X[:, c] for every column"},
     {"to_arrays", (PyCFunction)CSRMat_to_arrays, METH_VARARGS, "(indptr, indices, data) copied back from the device"},
     {NULL, NULL, 0, NULL}};
 
@@ -1161,9 +1234,16 @@ static PyObject *SSSMat_str(SSSMatObject *a) {
   return ret;
 }
 
+static PyObject *SSSMat_matmat(SSSMatObject *self, PyObject *args) {
+  PyArrayObject *xp, *yp;
+  if (parse_blocks(args, &xp, &yp, self->n, self->n)) return NULL;
+  return block_matmat(xp, yp, (matmat_fn)psp_sss_matmat, self->dev);
+}
+
 static PyMethodDef SSSMat_methods[] = {
     {"matvec", (PyCFunction)SSSMat_matvec, METH_VARARGS, "a.matvec(x, y): y := a * x"},
     {"matvec_transp", (PyCFunction)SSSMat_matvec, METH_VARARGS, "a.matvec_transp(x, y): y := a^T * x (== a * x)"},
+    {"matmat", (PyCFunction)SSSMat_matmat, METH_VARARGS, "a.matmat(X, Y): Y[:, c] := a * X[:, c] for every column"},
     {"to_arrays", (PyCFunction)SSSMat_to_arrays, METH_VARARGS, "(indptr, indices, data, diag) copied back from the device"},
     {NULL, NULL, 0, NULL}};
 
