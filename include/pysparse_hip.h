@@ -48,6 +48,7 @@ extern "C" {
 typedef struct psp_csr psp_csr_t;       /* device mirror of CSRMatObject, csr_mat.h:6-13     */
 typedef struct psp_sss psp_sss_t;       /* device mirror of SSSMatObject, sss_mat.h:6-14     */
 typedef struct psp_jacobi psp_jacobi_t; /* device mirror of JacobiObject, preconmodule.c:11-19 */
+typedef struct psp_mg psp_mg_t;         /* precon.multigrid: matrix-free V-cycle; no reference analogue */
 typedef struct psp_ssor psp_ssor_t;     /* device mirror of SSORObject, preconmodule.c:21-31   */
 typedef struct psp_op psp_op_t;         /* "anything with shape + matvec / precon":
                                            the operator protocol of spmatrixmodule.c:169-248 */
@@ -372,6 +373,26 @@ int psp_ssor_brick_info(const psp_ssor_t *K, int *bricks, int *edge);
 int psp_ssor_precon(psp_ssor_t *K, const double *x_host, double *y_host);
 int psp_ssor_precon_dev(psp_ssor_t *K, const double *x_dev, double *y_dev);
 
+/* ---------------------------------------------------------------- multigrid */
+
+/* precon.multigrid(A, grid, omega, steps): a geometric V-cycle for A = sum_a c_a T_a + s I on a grid of 1 to 3 axes
+ * (T_a = [-1 2 -1] along axis a, nothing stored across line ends, row k = i0 + n0 i1 + n0 n1 i2), matrix-free: c_a and
+ * s are read from A at creation, where a device pass checks that EVERY stored entry is the stencil's (PSP_EINVAL
+ * otherwise, also for a multi-device matrix); A is not used afterwards.  Axes with n_a >= 4 are halved level by level
+ * (coarse point j at fine 2j + 1, c_a / 4), `steps` damped-Jacobi sweeps before and after, a dense solve on the coarsest
+ * level (at most 27 points); 0 < omega <= 1, steps >= 1: the operator is symmetric positive definite.  DESIGN.md 9c.
+ * No reference analogue (the reference's preconditioners are jacobi and ssor); no host mode. */
+int psp_mg_create_csr(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out);
+int psp_mg_create_sss(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out);
+int psp_mg_destroy(psp_mg_t *K);
+/* y := K x (y must not alias x in the device form); same bits from call to call */
+int psp_mg_precon(psp_mg_t *K, const double *x_host, double *y_host);
+int psp_mg_precon_dev(psp_mg_t *K, const double *x_dev, double *y_dev);
+/* levels, the first level of the single-workgroup tail launch (that level and all below it run in one kernel with their
+ * vectors in LDS), kernel launches per application, and the level dimensions (3 ints per level, 1 on absent axes;
+ * dims may be NULL) */
+int psp_mg_info(const psp_mg_t *K, int *levels, int *tail_first_level, int *launches_per_apply, int *dims);
+
 /* --------------------------------------------------------- operator protocol */
 
 /* Host callback operator: the C image of SpMatrix_Matvec / SpMatrix_Precon
@@ -383,6 +404,7 @@ int psp_op_from_csr(psp_csr_t *A, psp_op_t **out);
 int psp_op_from_sss(psp_sss_t *A, psp_op_t **out);
 int psp_op_from_jacobi(psp_jacobi_t *K, psp_op_t **out);
 int psp_op_from_ssor(psp_ssor_t *K, psp_op_t **out);
+int psp_op_from_mg(psp_mg_t *K, psp_op_t **out);
 int psp_op_from_callback(int n, psp_host_apply_fn fn, void *ctx, psp_op_t **out);
 int psp_op_destroy(psp_op_t *op);
 

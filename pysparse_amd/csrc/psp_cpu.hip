@@ -119,6 +119,7 @@ int apply(const psp_op *op, const double *x, double *y) {
     case PSP_OP_SSS: sss_mv(op->sss, x, 1, y, 1); return PSP_OK;
     case PSP_OP_JACOBI: return jacobi_apply(op->jac, x, y);
     case PSP_OP_SSOR: return ssor_apply_host(op->ssor, x, y);
+    case PSP_OP_MG: return fail(PSP_ENODEV, "PSP_DEVICE=cpu: precon.multigrid has no host loop");
     case PSP_OP_CALLBACK:
       if (op->fn(op->ctx, op->n, x, y)) return fail(PSP_ECALLBACK, "host operator callback failed");
       return PSP_OK;

@@ -408,7 +408,8 @@ enum psp_op_kind {
   PSP_OP_JACOBI = 3,
   PSP_OP_CALLBACK = 4,
   PSP_OP_SSOR = 5,
-  PSP_OP_CORREQ = 6  // the projected operator / preconditioner of jdsym's correction equation (psp_jdsym.hip)
+  PSP_OP_CORREQ = 6,  // the projected operator / preconditioner of jdsym's correction equation (psp_jdsym.hip)
+  PSP_OP_MG = 7       // precon.multigrid: the matrix-free V-cycle of psp_mg.hip
 };
 struct psp_correq;
 
@@ -419,6 +420,7 @@ struct psp_op {
   psp_sss *sss = nullptr;
   psp_jacobi *jac = nullptr;
   psp_ssor *ssor = nullptr;
+  psp_mg *mg = nullptr;
   psp_host_apply_fn fn = nullptr;
   void *ctx = nullptr;
   // pinned staging for callback operators
@@ -472,6 +474,7 @@ inline void op_lock_add(HandleLock &L, const psp_op *op) {
   L.add(op->csr);
   L.add(op->sss);
   L.add(op->ssor);
+  L.add(op->mg);  // owns its level vectors; the matrix is only read at creation
   if (op->jac) {
     L.add(op->jac);
     L.add(op->jac->A.csr);
@@ -690,4 +693,5 @@ int ssor_apply_dev(psp_ssor *K, const double *b, double *x);  // psp_ssor.hip
 // waits for the error word of the last application's brick sweeps (sticky across applications until reported)
 int ssor_error_check(psp_ssor *K);
 int ssor_apply_host(psp_ssor *K, const double *b, double *x);  // psp_ssor.hip: PSP_DEVICE=cpu, host arrays
+int mg_apply_dev(psp_mg *K, const double *b, double *y);  // psp_mg.hip: one V-cycle, y must not alias b
 }  // namespace psp

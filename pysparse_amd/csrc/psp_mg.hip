@@ -1,0 +1,871 @@
+// psp_mg.hip -- precon.multigrid(A, grid, omega, steps): a matrix-free geometric V-cycle for the constant-coefficient
+// grid operators A = sum_a c_a T_a + s I (T_a = [-1 2 -1] along axis a, nothing stored across line ends; row
+// k = i0 + n0 i1 + n0 n1 i2, the ordering of tools/poisson.py).  No reference analogue: the reference's preconditioners
+// are jacobi and ssor (preconmodule.c).
+//
+// The cycle (DESIGN.md section 9c is the normative text):
+//   * level l -> l + 1 coarsens every axis with n_a >= 4: n_a' = n_a / 2, coarse point j at fine index 2 j + 1,
+//     c_a' = c_a / 4 on the coarsened axes; s' = s; the level's diagonal is d = 2 sum_{n_a > 1} c_a + s;
+//   * P = (x)_a P_a with P_a[2j+1, j] = 1, P_a[2j, j] = P_a[2j+2, j] = 1/2 where in range; R = P' / 2^(coarsened axes);
+//   * V(l, b): x = 0; `steps` sweeps x <- x + (omega / d)(b - A_l x); b_c = R (b - A_l x); x <- x + P V(l + 1, b_c);
+//     `steps` sweeps; the coarsest level (no axis >= 4: at most 27 points) is a dense product with the inverse formed
+//     on the host at creation.
+// Nothing of a level is stored but its vectors: c_a, s and the dimensions are kernel arguments, Dirichlet ends are
+// handled by omission.  Every sum has one fixed order and there are no atomics: the same bits from run to run.
+//
+// Kernels: mg_scale / mg_smooth (one out-of-place sweep; the first two sweeps from x = 0 in one pass over b),
+// mg_restrict (a workgroup owns a tile of coarse points, forms the fine residuals of the tile plus halo in LDS and
+// writes only b_c), mg_prolong (x += P e), mg_tail (the largest level of at most kTailT points and everything below
+// it, down and up, dense solve included, in ONE launch of one workgroup with the vectors in LDS).
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "psp_internal.h"
+
+using namespace psp;
+
+namespace {
+
+constexpr int kTailThreads = 1024;
+constexpr int kTailPts = 2;                        // points of a level per thread of the tail's workgroup
+constexpr int kTailT = kTailThreads * kTailPts;    // largest level the tail takes
+constexpr int kTailMaxLev = 12;                    // 2048 -> 1024 -> ... -> 4 -> 2 in 1-D is 11 levels
+constexpr int kCoarsestMax = 27;                   // no axis >= 4: at most 3^3 points
+constexpr int kMaxLevels = 32;                     // n < 2^31 and every level at least halves
+// LDS of the tail (doubles): x and b of every level (level sizes at least halve: their sum stays below 2 kTailT), one
+// level-sized scratch for the residual, the dense inverse
+constexpr int kTailLds = 5 * kTailT + kCoarsestMax * kCoarsestMax;
+// mg_restrict: 256 coarse points per workgroup; the fine residuals of the tile plus halo (2 t + 1 per coarsened axis)
+constexpr int kResThreads = 256;
+constexpr int kResLds = 33 * 9 * 9;  // the 3-D tile 16 x 4 x 4; 2-D 32 x 8 -> 65 x 17, 1-D 256 -> 513 are smaller
+
+struct MgLevelArg {
+  int n[3];     // dimensions (1 on the axes the grid does not have)
+  int co[3];    // 1: the axis is coarsened towards the next level
+  int nc[3];    // dimensions of the next level
+  double c[3];  // 0 on axes of length 1
+  double d;     // 2 sum c + s
+  double w;     // omega / d
+  double rs;    // 1 / 2^(coarsened axes)
+};
+
+struct MgTailArg {
+  int nlev;
+  int steps;
+  int off[kTailMaxLev];  // offset of the level's x (and, kTailT * 2 further, b) in the tail's LDS
+  MgLevelArg lev[kTailMaxLev];
+};
+
+// (A_l x)[i]: the diagonal first, then axis by axis the lower and the upper neighbour -- one fixed order everywhere
+template <class X>
+__device__ __forceinline__ double mg_ax(const MgLevelArg &L, const X &x, long i, int i0, int i1, int i2) {
+  double acc = L.d * x(i);
+  if (L.n[0] > 1) {
+    if (i0 > 0) acc -= L.c[0] * x(i - 1);
+    if (i0 < L.n[0] - 1) acc -= L.c[0] * x(i + 1);
+  }
+  if (L.n[1] > 1) {
+    const long s1 = L.n[0];
+    if (i1 > 0) acc -= L.c[1] * x(i - s1);
+    if (i1 < L.n[1] - 1) acc -= L.c[1] * x(i + s1);
+  }
+  if (L.n[2] > 1) {
+    const long s2 = (long)L.n[0] * L.n[1];
+    if (i2 > 0) acc -= L.c[2] * x(i - s2);
+    if (i2 < L.n[2] - 1) acc -= L.c[2] * x(i + s2);
+  }
+  return acc;
+}
+
+__device__ __forceinline__ void mg_split(const MgLevelArg &L, long i, int &i0, int &i1, int &i2) {
+  i0 = (int)(i % L.n[0]);
+  const long q = i / L.n[0];
+  i1 = (int)(q % L.n[1]);
+  i2 = (int)(q / L.n[1]);
+}
+
+// (R r)[j] for the coarse point (j0, j1, j2); r is indexed through `at(l0, l1, l2)` with fine coordinates, which returns 0
+// outside the grid.  Weights 1/2, 1, 1/2 along a coarsened axis at fine 2j, 2j+1, 2j+2; axis 2 outermost, ascending.
+template <class AT>
+__device__ __forceinline__ double mg_restrict_point(const MgLevelArg &L, const AT &at, int j0, int j1, int j2) {
+  const int b0 = L.co[0] ? 2 * j0 : j0, m0 = L.co[0] ? 3 : 1;
+  const int b1 = L.co[1] ? 2 * j1 : j1, m1 = L.co[1] ? 3 : 1;
+  const int b2 = L.co[2] ? 2 * j2 : j2, m2 = L.co[2] ? 3 : 1;
+  double sum = 0.0;
+  for (int k2 = 0; k2 < m2; ++k2) {
+    const double w2 = (L.co[2] && k2 != 1) ? 0.5 : 1.0;
+    for (int k1 = 0; k1 < m1; ++k1) {
+      const double w1 = (L.co[1] && k1 != 1) ? 0.5 * w2 : w2;
+      for (int k0 = 0; k0 < m0; ++k0) {
+        const double w0 = (L.co[0] && k0 != 1) ? 0.5 * w1 : w1;
+        sum += w0 * at(b0 + k0, b1 + k1, b2 + k2);
+      }
+    }
+  }
+  return sum * L.rs;
+}
+
+// (P e)[i] for the fine point (i0, i1, i2); e is the next level's vector.  Along a coarsened axis an odd index takes
+// coarse (i - 1) / 2 whole, an even one half of coarse i / 2 - 1 and half of i / 2 where they exist; lower before upper,
+// axis 2 outermost.
+struct MgAxisSrc {
+  int ja, jb, cnt;  // the coarse indices a fine index takes from (jb only when cnt == 2)
+  double wt;
+};
+__device__ __forceinline__ MgAxisSrc mg_axis_src(int co, int g, int nc) {
+  MgAxisSrc s;
+  s.jb = 0;
+  if (!co) {
+    s.ja = g, s.cnt = 1, s.wt = 1.0;
+  } else if (g & 1) {
+    s.ja = (g - 1) >> 1, s.cnt = 1, s.wt = 1.0;
+  } else {
+    const int lo = (g >> 1) - 1, hi = g >> 1;  // at least one exists: nc >= 2 on a coarsened axis
+    s.wt = 0.5;
+    if (lo >= 0 && hi < nc) {
+      s.ja = lo, s.jb = hi, s.cnt = 2;
+    } else {
+      s.ja = lo >= 0 ? lo : hi, s.cnt = 1;
+    }
+  }
+  return s;
+}
+template <class E>
+__device__ __forceinline__ double mg_prolong_point(const MgLevelArg &L, const E &e, int i0, int i1, int i2) {
+  const MgAxisSrc a0 = mg_axis_src(L.co[0], i0, L.nc[0]), a1 = mg_axis_src(L.co[1], i1, L.nc[1]),
+                  a2 = mg_axis_src(L.co[2], i2, L.nc[2]);
+  const double w = a0.wt * a1.wt * a2.wt;  // powers of two: exact
+  double sum = 0.0;
+  for (int k2 = 0; k2 < a2.cnt; ++k2) {
+    const long j2 = k2 ? a2.jb : a2.ja;
+    for (int k1 = 0; k1 < a1.cnt; ++k1) {
+      const long j1 = k1 ? a1.jb : a1.ja;
+      for (int k0 = 0; k0 < a0.cnt; ++k0) {
+        const long j0 = k0 ? a0.jb : a0.ja;
+        sum += w * e(j0 + (long)L.nc[0] * (j1 + (long)L.nc[1] * j2));
+      }
+    }
+  }
+  return sum;
+}
+
+// ------------------------------------------------------------------ the launch-per-step kernels of the large levels
+
+// the first sweep from x = 0: x = 0 + (omega / d)(b - 0) = (omega / d) b
+__global__ __launch_bounds__(256) void mg_scale_kernel(long N, double w, const double *__restrict__ b,
+                                                       double *__restrict__ x) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < N) x[i] = w * b[i];
+}
+
+// one sweep, out of place: xout = xin + (omega / d)(b - A xin); reads xin and b once, writes xout once (the neighbours
+// come from the caches).  FROMB: xin is the first sweep's (omega / d) b, formed on the fly -- sweeps one and two of a
+// cycle in one pass.  ND: axes the level's index is split into.
+template <int ND, bool FROMB>
+__global__ __launch_bounds__(256) void mg_smooth_kernel(MgLevelArg L, long N, const double *__restrict__ xin,
+                                                        const double *__restrict__ b, double *__restrict__ xout) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  int i0 = (int)i, i1 = 0, i2 = 0;
+  if constexpr (ND == 2) {
+    i0 = (int)(i % L.n[0]);
+    i1 = (int)(i / L.n[0]);
+  } else if constexpr (ND == 3) {
+    mg_split(L, i, i0, i1, i2);
+  }
+  if constexpr (ND < 3) L.n[2] = 1;
+  if constexpr (ND < 2) L.n[1] = 1;
+  const double w = L.w;
+  auto X = [&](long k) { return FROMB ? w * b[k] : xin[k]; };
+  const double ax = mg_ax(L, X, i, i0, i1, i2);
+  xout[i] = X(i) + w * (b[i] - ax);
+}
+
+// b_c = R (b - A x): blockIdx.x = the tile of coarse points (t[0] x t[1] x t[2] = 256 of them), `r` = the fine residuals
+// the tile's restriction reads; a fine point outside the grid counts as 0
+__global__ __launch_bounds__(kResThreads) void mg_restrict_kernel(MgLevelArg L, int t0, int t1, int t2, int g0n, int g1n,
+                                                                  const double *__restrict__ x,
+                                                                  const double *__restrict__ b,
+                                                                  double *__restrict__ bc) {
+  __shared__ double r[kResLds];
+  // the tile's three indices ride in blockIdx.x (g0n x g1n x g2n tiles, axis 0 fastest): a long second or third axis
+  // would not fit gridDim.y / gridDim.z
+  const unsigned bq = blockIdx.x / (unsigned)g0n;
+  const int J0 = (int)(blockIdx.x % (unsigned)g0n) * t0, J1 = (int)(bq % (unsigned)g1n) * t1, J2 = (int)(bq / (unsigned)g1n) * t2;
+  const int f0 = L.co[0] ? 2 * J0 : J0, F0 = L.co[0] ? 2 * t0 + 1 : t0;
+  const int f1 = L.co[1] ? 2 * J1 : J1, F1 = L.co[1] ? 2 * t1 + 1 : t1;
+  const int f2 = L.co[2] ? 2 * J2 : J2, F2 = L.co[2] ? 2 * t2 + 1 : t2;
+  const int total = F0 * F1 * F2;  // <= kResLds (mg_tile)
+  auto X = [&](long k) { return x[k]; };
+  for (int t = threadIdx.x; t < total; t += kResThreads) {
+    const int l0 = t % F0, q = t / F0, l1 = q % F1, l2 = q / F1;
+    const int g0 = f0 + l0, g1 = f1 + l1, g2 = f2 + l2;
+    double v = 0.0;
+    if (g0 < L.n[0] && g1 < L.n[1] && g2 < L.n[2]) {
+      const long i = g0 + (long)L.n[0] * (g1 + (long)L.n[1] * g2);
+      v = b[i] - mg_ax(L, X, i, g0, g1, g2);
+    }
+    r[t] = v;
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < t0 * t1 * t2) {
+    const int j0 = t % t0, q = t / t0, j1 = q % t1, j2 = q / t1;
+    if (J0 + j0 < L.nc[0] && J1 + j1 < L.nc[1] && J2 + j2 < L.nc[2]) {
+      // the tile's fine region starts at the fine image of its first coarse point: local fine coordinates
+      auto at = [&](int a0, int a1, int a2) { return r[a0 + F0 * (a1 + F1 * a2)]; };
+      const double v = mg_restrict_point(L, at, j0, j1, j2);
+      bc[(J0 + j0) + (long)L.nc[0] * ((J1 + j1) + (long)L.nc[1] * (J2 + j2))] = v;
+    }
+  }
+}
+
+// x += P e: reads x and e, writes x
+__global__ __launch_bounds__(256) void mg_prolong_kernel(MgLevelArg L, long N, const double *__restrict__ e,
+                                                         double *__restrict__ x) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  int i0, i1, i2;
+  mg_split(L, i, i0, i1, i2);
+  auto E = [&](long k) { return e[k]; };
+  x[i] = x[i] + mg_prolong_point(L, E, i0, i1, i2);
+}
+
+// ------------------------------------------------------------------ the tail: one workgroup, vectors in LDS
+
+// one sweep of a level in LDS: every thread forms its points' new values, then all are written
+__device__ __forceinline__ void tail_sweep(const MgLevelArg &L, int N, double *xs, const double *bs) {
+  auto X = [&](long k) { return xs[k]; };
+  double xn[kTailPts];
+#pragma unroll
+  for (int p = 0; p < kTailPts; ++p) {
+    const int i = threadIdx.x + p * kTailThreads;
+    xn[p] = 0.0;
+    if (i < N) {
+      int i0, i1, i2;
+      mg_split(L, i, i0, i1, i2);
+      xn[p] = xs[i] + L.w * (bs[i] - mg_ax(L, X, i, i0, i1, i2));
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < kTailPts; ++p) {
+    const int i = threadIdx.x + p * kTailThreads;
+    if (i < N) xs[i] = xn[p];
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const MgTailArg *__restrict__ T,
+                                                               const double *__restrict__ minv,
+                                                               const double *__restrict__ bin,
+                                                               double *__restrict__ xout) {
+  __shared__ double sh[kTailLds];
+  double *const scr = sh + 4 * kTailT;
+  double *const mi = sh + 5 * kTailT;
+  const int nl = T->nlev, steps = T->steps, tid = threadIdx.x;
+  {
+    const MgLevelArg &L = T->lev[0];
+    const int N = L.n[0] * L.n[1] * L.n[2];
+    double *bs = sh + 2 * kTailT + T->off[0];
+    for (int i = tid; i < N; i += kTailThreads) bs[i] = bin[i];
+    const MgLevelArg &C = T->lev[nl - 1];
+    const int nc = C.n[0] * C.n[1] * C.n[2];
+    for (int i = tid; i < nc * nc; i += kTailThreads) mi[i] = minv[i];
+  }
+  __syncthreads();
+  // down
+  for (int l = 0; l < nl - 1; ++l) {
+    const MgLevelArg L = T->lev[l];
+    const int N = L.n[0] * L.n[1] * L.n[2], Nc = L.nc[0] * L.nc[1] * L.nc[2];
+    double *xs = sh + T->off[l], *bs = sh + 2 * kTailT + T->off[l], *bn = sh + 2 * kTailT + T->off[l + 1];
+    for (int i = tid; i < N; i += kTailThreads) xs[i] = L.w * bs[i];
+    __syncthreads();
+    for (int k = 1; k < steps; ++k) tail_sweep(L, N, xs, bs);
+    auto X = [&](long k) { return xs[k]; };
+    for (int i = tid; i < N; i += kTailThreads) {
+      int i0, i1, i2;
+      mg_split(L, i, i0, i1, i2);
+      scr[i] = bs[i] - mg_ax(L, X, i, i0, i1, i2);
+    }
+    __syncthreads();
+    auto at = [&](int a0, int a1, int a2) {
+      return (a0 < L.n[0] && a1 < L.n[1] && a2 < L.n[2]) ? scr[a0 + L.n[0] * (a1 + L.n[1] * a2)] : 0.0;
+    };
+    for (int j = tid; j < Nc; j += kTailThreads) {
+      const int j0 = j % L.nc[0], q = j / L.nc[0], j1 = q % L.nc[1], j2 = q / L.nc[1];
+      bn[j] = mg_restrict_point(L, at, j0, j1, j2);
+    }
+    __syncthreads();
+  }
+  // the coarsest level: x = A^-1 b with the inverse formed at creation
+  {
+    const MgLevelArg &C = T->lev[nl - 1];
+    const int nc = C.n[0] * C.n[1] * C.n[2];
+    double *xs = sh + T->off[nl - 1];
+    const double *bs = sh + 2 * kTailT + T->off[nl - 1];
+    if (tid < nc) {
+      double s = 0.0;
+      for (int j = 0; j < nc; ++j) s += mi[tid * nc + j] * bs[j];
+      xs[tid] = s;
+    }
+    __syncthreads();
+  }
+  // up
+  for (int l = nl - 2; l >= 0; --l) {
+    const MgLevelArg L = T->lev[l];
+    const int N = L.n[0] * L.n[1] * L.n[2];
+    double *xs = sh + T->off[l];
+    const double *bs = sh + 2 * kTailT + T->off[l], *en = sh + T->off[l + 1];
+    auto E = [&](long k) { return en[k]; };
+    for (int i = tid; i < N; i += kTailThreads) {
+      int i0, i1, i2;
+      mg_split(L, i, i0, i1, i2);
+      xs[i] = xs[i] + mg_prolong_point(L, E, i0, i1, i2);
+    }
+    __syncthreads();
+    for (int k = 0; k < steps; ++k) tail_sweep(L, N, xs, bs);
+  }
+  {
+    const MgLevelArg &L = T->lev[0];
+    const int N = L.n[0] * L.n[1] * L.n[2];
+    const double *xs = sh + T->off[0];
+    for (int i = tid; i < N; i += kTailThreads) xout[i] = xs[i];
+  }
+}
+
+// ------------------------------------------------------------------ the exact check at creation
+
+// bit 0: the diagonal; bits 1 + 2a / 2 + 2a: the lower / upper neighbour along axis a
+__device__ __forceinline__ unsigned mg_expected(int r, int n0, int n1, int n2) {
+  const int i0 = r % n0, q = r / n0, i1 = q % n1, i2 = q / n1;
+  unsigned m = 1u;
+  if (i0 > 0) m |= 1u << 1;
+  if (i0 < n0 - 1) m |= 1u << 2;
+  if (i1 > 0) m |= 1u << 3;
+  if (i1 < n1 - 1) m |= 1u << 4;
+  if (i2 > 0) m |= 1u << 5;
+  if (i2 < n2 - 1) m |= 1u << 6;
+  return m;
+}
+
+struct MgStencil {
+  int n[3];
+  double c[3];
+  double d0;
+};
+
+// every stored entry of every row is one the stencil has, with the stencil's value, and none is missing
+__global__ __launch_bounds__(256) void mg_check_csr_kernel(int n, MgStencil S, const int *__restrict__ ind,
+                                                           const int *__restrict__ col, const double *__restrict__ val,
+                                                           int *__restrict__ bad) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const unsigned want = mg_expected(r, S.n[0], S.n[1], S.n[2]);
+  const long st[3] = {1, S.n[0], (long)S.n[0] * S.n[1]};
+  unsigned seen = 0;
+  bool ok = true;
+  for (int k = ind[r]; k < ind[r + 1]; ++k) {
+    const long off = (long)col[k] - r;
+    const double v = val[k];
+    int bit = -1;
+    double ev = 0.0;
+    if (off == 0) {
+      bit = 0;
+      ev = S.d0;
+    } else {
+      for (int a = 0; a < 3; ++a)
+        if (S.n[a] > 1 && (off == st[a] || off == -st[a])) {
+          bit = 1 + 2 * a + (off > 0 ? 1 : 0);
+          ev = -S.c[a];
+        }
+    }
+    if (bit < 0 || !((want >> bit) & 1u) || ((seen >> bit) & 1u) || !(v == ev)) ok = false;
+    if (bit >= 0) seen |= 1u << bit;
+  }
+  if (!ok || seen != want) *bad = 1;
+}
+
+// the same on the index-free layout: the values are constant per offset (checked on the host against the view's cval);
+// bit o of mask[r] says that row r stores offset slot o, slotbit[o] is that offset's bit in mg_expected's numbering
+struct MgSlots {
+  int no;
+  int bit[12];
+};
+__global__ __launch_bounds__(256) void mg_check_w4_kernel(int n, MgStencil S, MgSlots Q,
+                                                          const unsigned short *__restrict__ mask,
+                                                          int *__restrict__ bad) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const unsigned want = mg_expected(r, S.n[0], S.n[1], S.n[2]);
+  const unsigned m = mask[r];
+  unsigned seen = 0;
+  for (int o = 0; o < Q.no; ++o)
+    if ((m >> o) & 1u) seen |= 1u << Q.bit[o];
+  if (seen != want || (m >> Q.no) != 0) *bad = 1;
+}
+
+}  // namespace
+
+// ====================================================================== the handle
+
+struct psp_mg {
+  int n = 0, ndim = 0, steps = 2;
+  double omega = 0.8;
+  struct Level {
+    MgLevelArg a;
+    long N = 0;
+    double *x = nullptr, *b = nullptr, *t = nullptr;  // the level's vectors (levels in the tail have none)
+  };
+  std::vector<Level> lev;
+  int tail_first = 0;  // first level of the tail launch
+  int launches = 0;    // kernel launches of one application
+  double *minv = nullptr;
+  MgTailArg *tail = nullptr;
+};
+
+namespace {
+
+int level_nd(const MgLevelArg &a) { return a.n[2] > 1 ? 3 : a.n[1] > 1 ? 2 : 1; }
+
+// coarse points per workgroup of mg_restrict along each axis (256 in all): by the axes the level really has
+void mg_tile(const MgLevelArg &a, int t[3]) {
+  const int nd = level_nd(a);
+  if (nd == 1) {
+    t[0] = 256, t[1] = 1, t[2] = 1;
+  } else if (nd == 2) {
+    t[0] = 32, t[1] = 8, t[2] = 1;
+  } else {
+    t[0] = 16, t[1] = 4, t[2] = 4;
+  }
+}
+
+// the inverse of the coarsest level's matrix (dense, <= 27 x 27, symmetric positive definite) by Gauss-Jordan
+// elimination with partial pivoting
+int coarsest_inverse(const MgLevelArg &a, std::vector<double> *out) {
+  const int m = a.n[0] * a.n[1] * a.n[2];
+  std::vector<double> M((size_t)m * m, 0.0), I((size_t)m * m, 0.0);
+  const int st[3] = {1, a.n[0], a.n[0] * a.n[1]};
+  for (int r = 0; r < m; ++r) {
+    const int g[3] = {r % a.n[0], (r / a.n[0]) % a.n[1], r / (a.n[0] * a.n[1])};
+    M[(size_t)r * m + r] = a.d;
+    I[(size_t)r * m + r] = 1.0;
+    for (int x = 0; x < 3; ++x) {
+      if (a.n[x] <= 1) continue;
+      if (g[x] > 0) M[(size_t)r * m + r - st[x]] = -a.c[x];
+      if (g[x] < a.n[x] - 1) M[(size_t)r * m + r + st[x]] = -a.c[x];
+    }
+  }
+  for (int k = 0; k < m; ++k) {
+    int p = k;
+    for (int r = k + 1; r < m; ++r)
+      if (std::fabs(M[(size_t)r * m + k]) > std::fabs(M[(size_t)p * m + k])) p = r;
+    if (!(std::fabs(M[(size_t)p * m + k]) > 0.0)) return fail(PSP_ESINGULAR, "multigrid: the coarsest level is singular");
+    if (p != k)
+      for (int j = 0; j < m; ++j) {
+        std::swap(M[(size_t)p * m + j], M[(size_t)k * m + j]);
+        std::swap(I[(size_t)p * m + j], I[(size_t)k * m + j]);
+      }
+    const double piv = M[(size_t)k * m + k];
+    for (int j = 0; j < m; ++j) {
+      M[(size_t)k * m + j] /= piv;
+      I[(size_t)k * m + j] /= piv;
+    }
+    for (int r = 0; r < m; ++r) {
+      if (r == k) continue;
+      const double f = M[(size_t)r * m + k];
+      if (f == 0.0) continue;
+      for (int j = 0; j < m; ++j) {
+        M[(size_t)r * m + j] -= f * M[(size_t)k * m + j];
+        I[(size_t)r * m + j] -= f * I[(size_t)k * m + j];
+      }
+    }
+  }
+  *out = I;
+  return PSP_OK;
+}
+
+int read_flag(int *bad_dev, int *bad) {
+  PSP_HIP(hipMemcpyAsync(bad, bad_dev, sizeof(int), hipMemcpyDeviceToHost, stream()));
+  PSP_HIP(hipStreamSynchronize(stream()));
+  return PSP_OK;
+}
+
+// c_a, d0 of A and the exact check that A is that stencil on that grid -- from the CSR arrays, or, for a handle that only
+// kept its index-free layout, from that layout's offsets, values and row masks
+int read_stencil(const psp_csr *A, const int n[3], MgStencil *S) {
+  const long st[3] = {1, n[0], (long)n[0] * n[1]};
+  for (int a = 0; a < 3; ++a) {
+    S->n[a] = n[a];
+    S->c[a] = 0.0;
+  }
+  S->d0 = 0.0;
+  bool have_d = false, have_c[3] = {false, false, false};
+  int *bad_dev = nullptr;
+  int bad = 0;
+  const char *why = "multigrid: the matrix is not a constant-coefficient [-1 2 -1] stencil on this grid";
+  if (A->ind && A->col && A->val && !A->w4_only) {
+    // row 0 has its upper neighbour along every axis: it names every coefficient
+    int ind01[2];
+    PSP_HIP(hipMemcpyAsync(ind01, A->ind, 2 * sizeof(int), hipMemcpyDeviceToHost, stream()));
+    PSP_HIP(hipStreamSynchronize(stream()));
+    const int len = ind01[1] - ind01[0];
+    if (ind01[0] != 0 || len < 1 || len > 4) return fail(PSP_EINVAL, "%s (row 0 stores %d entries)", why, len);
+    int col[4];
+    double val[4];
+    PSP_HIP(hipMemcpyAsync(col, A->col, len * sizeof(int), hipMemcpyDeviceToHost, stream()));
+    PSP_HIP(hipMemcpyAsync(val, A->val, len * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    PSP_HIP(hipStreamSynchronize(stream()));
+    for (int k = 0; k < len; ++k) {
+      if (col[k] == 0) {
+        S->d0 = val[k];
+        have_d = true;
+      }
+      for (int a = 0; a < 3; ++a)
+        if (n[a] > 1 && col[k] == st[a]) {
+          S->c[a] = -val[k];
+          have_c[a] = true;
+        }
+    }
+  } else {
+    W4View v;
+    int avail = 0;
+    PSP_TRY(csr_w4_view(A, &v, &avail));
+    if (!avail || !v.constv || v.no > 7) return fail(PSP_EINVAL, "%s", why);
+    MgSlots Q;
+    Q.no = v.no;
+    double lower[3] = {0.0, 0.0, 0.0};
+    bool have_l[3] = {false, false, false};
+    for (int o = 0; o < v.no; ++o) {
+      int bit = -1;
+      if (v.offs[o] == 0) {
+        bit = 0;
+        S->d0 = v.cval[o];
+        have_d = true;
+      }
+      for (int a = 0; a < 3; ++a) {
+        if (n[a] <= 1) continue;
+        if (v.offs[o] == st[a]) {
+          bit = 2 + 2 * a;
+          S->c[a] = -v.cval[o];
+          have_c[a] = true;
+        } else if (v.offs[o] == -st[a]) {
+          bit = 1 + 2 * a;
+          lower[a] = -v.cval[o];
+          have_l[a] = true;
+        }
+      }
+      if (bit < 0) return fail(PSP_EINVAL, "%s (an entry at offset %d)", why, v.offs[o]);
+      Q.bit[o] = bit;
+    }
+    for (int a = 0; a < 3; ++a)
+      if (n[a] > 1 && (!have_c[a] || !have_l[a] || !(lower[a] == S->c[a]))) return fail(PSP_EINVAL, "%s", why);
+    if (!have_d) return fail(PSP_EINVAL, "%s", why);
+    PSP_HIP(hipMalloc((void **)&bad_dev, sizeof(int)));
+    hipError_t e = hipMemsetAsync(bad_dev, 0, sizeof(int), stream());
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(mg_check_w4_kernel, dim3((A->nrows + 255) / 256), dim3(256), 0, stream(), A->nrows, *S, Q, v.mask,
+                         bad_dev);
+      e = hipGetLastError();
+    }
+    int rc = e == hipSuccess ? read_flag(bad_dev, &bad) : fail(PSP_ENODEV, "multigrid: %s", hipGetErrorString(e));
+    (void)hipFree(bad_dev);
+    PSP_TRY(rc);
+    if (bad) return fail(PSP_EINVAL, "%s", why);
+    return PSP_OK;
+  }
+  if (!have_d) return fail(PSP_EINVAL, "%s (row 0 has no diagonal)", why);
+  for (int a = 0; a < 3; ++a)
+    if (n[a] > 1 && !have_c[a]) return fail(PSP_EINVAL, "%s (row 0 has no neighbour along axis %d)", why, a);
+  PSP_HIP(hipMalloc((void **)&bad_dev, sizeof(int)));
+  hipError_t e = hipMemsetAsync(bad_dev, 0, sizeof(int), stream());
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(mg_check_csr_kernel, dim3((A->nrows + 255) / 256), dim3(256), 0, stream(), A->nrows, *S, A->ind,
+                       A->col, A->val, bad_dev);
+    e = hipGetLastError();
+  }
+  int rc = e == hipSuccess ? read_flag(bad_dev, &bad) : fail(PSP_ENODEV, "multigrid: %s", hipGetErrorString(e));
+  (void)hipFree(bad_dev);
+  PSP_TRY(rc);
+  if (bad) return fail(PSP_EINVAL, "%s", why);
+  return PSP_OK;
+}
+
+int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, psp_mg **out) {
+  if (!A || !grid || !out) return fail(PSP_EINVAL, "psp_mg_create: NULL argument");
+  if (ndim < 1 || ndim > 3) return fail(PSP_EINVAL, "multigrid: grid must have 1 to 3 axes");
+  int n[3] = {1, 1, 1};
+  long prod = 1;
+  for (int a = 0; a < ndim; ++a) {
+    if (grid[a] < 1) return fail(PSP_EINVAL, "multigrid: grid axes must be positive");
+    n[a] = grid[a];
+    prod *= grid[a];
+    if (prod > 0x7fffffffL) return fail(PSP_EINVAL, "multigrid: prod(grid) does not match the matrix order");
+  }
+  if (A->nrows != A->ncols) return fail(PSP_EINVAL, "matrix is not square");
+  if (prod != A->nrows) return fail(PSP_EINVAL, "multigrid: prod(grid) = %ld does not match the matrix order %d", prod, A->nrows);
+  if (!(omega > 0.0 && omega <= 1.0)) return fail(PSP_EINVAL, "multigrid: omega must satisfy 0 < omega <= 1");
+  if (steps < 1) return fail(PSP_EINVAL, "multigrid: steps must be >= 1");
+  PSP_TRY(csr_spmm_check("precon.multigrid", A));
+  PSP_TRY(ensure_device());
+  MgStencil S;
+  PSP_TRY(read_stencil(A, n, &S));
+  double csum = 0.0;
+  for (int a = 0; a < 3; ++a) {
+    if (n[a] > 1 && !(S.c[a] > 0.0)) return fail(PSP_EINVAL, "multigrid: the coupling along axis %d is not negative", a);
+    csum += S.c[a];
+  }
+  double s = S.d0 - 2.0 * csum;
+  if (!(s >= -16.0 * DBL_EPSILON * std::fabs(S.d0)) || !(S.d0 > 0.0))
+    return fail(PSP_EINVAL, "multigrid: the shift s = diagonal - 2 sum c = %g is negative", s);
+  if (s < 0.0) s = 0.0;
+
+  psp_mg *K = new psp_mg();
+  K->n = A->nrows;
+  K->ndim = ndim;
+  K->omega = omega;
+  K->steps = steps;
+  // the levels
+  {
+    int cur[3] = {n[0], n[1], n[2]};
+    double c[3] = {S.c[0], S.c[1], S.c[2]};
+    for (;;) {
+      psp_mg::Level L;
+      int coarsened = 0;
+      double sum = 0.0;
+      for (int a = 0; a < 3; ++a) {
+        L.a.n[a] = cur[a];
+        L.a.c[a] = cur[a] > 1 ? c[a] : 0.0;
+        L.a.co[a] = cur[a] >= 4;
+        L.a.nc[a] = L.a.co[a] ? cur[a] / 2 : cur[a];
+        coarsened += L.a.co[a];
+        sum += L.a.c[a];
+      }
+      L.a.d = 2.0 * sum + s;
+      L.a.w = omega / L.a.d;
+      L.a.rs = 1.0 / (double)(1 << coarsened);
+      L.N = (long)cur[0] * cur[1] * cur[2];
+      K->lev.push_back(L);
+      if (!coarsened) break;
+      for (int a = 0; a < 3; ++a)
+        if (L.a.co[a]) {
+          cur[a] /= 2;
+          c[a] /= 4.0;
+        }
+    }
+  }
+  const int nl = (int)K->lev.size();
+  K->tail_first = nl - 1;
+  while (K->tail_first > 0 && K->lev[K->tail_first - 1].N <= kTailT) --K->tail_first;
+  int rc = PSP_OK;
+  if (nl - K->tail_first > kTailMaxLev || nl > kMaxLevels) rc = fail(PSP_EINVAL, "multigrid: too many levels");
+  // launches of one application: per large level the pre-smoothing (the first two sweeps are one pass), the restriction,
+  // the prolongation and the post-smoothing; one for the tail
+  K->launches = 1;
+  for (int l = 0; l < K->tail_first; ++l) K->launches += (steps >= 2 ? steps - 1 : 1) + 1 + 1 + steps;
+  // level vectors: the finest level works in the caller's vectors and one spare; a level that heads the tail needs its
+  // b and x in memory (the restriction above it writes b, the prolongation reads x)
+  for (int l = 0; l <= K->tail_first && rc == PSP_OK; ++l) {
+    psp_mg::Level &L = K->lev[l];
+    const size_t bytes = sizeof(double) * (size_t)L.N;
+    hipError_t e = hipSuccess;
+    if (l < K->tail_first) e = hipMalloc((void **)&L.t, bytes);
+    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&L.x, bytes);
+    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&L.b, bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      rc = fail(PSP_ENOMEM, "multigrid: level vector allocation failed");
+    }
+  }
+  std::vector<double> inv;
+  if (rc == PSP_OK) rc = coarsest_inverse(K->lev[nl - 1].a, &inv);
+  if (rc == PSP_OK) {
+    MgTailArg T;
+    memset(&T, 0, sizeof T);
+    T.nlev = nl - K->tail_first;
+    T.steps = steps;
+    int off = 0;
+    for (int l = K->tail_first; l < nl; ++l) {
+      T.off[l - K->tail_first] = off;
+      T.lev[l - K->tail_first] = K->lev[l].a;
+      off += (int)K->lev[l].N;
+    }
+    if (off > 2 * kTailT) rc = fail(PSP_EINVAL, "multigrid: the tail does not fit");
+    if (rc == PSP_OK &&
+        (hipMalloc((void **)&K->minv, sizeof(double) * inv.size()) != hipSuccess ||
+         hipMalloc((void **)&K->tail, sizeof(MgTailArg)) != hipSuccess ||
+         hipMemcpy(K->minv, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess ||
+         hipMemcpy(K->tail, &T, sizeof T, hipMemcpyHostToDevice) != hipSuccess)) {
+      (void)hipGetLastError();
+      rc = fail(PSP_ENOMEM, "multigrid: tail table allocation failed");
+    }
+  }
+  if (rc != PSP_OK) {
+    psp_mg_destroy(K);
+    return rc;
+  }
+  *out = K;
+  return PSP_OK;
+}
+
+template <bool FROMB>
+void launch_smooth(const psp_mg::Level &L, const double *xin, const double *b, double *xout) {
+  const dim3 g((unsigned)((L.N + 255) / 256)), t(256);
+  switch (level_nd(L.a)) {
+    case 1: hipLaunchKernelGGL((mg_smooth_kernel<1, FROMB>), g, t, 0, stream(), L.a, L.N, xin, b, xout); break;
+    case 2: hipLaunchKernelGGL((mg_smooth_kernel<2, FROMB>), g, t, 0, stream(), L.a, L.N, xin, b, xout); break;
+    default: hipLaunchKernelGGL((mg_smooth_kernel<3, FROMB>), g, t, 0, stream(), L.a, L.N, xin, b, xout); break;
+  }
+}
+
+}  // namespace
+
+namespace psp {
+
+// y = V(0, b) on device vectors; y must not alias b.  The handle is locked by the caller.
+int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
+  const int steps = K->steps, tf = K->tail_first;
+  // where each large level's iterate is after its pre-smoothing; every sweep writes the buffer the previous one did not
+  double *cur[kMaxLevels] = {};
+  // down
+  for (int l = 0; l < tf; ++l) {
+    const psp_mg::Level &L = K->lev[l];
+    const double *b = l == 0 ? b_dev : L.b;
+    double *const own = l == 0 ? y_dev : L.x;
+    // the finest level's last sweep must land in y: its writes are the pre-smoothing launches and `steps` more
+    const int writes = (steps >= 2 ? steps - 1 : 1) + steps;
+    double *dst = (l == 0 && (writes & 1) == 0) ? L.t : own;
+    const dim3 g((unsigned)((L.N + 255) / 256)), t(256);
+    if (steps == 1) {
+      hipLaunchKernelGGL(mg_scale_kernel, g, t, 0, stream(), L.N, L.a.w, b, dst);
+    } else {
+      launch_smooth<true>(L, nullptr, b, dst);
+      for (int k = 2; k < steps; ++k) {
+        double *nxt = dst == own ? L.t : own;
+        launch_smooth<false>(L, dst, b, nxt);
+        dst = nxt;
+      }
+    }
+    cur[l] = dst;
+    int tile[3];
+    mg_tile(L.a, tile);
+    // at most ceil(nc0 / t0) ceil(nc1 / t1) ceil(nc2 / t2) <= 2^31 / 256 + a few tiles: fits gridDim.x
+    const long g0n = (L.a.nc[0] + tile[0] - 1) / tile[0], g1n = (L.a.nc[1] + tile[1] - 1) / tile[1],
+               g2n = (L.a.nc[2] + tile[2] - 1) / tile[2];
+    hipLaunchKernelGGL(mg_restrict_kernel, dim3((unsigned)(g0n * g1n * g2n)), dim3(kResThreads), 0, stream(), L.a, tile[0],
+                       tile[1], tile[2], (int)g0n, (int)g1n, (const double *)dst, b, K->lev[l + 1].b);
+    PSP_LAUNCH_CHECK();
+  }
+  // the tail
+  {
+    const double *b = tf == 0 ? b_dev : K->lev[tf].b;
+    double *x = tf == 0 ? y_dev : K->lev[tf].x;
+    hipLaunchKernelGGL(mg_tail_kernel, dim3(1), dim3(kTailThreads), 0, stream(), (const MgTailArg *)K->tail,
+                       (const double *)K->minv, b, x);
+    PSP_LAUNCH_CHECK();
+    cur[tf] = x;
+  }
+  // up
+  for (int l = tf - 1; l >= 0; --l) {
+    const psp_mg::Level &L = K->lev[l];
+    const double *b = l == 0 ? b_dev : L.b;
+    double *const own = l == 0 ? y_dev : L.x;
+    double *x = cur[l];
+    const dim3 g((unsigned)((L.N + 255) / 256)), t(256);
+    hipLaunchKernelGGL(mg_prolong_kernel, g, t, 0, stream(), L.a, L.N, (const double *)cur[l + 1], x);
+    for (int k = 0; k < steps; ++k) {
+      double *nxt = x == own ? L.t : own;
+      launch_smooth<false>(L, x, b, nxt);
+      x = nxt;
+    }
+    cur[l] = x;
+    PSP_LAUNCH_CHECK();
+  }
+  if (tf > 0 && cur[0] != y_dev) return fail(PSP_EINVAL, "multigrid: internal error (the result is not in y)");
+  return PSP_OK;
+}
+
+}  // namespace psp
+
+extern "C" {
+
+int psp_mg_create_csr(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
+  PSP_API_GUARD_H(A);
+  return mg_create(A, ndim, grid, omega, steps, out);
+}
+
+int psp_mg_create_sss(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
+  PSP_API_GUARD_H(A, A ? A->full : nullptr);
+  if (!A) return fail(PSP_EINVAL, "psp_mg_create_sss: NULL argument");
+  if (A->host || cpu_mode())
+    return fail(PSP_ENODEV, "precon.multigrid: not available with PSP_DEVICE=cpu (host mode covers csr / sss / jacobi / pcg / minres)");
+  if (!A->full) return fail(PSP_EINVAL, "psp_mg_create_sss: the matrix has no device mirror");
+  return mg_create(A->full, ndim, grid, omega, steps, out);
+}
+
+int psp_mg_destroy(psp_mg_t *K) {
+  if (!K) return PSP_OK;
+  for (psp_mg::Level &L : K->lev)
+    for (void *p : {(void *)L.x, (void *)L.b, (void *)L.t}) (void)hipFree(p);
+  (void)hipFree(K->minv);
+  (void)hipFree(K->tail);
+  delete K;
+  return PSP_OK;
+}
+
+int psp_mg_info(const psp_mg_t *K, int *levels, int *tail_first_level, int *launches_per_apply, int *dims) {
+  if (!K) return fail(PSP_EINVAL, "psp_mg_info: NULL handle");
+  if (levels) *levels = (int)K->lev.size();
+  if (tail_first_level) *tail_first_level = K->tail_first;
+  if (launches_per_apply) *launches_per_apply = K->launches;
+  if (dims)
+    for (size_t l = 0; l < K->lev.size(); ++l)
+      for (int a = 0; a < 3; ++a) dims[3 * l + a] = K->lev[l].a.n[a];
+  return PSP_OK;
+}
+
+int psp_op_from_mg(psp_mg_t *K, psp_op_t **out) {
+  if (!K || !out) return fail(PSP_EINVAL, "psp_op_from_mg: NULL argument");
+  psp_op *op = new psp_op();
+  op->kind = PSP_OP_MG;
+  op->n = K->n;
+  op->mg = K;
+  *out = op;
+  return PSP_OK;
+}
+
+int psp_mg_precon_dev(psp_mg_t *K, const double *x_dev, double *y_dev) {
+  PSP_API_GUARD_H(K);
+  if (!K || !x_dev || !y_dev) return fail(PSP_EINVAL, "psp_mg_precon_dev: NULL argument");
+  if (x_dev == y_dev) return fail(PSP_EINVAL, "psp_mg_precon_dev: y must not alias x");
+  return mg_apply_dev(K, x_dev, y_dev);
+}
+
+int psp_mg_precon(psp_mg_t *K, const double *x_host, double *y_host) {
+  PSP_API_GUARD_H(K);
+  if (!K || !x_host || !y_host) return fail(PSP_EINVAL, "psp_mg_precon: NULL argument");
+  PSP_TRY(ensure_device());
+  const size_t n = (size_t)K->n, bytes = sizeof(double) * n;
+  double *x = nullptr, *y = nullptr;
+  PSP_TRY(scratch_get(n, &x));
+  int rc = scratch_get(n, &y);
+  if (rc != PSP_OK) {
+    scratch_put(x, n);
+    return rc;
+  }
+  hipError_t e = hipMemcpyAsync(x, x_host, bytes, hipMemcpyHostToDevice, stream());
+  if (e == hipSuccess) rc = mg_apply_dev(K, x, y);
+  if (e == hipSuccess && rc == PSP_OK) e = hipMemcpyAsync(y_host, y, bytes, hipMemcpyDeviceToHost, stream());
+  const hipError_t e2 = hipStreamSynchronize(stream());
+  scratch_put(x, n);
+  scratch_put(y, n);
+  if (rc != PSP_OK) return rc;
+  if (e != hipSuccess || e2 != hipSuccess)
+    return fail(PSP_ENODEV, "psp_mg_precon: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+  return PSP_OK;
+}
+
+}  // extern "C"

@@ -251,6 +251,8 @@ int op_apply(const psp_op *op, const double *x_dev, double *y_dev) {
       return jacobi_apply_dev(op->jac, x_dev, y_dev);
     case PSP_OP_SSOR:
       return ssor_apply_dev(op->ssor, x_dev, y_dev);
+    case PSP_OP_MG:
+      return mg_apply_dev(op->mg, x_dev, y_dev);
     case PSP_OP_CORREQ:
       return correq_apply(op, x_dev, y_dev);
     case PSP_OP_CALLBACK: {

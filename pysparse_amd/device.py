@@ -411,6 +411,8 @@ class _Op:
             check(lib().psp_op_from_jacobi(obj._h, C.byref(h)))
         elif isinstance(obj, DeviceSSOR):
             check(lib().psp_op_from_ssor(obj._h, C.byref(h)))
+        elif isinstance(obj, DeviceMultigrid):
+            check(lib().psp_op_from_mg(obj._h, C.byref(h)))
         else:
             # duck-typed operator: shape + matvec/precon (spmatrixmodule.c:86-132, :169-248)
             shape = obj.shape
@@ -535,6 +537,86 @@ class DeviceSSOR:
     def close(self):
         if getattr(self, "_h", None):
             lib().psp_ssor_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _check_einval(rc):
+    """PSP_EINVAL of a constructor -> ValueError with the library's text, anything else as check() raises it"""
+    if rc == -1:
+        raise ValueError(lib().psp_last_error().decode())
+    return check(rc)
+
+
+class DeviceMultigrid:
+    """precon.multigrid(A, grid, omega=0.8, steps=2): a matrix-free geometric V-cycle for the constant-coefficient grid
+    operators A = sum_a c_a T_a + s I (psp_mg.hip; no reference analogue).  `levels` are the level grids, finest first."""
+
+    def __init__(self, A, grid, omega=0.8, steps=2):
+        if not isinstance(A, (DeviceCSR, DeviceSSS)):
+            raise TypeError("multigrid() argument 1 must be a csr_mat or sss_mat handle")
+        if isinstance(grid, (str, bytes)) or not hasattr(grid, "__len__") or not hasattr(grid, "__getitem__"):
+            raise TypeError("multigrid() argument 2 must be a sequence of 1 to 3 positive integers")
+        if not 1 <= len(grid) <= 3:
+            raise ValueError("grid must have 1 to 3 axes")
+        dims = []
+        for g in grid:
+            if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+                raise TypeError("grid axes must be integers")
+            if g < 1:
+                raise ValueError("grid axes must be positive integers")
+            dims.append(int(g))
+        shape = A.shape if isinstance(A, DeviceCSR) else (A.n, A.n)
+        if shape[0] != shape[1]:
+            raise ValueError("matrix is not square")
+        if int(np.prod(dims, dtype=object)) != shape[0]:
+            raise ValueError("prod(grid) does not match the matrix order")
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)):
+            raise TypeError("steps must be an integer")
+        omega, steps = float(omega), int(steps)
+        if not 0.0 < omega <= 1.0:
+            raise ValueError("omega must satisfy 0 < omega <= 1")
+        if steps < 1:
+            raise ValueError("steps must be >= 1")
+        h = C.c_void_p()
+        g = (C.c_int * len(dims))(*dims)
+        create = lib().psp_mg_create_csr if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss
+        _check_einval(create(A._h, len(dims), g, omega, steps, C.byref(h)))
+        self._A = A
+        self._h = h
+        self.shape = (shape[0], shape[0])
+        self.ndim = len(dims)
+        self.levels = tuple(lv[:self.ndim] for lv in self.info()["dims"])
+
+    def info(self):
+        """levels, first level of the single-workgroup tail launch, kernel launches per application, level dimensions
+        (three per level, 1 on absent axes)"""
+        nl, tf, la = C.c_int(), C.c_int(), C.c_int()
+        check(lib().psp_mg_info(self._h, C.byref(nl), C.byref(tf), C.byref(la), None))
+        d = (C.c_int * (3 * nl.value))()
+        check(lib().psp_mg_info(self._h, None, None, None, d))
+        return {"levels": nl.value, "tail_first_level": tf.value, "launches_per_apply": la.value,
+                "dims": tuple(tuple(d[3 * l:3 * l + 3]) for l in range(nl.value))}
+
+    def precon(self, x, y):
+        n = self.shape[0]
+        for k, a in ((1, x), (2, y)):
+            if (not isinstance(a, np.ndarray) or a.ndim != 1 or a.dtype != np.float64 or a.shape[0] != n
+                    or not a.flags.c_contiguous):
+                raise ValueError("arg %d must be a contiguous 1-dimensional double array of appropriate size." % k)
+        check(lib().psp_mg_precon(self._h, _ptr(x), _ptr(y)))
+
+    def precon_dev(self, x_ptr, y_ptr):
+        check(lib().psp_mg_precon_dev(self._h, x_ptr, y_ptr))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().psp_mg_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1,7 +1,8 @@
 /*
  * pysparse_amd.precon.precon -- jacobi(A, omega=1.0, steps=1) and ssor(A, omega=1.0, steps=1):
  * objects with `shape` and `precon(x, y)` (pysparse/precon/src/preconmodule.c:11-80, 352-412,
- * 470-485 for jacobi; :21-31, 95-223, 414-459, 487-510 for ssor).
+ * 470-485 for jacobi; :21-31, 95-223, 414-459, 487-510 for ssor); multigrid(A, grid, omega=0.8, steps=2) has the
+ * same shape and no reference analogue.
  *
  * dinv[i] = omega / A[i,i] lives on the GPU.  Native matrices hand over their diagonal on
  * the device (csr_mat / sss_mat; the reference can only subscript ll_mat, so jacobi(csr_mat)
@@ -246,6 +247,182 @@ static PyGetSetDef SSOR_getset[] = {{"shape", (getter)SSOR_get_shape, NULL, "(n,
                                     {"_psp_op", (getter)SSOR_get_psp_op, NULL, "device operator", NULL},
                                     {NULL, NULL, NULL, NULL, NULL}};
 
+
+/* ------------------------------------------------------------------------- multigrid */
+
+/* multigrid(A, grid, omega=0.8, steps=2): geometric V-cycle for the constant-coefficient grid operators (psp_mg.hip);
+ * no reference analogue */
+#define MG_MAX_LEVELS 40
+
+typedef struct {
+  PyObject_VAR_HEAD
+  int n;
+  int ndim;
+  PyObject *matrix; /* kept for the caller's sake: the handle reads it at creation only */
+  psp_mg_t *dev;
+  psp_op_t *op;
+} MGObject;
+
+static PyTypeObject MGType;
+
+static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
+  static char *kwlist[] = {"A", "grid", "omega", "steps", NULL};
+  PyObject *matrix, *grid, *seq, *cap;
+  double omega = 0.8;
+  int steps = 2, ndim, a, rc, shape[2], dims[3] = {1, 1, 1};
+  int is_csr, is_sss, is_ll;
+  long long prod = 1;
+  MGObject *op;
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|di", kwlist, &matrix, &grid, &omega, &steps)) return NULL;
+  is_csr = PyObject_TypeCheck(matrix, &CSRMatType);
+  is_sss = PyObject_TypeCheck(matrix, &SSSMatType);
+  is_ll = PyObject_TypeCheck(matrix, &LLMatType);
+  if (!is_csr && !is_sss && !is_ll) {
+    PyErr_SetString(PyExc_TypeError, "multigrid() argument 1 must be csr_mat, sss_mat or ll_mat");
+    return NULL;
+  }
+  if (!PySequence_Check(grid) || PyUnicode_Check(grid) || PyBytes_Check(grid)) {
+    PyErr_SetString(PyExc_TypeError, "multigrid() argument 2 must be a sequence of 1 to 3 positive integers");
+    return NULL;
+  }
+  seq = PySequence_Fast(grid, "multigrid() argument 2 must be a sequence of 1 to 3 positive integers");
+  if (seq == NULL) return NULL;
+  ndim = (int)PySequence_Fast_GET_SIZE(seq);
+  if (ndim < 1 || ndim > 3) {
+    Py_DECREF(seq);
+    PyErr_SetString(PyExc_ValueError, "grid must have 1 to 3 axes");
+    return NULL;
+  }
+  for (a = 0; a < ndim; a++) {
+    long v = PyLong_AsLong(PySequence_Fast_GET_ITEM(seq, a));
+    if (v == -1 && PyErr_Occurred()) {
+      Py_DECREF(seq);
+      return NULL; /* TypeError of a non-integer, OverflowError */
+    }
+    if (v < 1 || v > 0x7fffffffL) {
+      Py_DECREF(seq);
+      PyErr_SetString(PyExc_ValueError, "grid axes must be positive integers");
+      return NULL;
+    }
+    dims[a] = (int)v;
+    prod *= v;
+    if (prod > 0x7fffffffLL) prod = 0x80000000LL; /* matches no matrix order */
+  }
+  Py_DECREF(seq);
+  if (SpMatrix_GetShape(matrix, shape)) return NULL;
+  if (shape[0] != shape[1]) {
+    PyErr_SetString(PyExc_ValueError, "matrix is not square");
+    return NULL;
+  }
+  if (prod != (long long)shape[0]) {
+    PyErr_SetString(PyExc_ValueError, "prod(grid) does not match the matrix order");
+    return NULL;
+  }
+  if (!(omega > 0.0 && omega <= 1.0)) {
+    PyErr_SetString(PyExc_ValueError, "omega must satisfy 0 < omega <= 1");
+    return NULL;
+  }
+  if (steps < 1) {
+    PyErr_SetString(PyExc_ValueError, "steps must be >= 1");
+    return NULL;
+  }
+  if (is_ll) { /* the device mirror of the linked list is built by the operator getter */
+    cap = PyObject_GetAttrString(matrix, "_psp_op");
+    if (cap == NULL) return NULL;
+    Py_DECREF(cap);
+    if (((LLMatObject *)matrix)->mirror == NULL) {
+      PyErr_SetString(PyExc_RuntimeError, "ll_mat has no device mirror");
+      return NULL;
+    }
+  }
+  op = PyObject_New(MGObject, &MGType);
+  if (op == NULL) return PyErr_NoMemory();
+  op->n = shape[0];
+  op->ndim = ndim;
+  op->matrix = NULL;
+  op->dev = NULL;
+  op->op = NULL;
+  Py_BEGIN_ALLOW_THREADS
+  if (is_sss)
+    rc = psp_mg_create_sss(((SSSMatObject *)matrix)->dev, ndim, dims, omega, steps, &op->dev);
+  else
+    rc = psp_mg_create_csr(is_csr ? ((CSRMatObject *)matrix)->dev : ((LLMatObject *)matrix)->mirror, ndim, dims, omega,
+                           steps, &op->dev);
+  Py_END_ALLOW_THREADS
+  if (rc != PSP_OK) {
+    Py_DECREF(op);
+    return raise_psp(rc);
+  }
+  Py_INCREF(matrix);
+  op->matrix = matrix;
+  return (PyObject *)op;
+}
+
+/* self.precon(x, y): one V-cycle -- contiguous arrays only */
+static PyObject *MG_precon(MGObject *self, PyObject *args) {
+  double *x, *y;
+  int rc;
+  if (SpMatrix_ParseVecOpArgs(args, &x, &y, self->n)) return NULL;
+  Py_BEGIN_ALLOW_THREADS
+  rc = psp_mg_precon(self->dev, x, y);
+  Py_END_ALLOW_THREADS
+  if (rc != PSP_OK) return raise_psp(rc);
+  Py_RETURN_NONE;
+}
+
+static void MG_dealloc(MGObject *self) {
+  if (self->op) psp_op_destroy(self->op);
+  if (self->dev) psp_mg_destroy(self->dev);
+  Py_XDECREF(self->matrix);
+  PyObject_Del(self);
+}
+
+static PyObject *MG_get_shape(MGObject *self, void *c) { return Py_BuildValue("(i,i)", self->n, self->n); }
+
+static PyObject *MG_get_psp_op(MGObject *self, void *c) {
+  if (self->op == NULL) {
+    int rc = psp_op_from_mg(self->dev, &self->op);
+    if (rc != PSP_OK) return raise_psp(rc);
+  }
+  return PyCapsule_New(self->op, PSP_OP_CAPSULE_NAME, NULL);
+}
+
+/* the level grids, finest first: a tuple of tuples with as many entries as `grid` had */
+static PyObject *MG_get_levels(MGObject *self, void *c) {
+  int levels = 0, l, a, rc, dims[3 * MG_MAX_LEVELS];
+  PyObject *out;
+  rc = psp_mg_info(self->dev, &levels, NULL, NULL, NULL);
+  if (rc != PSP_OK) return raise_psp(rc);
+  if (levels > MG_MAX_LEVELS) {
+    PyErr_SetString(PyExc_RuntimeError, "too many levels");
+    return NULL;
+  }
+  rc = psp_mg_info(self->dev, NULL, NULL, NULL, dims);
+  if (rc != PSP_OK) return raise_psp(rc);
+  out = PyTuple_New(levels);
+  if (out == NULL) return NULL;
+  for (l = 0; l < levels; l++) {
+    PyObject *t = PyTuple_New(self->ndim);
+    if (t == NULL) {
+      Py_DECREF(out);
+      return NULL;
+    }
+    for (a = 0; a < self->ndim; a++) PyTuple_SET_ITEM(t, a, PyLong_FromLong(dims[3 * l + a]));
+    PyTuple_SET_ITEM(out, l, t);
+  }
+  return out;
+}
+
+static PyMethodDef MG_methods[] = {
+    {"precon", (PyCFunction)MG_precon, METH_VARARGS,
+     "self.precon(x, y)\n\napply preconditioner self on x, store result in y. x is unchanged."},
+    {NULL, NULL, 0, NULL}};
+
+static PyGetSetDef MG_getset[] = {{"shape", (getter)MG_get_shape, NULL, "(n, n)", NULL},
+                                  {"levels", (getter)MG_get_levels, NULL, "the level grids, finest first", NULL},
+                                  {"_psp_op", (getter)MG_get_psp_op, NULL, "device operator", NULL},
+                                  {NULL, NULL, NULL, NULL, NULL}};
+
 static PyMethodDef precon_methods[] = {
     {"jacobi", (PyCFunction)jacobi_prec, METH_VARARGS | METH_KEYWORDS,
      "jacobi(A, omega=1.0, steps=1)\n\nnew Jacobi preconditioner object"},
@@ -255,6 +432,13 @@ static PyMethodDef precon_methods[] = {
      "A      'sss_mat' object, symmetric sparse matrix\n"
      "omega  relaxation parameter (default value: 1.0)\n"
      "steps  number of SSOR steps"},
+    {"multigrid", (PyCFunction)multigrid_prec, METH_VARARGS | METH_KEYWORDS,
+     "multigrid(A, grid, omega=0.8, steps=2) -- return geometric multigrid preconditioner object\n\n"
+     "One V-cycle with damped-Jacobi smoothing for A = sum_a c_a T_a + s I on a grid (no reference analogue).\n\n"
+     "A      'csr_mat', 'sss_mat' or 'll_mat': the constant-coefficient [-1 2 -1] stencil on the grid\n"
+     "grid   (n0[, n1[, n2]]), prod(grid) == n, row k = i0 + n0*i1 + n0*n1*i2\n"
+     "omega  damping of the Jacobi sweeps, 0 < omega <= 1 (default value: 0.8)\n"
+     "steps  sweeps before and after the coarse-grid correction (default value: 2)"},
     {NULL, NULL, 0, NULL}};
 
 static struct PyModuleDef precon_module = {PyModuleDef_HEAD_INIT, "precon",
@@ -287,11 +471,24 @@ PyMODINIT_FUNC PyInit_precon(void) {
   SSORType.tp_methods = SSOR_methods;
   SSORType.tp_getset = SSOR_getset;
   if (PyType_Ready(&SSORType) < 0) return NULL;
+  {
+    PyTypeObject zero = {PyVarObject_HEAD_INIT(NULL, 0)};
+    MGType = zero;
+  }
+  MGType.tp_name = "pysparse_amd.precon.precon.multigrid";
+  MGType.tp_basicsize = sizeof(MGObject);
+  MGType.tp_dealloc = (destructor)MG_dealloc;
+  MGType.tp_flags = Py_TPFLAGS_DEFAULT;
+  MGType.tp_methods = MG_methods;
+  MGType.tp_getset = MG_getset;
+  if (PyType_Ready(&MGType) < 0) return NULL;
   m = PyModule_Create(&precon_module);
   if (m == NULL) return NULL;
   Py_INCREF(&JacobiType);
   PyModule_AddObject(m, "JacobiType", (PyObject *)&JacobiType);
   Py_INCREF(&SSORType);
   PyModule_AddObject(m, "SSORType", (PyObject *)&SSORType);
+  Py_INCREF(&MGType);
+  PyModule_AddObject(m, "MultigridType", (PyObject *)&MGType);
   return m;
 }
