@@ -393,6 +393,27 @@ int psp_mg_precon_dev(psp_mg_t *K, const double *x_dev, double *y_dev);
  * dims may be NULL) */
 int psp_mg_info(const psp_mg_t *K, int *levels, int *tail_first_level, int *launches_per_apply, int *dims);
 
+/* precon.multigrid(A, grid, omega, steps, galerkin=True): the same cycle (level grids, P, R, smoother, tail, dense
+ * coarsest solve) for ANY symmetric 3- / 5- / 7-point operator on the grid, e.g. -div(kappa grad u) + s u with kappa varying
+ * from cell to cell: the level operators are A_0 = A, A_{l+1} = R_l A_l P_l, stored as symmetric stencils (the diagonal
+ * and one array per lower offset), the smoother is x += (omega / diag(A_l)) o (b - A_l x).  DESIGN.md 9d.  One device pass
+ * checks every row: entries only at offset 0 or +-stride of an axis with n_a > 1, none across a line end, none twice, the
+ * diagonal stored, finite and > 0, A[k, k+st] == A[k+st, k] bit for bit (a neighbour that is not stored counts as 0);
+ * anything else is PSP_EINVAL naming the first kind of violation, as are multi-device handles, handles stored in parts
+ * and handles without their index arrays (psp_csr_poisson_big, after psp_csr_release_arrays).  PSP_ESINGULAR when a level
+ * diagonal is not finite and > 0.  The handle is used through psp_mg_precon / _precon_dev / _info / _destroy and
+ * psp_op_from_mg like the matrix-free one. */
+int psp_mg_create_csr_galerkin(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out);
+int psp_mg_create_sss_galerkin(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out);
+/* 1 when the handle stores Galerkin level operators, 0 for the matrix-free mode */
+int psp_mg_is_galerkin(const psp_mg_t *K, int *galerkin);
+/* Test hook: level `level`'s stored stencil arrays, the diagonal first, then one array per lower offset o with entry K =
+ * A_l[K, K+o] (0 where that neighbour does not exist); every level, those of the tail included.  *noff_inout: in, the
+ * room in arrays; out, the arrays of the level (1 + lower offsets).  offsets_out takes 3 ints (d0, d1, d2) per array,
+ * values_host prod(level grid) doubles per array; with both NULL only the count is returned.  PSP_EINVAL for a
+ * matrix-free handle. */
+int psp_mg_level_operator(psp_mg_t *K, int level, int *offsets_out, int *noff_inout, double *values_host);
+
 /* --------------------------------------------------------- operator protocol */
 
 /* Host callback operator: the C image of SpMatrix_Matvec / SpMatrix_Precon

@@ -32,6 +32,7 @@ psp_jacobi_create_csr psp_jacobi_create_sss psp_jacobi_create_diag psp_jacobi_de
 psp_jacobi_shape psp_jacobi_precon psp_jacobi_precon_dev
 psp_ssor_create psp_ssor_destroy psp_ssor_info psp_ssor_run_info psp_ssor_brick_info psp_ssor_precon psp_ssor_precon_dev
 psp_mg_create_csr psp_mg_create_sss psp_mg_destroy psp_mg_precon psp_mg_precon_dev psp_mg_info psp_op_from_mg
+psp_mg_create_csr_galerkin psp_mg_create_sss_galerkin psp_mg_is_galerkin psp_mg_level_operator
 psp_op_from_csr psp_op_from_sss psp_op_from_jacobi psp_op_from_ssor psp_op_from_callback psp_op_destroy
 psp_pcg psp_pcg_dev psp_minres psp_minres_dev psp_cgs psp_bicgstab psp_qmrs psp_gmres
 psp_k_dot psp_k_residual psp_k_pupdate psp_k_csr_matvec_dot psp_k_xr_update psp_k_gather
@@ -155,6 +156,8 @@ def _declare(L):
         "psp_ssor_create": [vp, d, i, pvp], "psp_ssor_destroy": [vp], "psp_ssor_info": [vp, pi, pi, pi], "psp_ssor_run_info": [vp, pi, pi, vp, vp], "psp_ssor_brick_info": [vp, pi, pi],
         "psp_ssor_precon": [vp, vp, vp], "psp_ssor_precon_dev": [vp, vp, vp], "psp_op_from_ssor": [vp, pvp],
         "psp_mg_create_csr": [vp, i, pi, d, i, pvp], "psp_mg_create_sss": [vp, i, pi, d, i, pvp], "psp_mg_destroy": [vp],
+        "psp_mg_create_csr_galerkin": [vp, i, pi, d, i, pvp], "psp_mg_create_sss_galerkin": [vp, i, pi, d, i, pvp],
+        "psp_mg_is_galerkin": [vp, pi], "psp_mg_level_operator": [vp, i, pi, pi, vp],
         "psp_mg_precon": [vp, vp, vp], "psp_mg_precon_dev": [vp, vp, vp], "psp_mg_info": [vp, pi, pi, pi, pi],
         "psp_op_from_mg": [vp, pvp],
         "psp_op_from_csr": [vp, pvp], "psp_op_from_sss": [vp, pvp], "psp_op_from_jacobi": [vp, pvp],

@@ -17,10 +17,15 @@
 // mg_restrict (a workgroup owns a tile of coarse points, forms the fine residuals of the tile plus halo in LDS and
 // writes only b_c), mg_prolong (x += P e), mg_tail (the largest level of at most kTailT points and everything below
 // it, down and up, dense solve included, in ONE launch of one workgroup with the vectors in LDS).
+//
+// galerkin = True (psp_mg_create_*_galerkin) is the same cycle for any symmetric 3- / 5- / 7-point
+// operator on the grid, with stored level operators A_{l+1} = R A_l P: its kernels are in psp_mg_galerkin.h, which this file
+// includes; its creation and its schedule are below, next to the matrix-free ones.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "psp_internal.h"
@@ -410,6 +415,8 @@ __global__ __launch_bounds__(256) void mg_check_w4_kernel(int n, MgStencil S, Mg
 
 }  // namespace
 
+#include "psp_mg_galerkin.h"
+
 // ====================================================================== the handle
 
 struct psp_mg {
@@ -425,6 +432,12 @@ struct psp_mg {
   int launches = 0;    // kernel launches of one application
   double *minv = nullptr;
   MgTailArg *tail = nullptr;
+  // galerkin = True (psp_mg_galerkin.h): the stored level operators; `coef` owns each level's arrays in one allocation
+  // (diagonal, omega / diagonal, the lower arrays)
+  bool galerkin = false;
+  std::vector<GLevel> glev;
+  std::vector<double *> coef;
+  GTailArg *gtail = nullptr;
 };
 
 namespace {
@@ -445,20 +458,28 @@ void mg_tile(const MgLevelArg &a, int t[3]) {
 
 // the inverse of the coarsest level's matrix (dense, <= 27 x 27, symmetric positive definite) by Gauss-Jordan
 // elimination with partial pivoting
+int dense_inverse(int m, std::vector<double> &M, std::vector<double> *out);
+
 int coarsest_inverse(const MgLevelArg &a, std::vector<double> *out) {
   const int m = a.n[0] * a.n[1] * a.n[2];
-  std::vector<double> M((size_t)m * m, 0.0), I((size_t)m * m, 0.0);
+  std::vector<double> M((size_t)m * m, 0.0);
   const int st[3] = {1, a.n[0], a.n[0] * a.n[1]};
   for (int r = 0; r < m; ++r) {
     const int g[3] = {r % a.n[0], (r / a.n[0]) % a.n[1], r / (a.n[0] * a.n[1])};
     M[(size_t)r * m + r] = a.d;
-    I[(size_t)r * m + r] = 1.0;
     for (int x = 0; x < 3; ++x) {
       if (a.n[x] <= 1) continue;
       if (g[x] > 0) M[(size_t)r * m + r - st[x]] = -a.c[x];
       if (g[x] < a.n[x] - 1) M[(size_t)r * m + r + st[x]] = -a.c[x];
     }
   }
+  return dense_inverse(m, M, out);
+}
+
+// the inverse of the dense m x m matrix M (overwritten) by Gauss-Jordan elimination with partial pivoting
+int dense_inverse(int m, std::vector<double> &M, std::vector<double> *out) {
+  std::vector<double> I((size_t)m * m, 0.0);
+  for (int r = 0; r < m; ++r) I[(size_t)r * m + r] = 1.0;
   for (int k = 0; k < m; ++k) {
     int p = k;
     for (int r = k + 1; r < m; ++r)
@@ -594,10 +615,11 @@ int read_stencil(const psp_csr *A, const int n[3], MgStencil *S) {
   return PSP_OK;
 }
 
-int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, psp_mg **out) {
+// the argument checks both modes make before the first device call; n = the grid padded with ones
+int mg_check_args(const psp_csr *A, int ndim, const int *grid, double omega, int steps, psp_mg **out, int n[3]) {
   if (!A || !grid || !out) return fail(PSP_EINVAL, "psp_mg_create: NULL argument");
   if (ndim < 1 || ndim > 3) return fail(PSP_EINVAL, "multigrid: grid must have 1 to 3 axes");
-  int n[3] = {1, 1, 1};
+  n[0] = n[1] = n[2] = 1;
   long prod = 1;
   for (int a = 0; a < ndim; ++a) {
     if (grid[a] < 1) return fail(PSP_EINVAL, "multigrid: grid axes must be positive");
@@ -609,7 +631,44 @@ int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, ps
   if (prod != A->nrows) return fail(PSP_EINVAL, "multigrid: prod(grid) = %ld does not match the matrix order %d", prod, A->nrows);
   if (!(omega > 0.0 && omega <= 1.0)) return fail(PSP_EINVAL, "multigrid: omega must satisfy 0 < omega <= 1");
   if (steps < 1) return fail(PSP_EINVAL, "multigrid: steps must be >= 1");
-  PSP_TRY(csr_spmm_check("precon.multigrid", A));
+  return csr_spmm_check("precon.multigrid", A);
+}
+
+// the geometry of the cycle, the same in both modes: the level grids (n, co, nc, rs, N of every level; c, d, w are left
+// 0), the first level of the tail and the launches of one application
+int mg_level_grids(psp_mg *K, const int n[3], int steps) {
+  int cur[3] = {n[0], n[1], n[2]};
+  for (;;) {
+    psp_mg::Level L;
+    memset(&L.a, 0, sizeof L.a);
+    int coarsened = 0;
+    for (int a = 0; a < 3; ++a) {
+      L.a.n[a] = cur[a];
+      L.a.co[a] = cur[a] >= 4;
+      L.a.nc[a] = L.a.co[a] ? cur[a] / 2 : cur[a];
+      coarsened += L.a.co[a];
+    }
+    L.a.rs = 1.0 / (double)(1 << coarsened);
+    L.N = (long)cur[0] * cur[1] * cur[2];
+    K->lev.push_back(L);
+    if (!coarsened) break;
+    for (int a = 0; a < 3; ++a)
+      if (L.a.co[a]) cur[a] /= 2;
+  }
+  const int nl = (int)K->lev.size();
+  K->tail_first = nl - 1;
+  while (K->tail_first > 0 && K->lev[K->tail_first - 1].N <= kTailT) --K->tail_first;
+  // launches of one application: per large level the pre-smoothing (the first two sweeps are one pass), the restriction,
+  // the prolongation and the post-smoothing; one for the tail
+  K->launches = 1;
+  for (int l = 0; l < K->tail_first; ++l) K->launches += (steps >= 2 ? steps - 1 : 1) + 1 + 1 + steps;
+  if (nl - K->tail_first > kTailMaxLev || nl > kMaxLevels) return fail(PSP_EINVAL, "multigrid: too many levels");
+  return PSP_OK;
+}
+
+int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, psp_mg **out) {
+  int n[3];
+  PSP_TRY(mg_check_args(A, ndim, grid, omega, steps, out, n));
   PSP_TRY(ensure_device());
   MgStencil S;
   PSP_TRY(read_stencil(A, n, &S));
@@ -628,44 +687,23 @@ int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, ps
   K->ndim = ndim;
   K->omega = omega;
   K->steps = steps;
-  // the levels
+  // the levels: c_a / 4 on the axes coarsened above, d = 2 sum c + s
+  int rc = mg_level_grids(K, n, steps);
   {
-    int cur[3] = {n[0], n[1], n[2]};
     double c[3] = {S.c[0], S.c[1], S.c[2]};
-    for (;;) {
-      psp_mg::Level L;
-      int coarsened = 0;
+    for (psp_mg::Level &L : K->lev) {
       double sum = 0.0;
       for (int a = 0; a < 3; ++a) {
-        L.a.n[a] = cur[a];
-        L.a.c[a] = cur[a] > 1 ? c[a] : 0.0;
-        L.a.co[a] = cur[a] >= 4;
-        L.a.nc[a] = L.a.co[a] ? cur[a] / 2 : cur[a];
-        coarsened += L.a.co[a];
+        L.a.c[a] = L.a.n[a] > 1 ? c[a] : 0.0;
         sum += L.a.c[a];
       }
       L.a.d = 2.0 * sum + s;
       L.a.w = omega / L.a.d;
-      L.a.rs = 1.0 / (double)(1 << coarsened);
-      L.N = (long)cur[0] * cur[1] * cur[2];
-      K->lev.push_back(L);
-      if (!coarsened) break;
       for (int a = 0; a < 3; ++a)
-        if (L.a.co[a]) {
-          cur[a] /= 2;
-          c[a] /= 4.0;
-        }
+        if (L.a.co[a]) c[a] /= 4.0;
     }
   }
   const int nl = (int)K->lev.size();
-  K->tail_first = nl - 1;
-  while (K->tail_first > 0 && K->lev[K->tail_first - 1].N <= kTailT) --K->tail_first;
-  int rc = PSP_OK;
-  if (nl - K->tail_first > kTailMaxLev || nl > kMaxLevels) rc = fail(PSP_EINVAL, "multigrid: too many levels");
-  // launches of one application: per large level the pre-smoothing (the first two sweeps are one pass), the restriction,
-  // the prolongation and the post-smoothing; one for the tail
-  K->launches = 1;
-  for (int l = 0; l < K->tail_first; ++l) K->launches += (steps >= 2 ? steps - 1 : 1) + 1 + 1 + steps;
   // level vectors: the finest level works in the caller's vectors and one spare; a level that heads the tail needs its
   // b and x in memory (the restriction above it writes b, the prolongation reads x)
   for (int l = 0; l <= K->tail_first && rc == PSP_OK; ++l) {
@@ -711,6 +749,202 @@ int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, ps
   return PSP_OK;
 }
 
+// ------------------------------------------------------------------ galerkin = True: creation
+
+const char *g_why(int bits) {
+  if (bits & kGBadOffset) return "an entry at an offset that is no axis stride of the grid";
+  if (bits & kGBadWrap) return "an entry that wraps across a line end";
+  if (bits & kGBadDup) return "an entry that is stored twice";
+  if (bits & kGBadDiag) return "a diagonal entry that is missing, or not finite and > 0";
+  return "an unsymmetric pair, A[k, k+st] != A[k+st, k]";
+}
+
+GOut g_out(const GLevel &G) {
+  GOut o;
+  o.diag = const_cast<double *>(G.diag);
+  o.w = const_cast<double *>(G.w);
+  for (int k = 0; k < kGMaxOff; ++k) o.lo[k] = const_cast<double *>(G.lo[k]);
+  return o;
+}
+
+int g_bad_shape(const GLevel &G) {
+  return fail(PSP_EINVAL, "multigrid: internal error (a level of %d axes with %d lower arrays)", G.nd, G.noff);
+}
+
+int launch_galerkin(const GLevel &S, long Nc, double omega, const GOut &o, int *flag) {
+  const dim3 g((unsigned)((Nc + 255) / 256)), t(256);
+  switch (S.nd * 16 + S.noff) {
+    case 1 * 16 + 1: hipLaunchKernelGGL((mg_galerkin_kernel<1, 1>), g, t, 0, stream(), S, Nc, omega, o, flag); break;
+    case 2 * 16 + 2: hipLaunchKernelGGL((mg_galerkin_kernel<2, 2>), g, t, 0, stream(), S, Nc, omega, o, flag); break;
+    case 2 * 16 + 4: hipLaunchKernelGGL((mg_galerkin_kernel<2, 4>), g, t, 0, stream(), S, Nc, omega, o, flag); break;
+    case 3 * 16 + 3: hipLaunchKernelGGL((mg_galerkin_kernel<3, 3>), g, t, 0, stream(), S, Nc, omega, o, flag); break;
+    case 3 * 16 + 13: hipLaunchKernelGGL((mg_galerkin_kernel<3, 13>), g, t, 0, stream(), S, Nc, omega, o, flag); break;
+    default: return g_bad_shape(S);
+  }
+  return PSP_OK;
+}
+
+// the dense matrix of a (small) level from its downloaded arrays: blk = diagonal, omega / diagonal, the lower arrays
+void g_dense(const GLevel &G, const std::vector<double> &blk, std::vector<double> *M) {
+  const int n0 = G.a.n[0], n1 = G.a.n[1], n2 = G.a.n[2], m = n0 * n1 * n2;
+  M->assign((size_t)m * m, 0.0);
+  for (int r = 0; r < m; ++r) {
+    const int g[3] = {r % n0, (r / n0) % n1, r / (n0 * n1)};
+    (*M)[(size_t)r * m + r] = blk[r];
+    for (int k = 0; k < G.noff; ++k) {
+      const int d[3] = {g_d(G.nd, G.noff, k, 0), g_d(G.nd, G.noff, k, 1), g_d(G.nd, G.noff, k, 2)};
+      const int h[3] = {g[0] + d[0], g[1] + d[1], g[2] + d[2]};
+      if (h[0] < 0 || h[0] >= n0 || h[1] < 0 || h[1] >= n1 || h[2] < 0 || h[2] >= n2) continue;
+      const int c = h[0] + n0 * (h[1] + n1 * h[2]);
+      const double v = blk[(size_t)(2 + k) * m + r];
+      (*M)[(size_t)r * m + c] = v;
+      (*M)[(size_t)c * m + r] = v;
+    }
+  }
+}
+
+// everything of mg_create_galerkin that can fail after the handle exists (the caller destroys it then)
+int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
+  const double omega = K->omega;
+  const int steps = K->steps;
+  const int nd = n[2] > 1 ? 3 : n[1] > 1 ? 2 : 1;
+  PSP_TRY(mg_level_grids(K, n, steps));  // section 9c's
+  const int nl = (int)K->lev.size();
+  // the level operators' arrays and the level vectors
+  K->glev.resize(nl);
+  K->coef.assign(nl, nullptr);
+  for (int l = 0; l < nl; ++l) {
+    psp_mg::Level &L = K->lev[l];
+    GLevel &G = K->glev[l];
+    memset(&G, 0, sizeof G);
+    G.a = L.a;
+    G.nd = nd;
+    G.noff = l == 0 ? nd : g_full_noff(nd);
+    if (hipMalloc((void **)&K->coef[l], sizeof(double) * (size_t)(2 + G.noff) * (size_t)L.N) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(PSP_ENOMEM, "multigrid: level operator allocation failed");
+    }
+    G.diag = K->coef[l];
+    G.w = K->coef[l] + L.N;
+    for (int k = 0; k < G.noff; ++k) {
+      G.lo[k] = K->coef[l] + (size_t)(2 + k) * (size_t)L.N;
+      for (int a = 0; a < 3; ++a) G.od[k][a] = g_d(nd, G.noff, k, a);
+    }
+    const size_t bytes = sizeof(double) * (size_t)L.N;
+    hipError_t e = hipSuccess;
+    if (l < K->tail_first) e = hipMalloc((void **)&L.t, bytes);
+    if (l > 0 && l <= K->tail_first && e == hipSuccess) e = hipMalloc((void **)&L.x, bytes);
+    if (l > 0 && l <= K->tail_first && e == hipSuccess) e = hipMalloc((void **)&L.b, bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(PSP_ENOMEM, "multigrid: level vector allocation failed");
+    }
+  }
+  // level 0: the checking pass writes it
+  PSP_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), stream()));
+  PSP_HIP(hipMemsetAsync(K->coef[0], 0, sizeof(double) * (size_t)(2 + nd) * (size_t)K->lev[0].N, stream()));
+  hipLaunchKernelGGL(mg_extract_csr_kernel, dim3((A->nrows + 255) / 256), dim3(256), 0, stream(), A->nrows, n[0], n[1], n[2],
+                     omega, (const int *)A->ind, (const int *)A->col, (const double *)A->val, g_out(K->glev[0]), flags);
+  PSP_LAUNCH_CHECK();
+  int bad = 0;
+  PSP_TRY(read_flag(flags, &bad));
+  if (bad)
+    return fail(PSP_EINVAL, "multigrid(galerkin=True): the matrix is not a symmetric 3- / 5- / 7-point stencil on this grid: it has %s",
+                g_why(bad));
+  // A_{l+1} = R_l A_l P_l, level by level
+  for (int l = 0; l + 1 < nl; ++l) {
+    PSP_TRY(launch_galerkin(K->glev[l], K->lev[l + 1].N, omega, g_out(K->glev[l + 1]), flags + 1));
+    PSP_LAUNCH_CHECK();
+  }
+  PSP_TRY(read_flag(flags + 1, &bad));
+  if (bad) return fail(PSP_ESINGULAR, "multigrid(galerkin=True): a level operator's diagonal is not finite and > 0");
+  // the coarsest level: downloaded and inverted on the host
+  const GLevel &C = K->glev[nl - 1];
+  const int m = (int)K->lev[nl - 1].N;
+  std::vector<double> blk((size_t)(2 + C.noff) * m), M, inv;
+  PSP_HIP(hipMemcpyAsync(blk.data(), K->coef[nl - 1], sizeof(double) * blk.size(), hipMemcpyDeviceToHost, stream()));
+  PSP_HIP(hipStreamSynchronize(stream()));
+  g_dense(C, blk, &M);
+  PSP_TRY(dense_inverse(m, M, &inv));
+  GTailArg T;
+  memset(&T, 0, sizeof T);
+  T.nlev = nl - K->tail_first;
+  T.steps = steps;
+  int off = 0;
+  for (int l = K->tail_first; l < nl; ++l) {
+    T.off[l - K->tail_first] = off;
+    T.lev[l - K->tail_first] = K->glev[l];
+    off += (int)K->lev[l].N;
+  }
+  if (off > 2 * kTailT) return fail(PSP_EINVAL, "multigrid: the tail does not fit");
+  if (hipMalloc((void **)&K->minv, sizeof(double) * inv.size()) != hipSuccess ||
+      hipMalloc((void **)&K->gtail, sizeof(GTailArg)) != hipSuccess ||
+      hipMemcpy(K->minv, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(K->gtail, &T, sizeof T, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PSP_ENOMEM, "multigrid: tail table allocation failed");
+  }
+  return PSP_OK;
+}
+
+int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int steps, psp_mg **out) {
+  int n[3];
+  PSP_TRY(mg_check_args(A, ndim, grid, omega, steps, out, n));
+  if (!(A->ind && A->col && A->val) || A->w4_only)
+    return fail(PSP_EINVAL, "multigrid(galerkin=True): the handle no longer holds its index arrays on the device");
+  PSP_TRY(ensure_device());
+  int *flags = nullptr;
+  PSP_HIP(hipMalloc((void **)&flags, 2 * sizeof(int)));
+  psp_mg *K = new psp_mg();
+  K->n = A->nrows;
+  K->ndim = ndim;
+  K->omega = omega;
+  K->steps = steps;
+  K->galerkin = true;
+  const int rc = g_build(K, A, n, flags);
+  (void)hipFree(flags);
+  if (rc != PSP_OK) {
+    psp_mg_destroy(K);
+    return rc;
+  }
+  *out = K;
+  return PSP_OK;
+}
+
+template <bool FROMB>
+int launch_vsmooth(const GLevel &G, long N, const double *xin, const double *b, double *xout) {
+  const dim3 g((unsigned)((N + 255) / 256)), t(256);
+  switch (G.nd * 16 + G.noff) {
+    case 1 * 16 + 1: hipLaunchKernelGGL((mg_vsmooth_kernel<1, 1, FROMB>), g, t, 0, stream(), G, N, xin, b, xout); break;
+    case 2 * 16 + 2: hipLaunchKernelGGL((mg_vsmooth_kernel<2, 2, FROMB>), g, t, 0, stream(), G, N, xin, b, xout); break;
+    case 2 * 16 + 4: hipLaunchKernelGGL((mg_vsmooth_kernel<2, 4, FROMB>), g, t, 0, stream(), G, N, xin, b, xout); break;
+    case 3 * 16 + 3: hipLaunchKernelGGL((mg_vsmooth_kernel<3, 3, FROMB>), g, t, 0, stream(), G, N, xin, b, xout); break;
+    case 3 * 16 + 13: hipLaunchKernelGGL((mg_vsmooth_kernel<3, 13, FROMB>), g, t, 0, stream(), G, N, xin, b, xout); break;
+    default: return g_bad_shape(G);
+  }
+  return PSP_OK;
+}
+
+int launch_vrestrict(const GLevel &G, const double *x, const double *b, double *bc) {
+  int tile[3];
+  mg_tile(G.a, tile);
+  const long g0n = (G.a.nc[0] + tile[0] - 1) / tile[0], g1n = (G.a.nc[1] + tile[1] - 1) / tile[1],
+             g2n = (G.a.nc[2] + tile[2] - 1) / tile[2];
+  const dim3 g((unsigned)(g0n * g1n * g2n)), t(kResThreads);
+#define PSP_VRES(ND, NOFF) \
+  hipLaunchKernelGGL((mg_vrestrict_kernel<ND, NOFF>), g, t, 0, stream(), G, tile[0], tile[1], tile[2], (int)g0n, (int)g1n, x, b, bc)
+  switch (G.nd * 16 + G.noff) {
+    case 1 * 16 + 1: PSP_VRES(1, 1); break;
+    case 2 * 16 + 2: PSP_VRES(2, 2); break;
+    case 2 * 16 + 4: PSP_VRES(2, 4); break;
+    case 3 * 16 + 3: PSP_VRES(3, 3); break;
+    case 3 * 16 + 13: PSP_VRES(3, 13); break;
+    default: return g_bad_shape(G);
+  }
+#undef PSP_VRES
+  return PSP_OK;
+}
+
 template <bool FROMB>
 void launch_smooth(const psp_mg::Level &L, const double *xin, const double *b, double *xout) {
   const dim3 g((unsigned)((L.N + 255) / 256)), t(256);
@@ -721,12 +955,65 @@ void launch_smooth(const psp_mg::Level &L, const double *xin, const double *b, d
   }
 }
 
-}  // namespace
+void launch_restrict(const psp_mg::Level &L, const double *x, const double *b, double *bc) {
+  int tile[3];
+  mg_tile(L.a, tile);
+  // at most ceil(nc0 / t0) ceil(nc1 / t1) ceil(nc2 / t2) <= 2^31 / 256 + a few tiles: fits gridDim.x
+  const long g0n = (L.a.nc[0] + tile[0] - 1) / tile[0], g1n = (L.a.nc[1] + tile[1] - 1) / tile[1],
+             g2n = (L.a.nc[2] + tile[2] - 1) / tile[2];
+  hipLaunchKernelGGL(mg_restrict_kernel, dim3((unsigned)(g0n * g1n * g2n)), dim3(kResThreads), 0, stream(), L.a, tile[0],
+                     tile[1], tile[2], (int)g0n, (int)g1n, x, b, bc);
+}
 
-namespace psp {
+// what the two modes launch for the steps of the schedule below: the first pass from x = 0 (x = w b when steps = 1, else
+// sweeps one and two in one pass over b), a further sweep, b_c = R (b - A x), the tail
+struct MatrixFreeOps {
+  psp_mg *K;
+  int first(int l, const double *b, double *dst) const {
+    const psp_mg::Level &L = K->lev[l];
+    if (K->steps == 1)
+      hipLaunchKernelGGL(mg_scale_kernel, dim3((unsigned)((L.N + 255) / 256)), dim3(256), 0, stream(), L.N, L.a.w, b, dst);
+    else
+      launch_smooth<true>(L, nullptr, b, dst);
+    return PSP_OK;
+  }
+  int sweep(int l, const double *xin, const double *b, double *xout) const {
+    launch_smooth<false>(K->lev[l], xin, b, xout);
+    return PSP_OK;
+  }
+  int restrict_to(int l, const double *x, const double *b, double *bc) const {
+    launch_restrict(K->lev[l], x, b, bc);
+    return PSP_OK;
+  }
+  void tail(const double *b, double *x) const {
+    hipLaunchKernelGGL(mg_tail_kernel, dim3(1), dim3(kTailThreads), 0, stream(), (const MgTailArg *)K->tail,
+                       (const double *)K->minv, b, x);
+  }
+};
 
-// y = V(0, b) on device vectors; y must not alias b.  The handle is locked by the caller.
-int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
+struct GalerkinOps {
+  psp_mg *K;
+  int first(int l, const double *b, double *dst) const {
+    const long N = K->lev[l].N;
+    if (K->steps > 1) return launch_vsmooth<true>(K->glev[l], N, nullptr, b, dst);
+    hipLaunchKernelGGL(mg_vscale_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream(), N, K->glev[l].w, b, dst);
+    return PSP_OK;
+  }
+  int sweep(int l, const double *xin, const double *b, double *xout) const {
+    return launch_vsmooth<false>(K->glev[l], K->lev[l].N, xin, b, xout);
+  }
+  int restrict_to(int l, const double *x, const double *b, double *bc) const {
+    return launch_vrestrict(K->glev[l], x, b, bc);
+  }
+  void tail(const double *b, double *x) const {
+    hipLaunchKernelGGL(mg_gtail_kernel, dim3(1), dim3(kTailThreads), 0, stream(), (const GTailArg *)K->gtail,
+                       (const double *)K->minv, b, x);
+  }
+};
+
+// one V-cycle: the schedule of launches and buffers, the same in both modes
+template <class Ops>
+int mg_schedule(psp_mg *K, const double *b_dev, double *y_dev, const Ops &ops) {
   const int steps = K->steps, tf = K->tail_first;
   // where each large level's iterate is after its pre-smoothing; every sweep writes the buffer the previous one did not
   double *cur[kMaxLevels] = {};
@@ -738,33 +1025,21 @@ int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
     // the finest level's last sweep must land in y: its writes are the pre-smoothing launches and `steps` more
     const int writes = (steps >= 2 ? steps - 1 : 1) + steps;
     double *dst = (l == 0 && (writes & 1) == 0) ? L.t : own;
-    const dim3 g((unsigned)((L.N + 255) / 256)), t(256);
-    if (steps == 1) {
-      hipLaunchKernelGGL(mg_scale_kernel, g, t, 0, stream(), L.N, L.a.w, b, dst);
-    } else {
-      launch_smooth<true>(L, nullptr, b, dst);
-      for (int k = 2; k < steps; ++k) {
-        double *nxt = dst == own ? L.t : own;
-        launch_smooth<false>(L, dst, b, nxt);
-        dst = nxt;
-      }
+    PSP_TRY(ops.first(l, b, dst));
+    for (int k = 2; k < steps; ++k) {
+      double *nxt = dst == own ? L.t : own;
+      PSP_TRY(ops.sweep(l, dst, b, nxt));
+      dst = nxt;
     }
     cur[l] = dst;
-    int tile[3];
-    mg_tile(L.a, tile);
-    // at most ceil(nc0 / t0) ceil(nc1 / t1) ceil(nc2 / t2) <= 2^31 / 256 + a few tiles: fits gridDim.x
-    const long g0n = (L.a.nc[0] + tile[0] - 1) / tile[0], g1n = (L.a.nc[1] + tile[1] - 1) / tile[1],
-               g2n = (L.a.nc[2] + tile[2] - 1) / tile[2];
-    hipLaunchKernelGGL(mg_restrict_kernel, dim3((unsigned)(g0n * g1n * g2n)), dim3(kResThreads), 0, stream(), L.a, tile[0],
-                       tile[1], tile[2], (int)g0n, (int)g1n, (const double *)dst, b, K->lev[l + 1].b);
+    PSP_TRY(ops.restrict_to(l, dst, b, K->lev[l + 1].b));
     PSP_LAUNCH_CHECK();
   }
   // the tail
   {
     const double *b = tf == 0 ? b_dev : K->lev[tf].b;
     double *x = tf == 0 ? y_dev : K->lev[tf].x;
-    hipLaunchKernelGGL(mg_tail_kernel, dim3(1), dim3(kTailThreads), 0, stream(), (const MgTailArg *)K->tail,
-                       (const double *)K->minv, b, x);
+    ops.tail(b, x);
     PSP_LAUNCH_CHECK();
     cur[tf] = x;
   }
@@ -774,11 +1049,11 @@ int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
     const double *b = l == 0 ? b_dev : L.b;
     double *const own = l == 0 ? y_dev : L.x;
     double *x = cur[l];
-    const dim3 g((unsigned)((L.N + 255) / 256)), t(256);
-    hipLaunchKernelGGL(mg_prolong_kernel, g, t, 0, stream(), L.a, L.N, (const double *)cur[l + 1], x);
+    hipLaunchKernelGGL(mg_prolong_kernel, dim3((unsigned)((L.N + 255) / 256)), dim3(256), 0, stream(), L.a, L.N,
+                       (const double *)cur[l + 1], x);
     for (int k = 0; k < steps; ++k) {
       double *nxt = x == own ? L.t : own;
-      launch_smooth<false>(L, x, b, nxt);
+      PSP_TRY(ops.sweep(l, x, b, nxt));
       x = nxt;
     }
     cur[l] = x;
@@ -786,6 +1061,15 @@ int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
   }
   if (tf > 0 && cur[0] != y_dev) return fail(PSP_EINVAL, "multigrid: internal error (the result is not in y)");
   return PSP_OK;
+}
+
+}  // namespace
+
+namespace psp {
+
+// y = V(0, b) on device vectors; y must not alias b.  The handle is locked by the caller.
+int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
+  return K->galerkin ? mg_schedule(K, b_dev, y_dev, GalerkinOps{K}) : mg_schedule(K, b_dev, y_dev, MatrixFreeOps{K});
 }
 
 }  // namespace psp
@@ -806,8 +1090,56 @@ int psp_mg_create_sss(psp_sss_t *A, int ndim, const int *grid, double omega, int
   return mg_create(A->full, ndim, grid, omega, steps, out);
 }
 
+int psp_mg_create_csr_galerkin(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
+  PSP_API_GUARD_H(A);
+  return mg_create_galerkin(A, ndim, grid, omega, steps, out);
+}
+
+int psp_mg_create_sss_galerkin(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
+  PSP_API_GUARD_H(A, A ? A->full : nullptr);
+  if (!A) return fail(PSP_EINVAL, "psp_mg_create_sss_galerkin: NULL argument");
+  if (A->host || cpu_mode())
+    return fail(PSP_ENODEV, "precon.multigrid: not available with PSP_DEVICE=cpu (host mode covers csr / sss / jacobi / pcg / minres)");
+  if (!A->full) return fail(PSP_EINVAL, "psp_mg_create_sss_galerkin: the matrix has no device mirror");
+  return mg_create_galerkin(A->full, ndim, grid, omega, steps, out);
+}
+
+int psp_mg_is_galerkin(const psp_mg_t *K, int *galerkin) {
+  if (!K || !galerkin) return fail(PSP_EINVAL, "psp_mg_is_galerkin: NULL argument");
+  *galerkin = K->galerkin ? 1 : 0;
+  return PSP_OK;
+}
+
+int psp_mg_level_operator(psp_mg_t *K, int level, int *offsets_out, int *noff_inout, double *values_host) {
+  PSP_API_GUARD_H(K);
+  if (!K || !noff_inout) return fail(PSP_EINVAL, "psp_mg_level_operator: NULL argument");
+  if (!K->galerkin) return fail(PSP_EINVAL, "psp_mg_level_operator: the handle stores no level operators (galerkin=False)");
+  if (level < 0 || level >= (int)K->glev.size()) return fail(PSP_EINVAL, "psp_mg_level_operator: no level %d", level);
+  const GLevel &G = K->glev[level];
+  const int cap = *noff_inout, cnt = 1 + G.noff;
+  *noff_inout = cnt;
+  if (!offsets_out && !values_host) return PSP_OK;
+  if (cap < cnt) return fail(PSP_EINVAL, "psp_mg_level_operator: room for %d arrays, the level has %d", cap, cnt);
+  if (offsets_out) {
+    offsets_out[0] = offsets_out[1] = offsets_out[2] = 0;
+    for (int k = 0; k < G.noff; ++k)
+      for (int a = 0; a < 3; ++a) offsets_out[3 * (k + 1) + a] = g_d(G.nd, G.noff, k, a);
+  }
+  if (values_host) {
+    const size_t N = (size_t)K->lev[level].N;
+    PSP_TRY(ensure_device());
+    PSP_HIP(hipMemcpyAsync(values_host, G.diag, sizeof(double) * N, hipMemcpyDeviceToHost, stream()));
+    if (G.noff > 0)  // the lower arrays follow omega / diagonal in the level's allocation
+      PSP_HIP(hipMemcpyAsync(values_host + N, G.lo[0], sizeof(double) * N * (size_t)G.noff, hipMemcpyDeviceToHost, stream()));
+    PSP_HIP(hipStreamSynchronize(stream()));
+  }
+  return PSP_OK;
+}
+
 int psp_mg_destroy(psp_mg_t *K) {
   if (!K) return PSP_OK;
+  for (double *p : K->coef) (void)hipFree(p);
+  (void)hipFree(K->gtail);
   for (psp_mg::Level &L : K->lev)
     for (void *p : {(void *)L.x, (void *)L.b, (void *)L.t}) (void)hipFree(p);
   (void)hipFree(K->minv);

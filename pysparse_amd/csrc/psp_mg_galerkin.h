@@ -1,0 +1,433 @@
+// psp_mg_galerkin.h -- the second mode of precon.multigrid: galerkin=True (DESIGN.md section 9d is the normative text).
+// Part of psp_mg.hip's translation unit (included after the matrix-free kernels, whose transfer operators it reuses).
+//
+// A is any symmetric 3- / 5- / 7-point operator on the grid (varying coefficients); the level operators are
+// A_0 = A, A_{l+1} = R_l A_l P_l with section 9c's P and R, stored as symmetric stencils, offset-major: the diagonal
+// array and one array per LOWER offset o (entry K holds A_l[K, K+o], 0 where that neighbour does not exist); the upper
+// coupling of K is read as the lower one stored at K - o, so what the kernels apply is exactly symmetric.  Level 0
+// carries the ND axis offsets, every other level the (3^ND - 1) / 2 lower members of {-1, 0, 1}^ND.
+//
+// The lower offsets of the full pattern in their fixed order (ascending |o| = |d0 + n0 d1 + n0 n1 d2| on every grid with
+// n0, n1 >= 3): d2 = 0, -1; within it d1 = +1, 0, -1; within it d0 = +1, 0, -1; the lexicographically negative ones.
+namespace {
+
+constexpr int kGMaxOff = 13;
+
+struct GLevel {
+  MgLevelArg a;  // n, co, nc, rs as in the matrix-free mode (c, d, w are not used)
+  int nd;        // axes of the level's index
+  int noff;      // lower arrays: nd on level 0, (3^nd - 1) / 2 below
+  const double *diag, *w;  // A_l[K, K] and omega / A_l[K, K]
+  const double *lo[kGMaxOff];
+  int od[kGMaxOff][3];  // the lower offsets' components, for the tail's run-time loop (g_ax_rt)
+};
+
+struct GOut {
+  double *diag, *w, *lo[kGMaxOff];
+};
+
+struct GTailArg {
+  int nlev;
+  int steps;
+  int off[kTailMaxLev];
+  GLevel lev[kTailMaxLev];
+};
+
+constexpr int g_full_noff(int nd) { return nd == 1 ? 1 : nd == 2 ? 4 : 13; }
+constexpr int g_pow3(int nd) { return nd == 1 ? 3 : nd == 2 ? 9 : 27; }
+
+// component `axis` of the k-th lower offset of the full pattern
+constexpr int g_full_d(int k, int axis) {
+  int idx = 0;
+  for (int m2 = 0; m2 <= 1; ++m2)
+    for (int d1 = 1; d1 >= -1; --d1)
+      for (int d0 = 1; d0 >= -1; --d0) {
+        const int d2 = -m2;
+        const bool lower = d2 < 0 || (d2 == 0 && (d1 < 0 || (d1 == 0 && d0 < 0)));
+        if (!lower) continue;
+        if (idx == k) return axis == 0 ? d0 : axis == 1 ? d1 : d2;
+        ++idx;
+      }
+  return 0;
+}
+
+// component `axis` of the k-th lower offset of a level of nd axes that stores noff arrays
+constexpr int g_d(int nd, int noff, int k, int axis) {
+  if (noff == nd && nd > 1) return axis == k ? -1 : 0;  // the axis offsets of level 0
+  return g_full_d(k, axis);
+}
+
+// which array of such a level holds the lower offset (d0, d1, d2); -1: none (the coupling is structurally 0)
+constexpr int g_slot(int nd, int noff, int d0, int d1, int d2) {
+  for (int k = 0; k < noff; ++k)
+    if (g_d(nd, noff, k, 0) == d0 && g_d(nd, noff, k, 1) == d1 && g_d(nd, noff, k, 2) == d2) return k;
+  return -1;
+}
+
+// f(integral_constant<int, I>) for I = I0 .. N - 1, in this order, unrolled by the compiler's own instantiation: every
+// offset below is a compile-time constant, no array of pointers or sums is ever indexed by a run-time value
+template <int I, int N, class F>
+__device__ __forceinline__ void g_for(F &&f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    g_for<I + 1, N>(f);
+  }
+}
+
+template <int D>
+__device__ __forceinline__ bool g_in(int v, int n) {
+  if constexpr (D == 0)
+    return true;
+  else
+    return (unsigned)(v + D) < (unsigned)n;
+}
+
+// (A_l x)[i]: the diagonal term, then per stored offset in its fixed order the lower and the upper neighbour
+template <int ND, int NOFF, class X>
+__device__ __forceinline__ double g_ax(const GLevel &L, const X &x, long i, int i0, int i1, int i2) {
+  double acc = L.diag[i] * x(i);
+  const int n0 = L.a.n[0], n1 = L.a.n[1], n2 = L.a.n[2];
+  g_for<0, NOFF>([&](auto kc) {
+    constexpr int k = decltype(kc)::value;
+    constexpr int d0 = g_d(ND, NOFF, k, 0), d1 = g_d(ND, NOFF, k, 1), d2 = g_d(ND, NOFF, k, 2);
+    const long o = d0 + (long)n0 * (d1 + (long)n1 * d2);
+    if (g_in<d0>(i0, n0) && g_in<d1>(i1, n1) && g_in<d2>(i2, n2)) acc += L.lo[k][i] * x(i + o);
+    if (g_in<-d0>(i0, n0) && g_in<-d1>(i1, n1) && g_in<-d2>(i2, n2)) acc += L.lo[k][i - o] * x(i - o);
+  });
+  return acc;
+}
+
+// the same sum in the same order for a level whose shape is only known at run time (the tail, where L lives in global
+// memory: the offsets and the array pointers are loads, nothing is indexed in registers)
+template <class X>
+__device__ __forceinline__ double g_ax_rt(const GLevel &L, const X &x, int i, int i0, int i1, int i2) {
+  double acc = L.diag[i] * x(i);
+  const int n0 = L.a.n[0], n1 = L.a.n[1], n2 = L.a.n[2], noff = L.noff;
+  for (int k = 0; k < noff; ++k) {
+    const int d0 = L.od[k][0], d1 = L.od[k][1], d2 = L.od[k][2];
+    const int o = d0 + n0 * (d1 + n1 * d2);
+    const double *__restrict__ lo = L.lo[k];
+    if ((unsigned)(i0 + d0) < (unsigned)n0 && (unsigned)(i1 + d1) < (unsigned)n1 && (unsigned)(i2 + d2) < (unsigned)n2)
+      acc += lo[i] * x(i + o);
+    if ((unsigned)(i0 - d0) < (unsigned)n0 && (unsigned)(i1 - d1) < (unsigned)n1 && (unsigned)(i2 - d2) < (unsigned)n2)
+      acc += lo[i - o] * x(i - o);
+  }
+  return acc;
+}
+
+template <int ND>
+__device__ __forceinline__ void g_split(const MgLevelArg &a, long i, int &i0, int &i1, int &i2) {
+  i0 = (int)i, i1 = 0, i2 = 0;
+  if constexpr (ND == 2) {
+    i0 = (int)(i % a.n[0]);
+    i1 = (int)(i / a.n[0]);
+  } else if constexpr (ND == 3) {
+    mg_split(a, i, i0, i1, i2);
+  }
+}
+
+// ------------------------------------------------------------------ creation: extraction and the Galerkin product
+
+enum {
+  kGBadOffset = 1,   // an entry at an offset that is no axis stride
+  kGBadWrap = 2,     // an entry across a line end
+  kGBadDup = 4,      // an entry stored twice
+  kGBadDiag = 8,     // no diagonal, or one that is not finite and > 0
+  kGBadSym = 16      // A[k, k+st] != A[k+st, k]
+};
+
+// one thread per row: checks every stored entry (section 9d, "accepted operators") and writes level 0's arrays; the
+// lower arrays were zeroed before (a neighbour that is not stored counts as coupling 0)
+__global__ __launch_bounds__(256) void mg_extract_csr_kernel(int n, int n0, int n1, int n2, double omega,
+                                                             const int *__restrict__ ind, const int *__restrict__ col,
+                                                             const double *__restrict__ val, GOut out,
+                                                             int *__restrict__ bad) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const int dim[3] = {n0, n1, n2};
+  const long st[3] = {1, n0, (long)n0 * n1};
+  const int g[3] = {r % n0, (r / n0) % n1, r / n0 / n1};
+  unsigned seen = 0;
+  int why = 0;
+  double dg = 0.0;
+  for (int k = ind[r]; k < ind[r + 1]; ++k) {
+    const long off = (long)col[k] - r;
+    const double v = val[k];
+    if (off == 0) {
+      if (seen & 1u) why |= kGBadDup;
+      seen |= 1u;
+      dg = v;
+      continue;
+    }
+    int ax = -1, ga = 0, da = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+      if (dim[a] > 1 && (off == st[a] || off == -st[a])) ax = a, ga = g[a], da = dim[a];
+    if (ax < 0) {
+      why |= kGBadOffset;
+      continue;
+    }
+    const int up = off > 0;
+    if (up ? ga >= da - 1 : ga <= 0) {
+      why |= kGBadWrap;
+      continue;
+    }
+    const unsigned bit = 1u << (1 + 2 * ax + up);
+    if (seen & bit) why |= kGBadDup;
+    seen |= bit;
+    // the mirrored entry A[c, r], +0.0 where it is not stored, must have the same bits
+    const int c = col[k];
+    double m = 0.0;
+    for (int q = ind[c]; q < ind[c + 1]; ++q)
+      if (col[q] == r) m = val[q];
+    if (__double_as_longlong(m) != __double_as_longlong(v)) why |= kGBadSym;
+    if (!up) {
+      if (ax == 0) out.lo[0][r] = v;
+      if (ax == 1) out.lo[1][r] = v;
+      if (ax == 2) out.lo[2][r] = v;
+    }
+  }
+  if (!(seen & 1u) || !(dg > 0.0) || !(dg <= DBL_MAX)) why |= kGBadDiag;
+  out.diag[r] = dg;
+  out.w[r] = omega / dg;
+  if (why) atomicOr(bad, why);
+}
+
+// One coarse point K of A_c = R A P: its diagonal and its lower entries A_c[K, K + D].  Each is the sum over the fine
+// rows i with P[i, K] != 0 (ascending) and, within i, the fine columns j with A[i, j] stored and P[j, J] != 0 (ascending)
+// of A[i, j] * (P[i, K] P[j, J] / 2^coarsened axes): the factor is an exact power of two.  Along a coarsened axis
+// i = c + e with c = 2K + 1 the centre and e in {-1, 0, 1} (weight 1 at e = 0, else 1/2), j = i + f, and the centre of
+// J = K + D lies at c + 2D: the weight of j is 1 where e + f = 2D, 1/2 where |e + f - 2D| = 1, else 0.  An axis that is
+// not coarsened has P = I: e = 0 and f = D.  e, f and D are compile-time constants, so that the terms that cannot
+// contribute are not compiled at all; SNOFF = the lower arrays of the source level (ND on level 0).
+template <int ND, int SNOFF>
+__global__ __launch_bounds__(256) void mg_galerkin_kernel(GLevel S, long Nc, double omega, GOut out,
+                                                          int *__restrict__ flag) {
+  const long K = (long)blockIdx.x * 256 + threadIdx.x;
+  if (K >= Nc) return;
+  const int n0 = S.a.n[0], n1 = S.a.n[1], n2 = S.a.n[2];
+  const int K0 = (int)(K % S.a.nc[0]), K1 = (int)((K / S.a.nc[0]) % S.a.nc[1]), K2 = (int)(K / S.a.nc[0] / S.a.nc[1]);
+  const bool co0 = S.a.co[0], co1 = S.a.co[1], co2 = S.a.co[2];
+  const int c0 = co0 ? 2 * K0 + 1 : K0, c1 = co1 ? 2 * K1 + 1 : K1, c2 = co2 ? 2 * K2 + 1 : K2;
+  const long cl = c0 + (long)n0 * (c1 + (long)n1 * c2);
+  const double rs = S.a.rs;
+  constexpr int DN = g_full_noff(ND), P3 = g_pow3(ND);
+  g_for<0, DN + 1>([&](auto dc) {
+    constexpr int dk = decltype(dc)::value;  // 0: the diagonal; k + 1: the k-th lower offset
+    constexpr int D0 = dk ? g_full_d(dk - 1, 0) : 0, D1 = dk ? g_full_d(dk - 1, 1) : 0, D2 = dk ? g_full_d(dk - 1, 2) : 0;
+    double acc = 0.0;
+    if (g_in<D0>(K0, S.a.nc[0]) && g_in<D1>(K1, S.a.nc[1]) && g_in<D2>(K2, S.a.nc[2])) {
+      g_for<0, P3>([&](auto ec) {
+        constexpr int ee = decltype(ec)::value;
+        constexpr int e0 = ee % 3 - 1, e1 = ND > 1 ? (ee / 3) % 3 - 1 : 0, e2 = ND > 2 ? ee / 9 - 1 : 0;
+        g_for<0, P3>([&](auto fc) {
+          constexpr int ff = decltype(fc)::value;
+          constexpr int f0 = ff % 3 - 1, f1 = ND > 1 ? (ff / 3) % 3 - 1 : 0, f2 = ND > 2 ? ff / 9 - 1 : 0;
+          // per axis: can the term contribute when the axis is coarsened (pc) / when it is not (pn)
+          constexpr int t0 = e0 + f0 - 2 * D0, t1 = e1 + f1 - 2 * D1, t2 = e2 + f2 - 2 * D2;
+          constexpr bool pc0 = t0 >= -1 && t0 <= 1, pc1 = t1 >= -1 && t1 <= 1, pc2 = t2 >= -1 && t2 <= 1;
+          constexpr bool pn0 = e0 == 0 && f0 == D0, pn1 = e1 == 0 && f1 == D1, pn2 = e2 == 0 && f2 == D2;
+          // where A[i, j] is stored: the diagonal, a lower array at i, or (an upper offset) the mirrored lower array at j
+          constexpr bool isdiag = f0 == 0 && f1 == 0 && f2 == 0;
+          constexpr bool islower = f2 < 0 || (f2 == 0 && (f1 < 0 || (f1 == 0 && f0 < 0)));
+          constexpr int slot = isdiag ? 0 : islower ? g_slot(ND, SNOFF, f0, f1, f2) : g_slot(ND, SNOFF, -f0, -f1, -f2);
+          if constexpr ((pc0 || pn0) && (pc1 || pn1) && (pc2 || pn2) && slot >= 0) {
+            const bool ok = (co0 ? pc0 : pn0) && (co1 ? pc1 : pn1) && (co2 ? pc2 : pn2);
+            const int i0 = c0 + e0, i1 = c1 + e1, i2 = c2 + e2;
+            if (ok && i0 < n0 && i1 < n1 && i2 < n2 && g_in<f0>(i0, n0) && g_in<f1>(i1, n1) && g_in<f2>(i2, n2)) {
+              const double w0 = co0 ? (e0 == 0 ? 1.0 : 0.5) * (t0 == 0 ? 1.0 : 0.5) : 1.0;
+              const double w1 = co1 ? (e1 == 0 ? 1.0 : 0.5) * (t1 == 0 ? 1.0 : 0.5) : 1.0;
+              const double w2 = co2 ? (e2 == 0 ? 1.0 : 0.5) * (t2 == 0 ? 1.0 : 0.5) : 1.0;
+              const long il = cl + e0 + (long)n0 * (e1 + (long)n1 * e2);
+              const long jl = il + f0 + (long)n0 * (f1 + (long)n1 * f2);
+              double a;
+              if constexpr (isdiag)
+                a = S.diag[il];
+              else if constexpr (islower)
+                a = S.lo[slot][il];
+              else
+                a = S.lo[slot][jl];
+              acc += a * (w0 * w1 * w2 * rs);
+            }
+          }
+        });
+      });
+    }
+    if constexpr (dk == 0) {
+      out.diag[K] = acc;
+      out.w[K] = omega / acc;
+      if (!(acc > 0.0) || !(acc <= DBL_MAX)) *flag = 1;
+    } else {
+      out.lo[dk - 1][K] = acc;
+    }
+  });
+}
+
+// ------------------------------------------------------------------ the launch-per-step kernels of the large levels
+
+// the first sweep from x = 0: x = w o b
+__global__ __launch_bounds__(256) void mg_vscale_kernel(long N, const double *__restrict__ w, const double *__restrict__ b,
+                                                        double *__restrict__ x) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < N) x[i] = w[i] * b[i];
+}
+
+// one sweep, out of place, with the stored stencil: xout = xin + w o (b - A_l xin).  Reads xin, b, w and every
+// coefficient array once, writes xout once; the neighbours' rows of the lower arrays (the upper couplings) and of xin are
+// cache hits.  FROMB as in mg_smooth_kernel: xin = w o b formed on the fly.
+template <int ND, int NOFF, bool FROMB>
+__global__ __launch_bounds__(256) void mg_vsmooth_kernel(GLevel L, long N, const double *__restrict__ xin,
+                                                         const double *__restrict__ b, double *__restrict__ xout) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  int i0, i1, i2;
+  g_split<ND>(L.a, i, i0, i1, i2);
+  const double *__restrict__ w = L.w;
+  auto X = [&](long k) { return FROMB ? w[k] * b[k] : xin[k]; };
+  const double ax = g_ax<ND, NOFF>(L, X, i, i0, i1, i2);
+  xout[i] = X(i) + w[i] * (b[i] - ax);
+}
+
+// b_c = R (b - A_l x): mg_restrict_kernel's tile in LDS with the stored stencil; the fine residual never reaches memory
+template <int ND, int NOFF>
+__global__ __launch_bounds__(kResThreads) void mg_vrestrict_kernel(GLevel L, int t0, int t1, int t2, int g0n, int g1n,
+                                                                   const double *__restrict__ x,
+                                                                   const double *__restrict__ b,
+                                                                   double *__restrict__ bc) {
+  __shared__ double r[kResLds];
+  const MgLevelArg &a = L.a;
+  const unsigned bq = blockIdx.x / (unsigned)g0n;
+  const int J0 = (int)(blockIdx.x % (unsigned)g0n) * t0, J1 = (int)(bq % (unsigned)g1n) * t1, J2 = (int)(bq / (unsigned)g1n) * t2;
+  const int f0 = a.co[0] ? 2 * J0 : J0, F0 = a.co[0] ? 2 * t0 + 1 : t0;
+  const int f1 = a.co[1] ? 2 * J1 : J1, F1 = a.co[1] ? 2 * t1 + 1 : t1;
+  const int f2 = a.co[2] ? 2 * J2 : J2, F2 = a.co[2] ? 2 * t2 + 1 : t2;
+  const int total = F0 * F1 * F2;  // <= kResLds (mg_tile)
+  auto X = [&](long k) { return x[k]; };
+  for (int t = threadIdx.x; t < total; t += kResThreads) {
+    const int l0 = t % F0, q = t / F0, l1 = q % F1, l2 = q / F1;
+    const int g0 = f0 + l0, g1 = f1 + l1, g2 = f2 + l2;
+    double v = 0.0;
+    if (g0 < a.n[0] && g1 < a.n[1] && g2 < a.n[2]) {
+      const long i = g0 + (long)a.n[0] * (g1 + (long)a.n[1] * g2);
+      v = b[i] - g_ax<ND, NOFF>(L, X, i, g0, g1, g2);
+    }
+    r[t] = v;
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < t0 * t1 * t2) {
+    const int j0 = t % t0, q = t / t0, j1 = q % t1, j2 = q / t1;
+    if (J0 + j0 < a.nc[0] && J1 + j1 < a.nc[1] && J2 + j2 < a.nc[2]) {
+      auto at = [&](int a0, int a1, int a2) { return r[a0 + F0 * (a1 + F1 * a2)]; };
+      const double v = mg_restrict_point(a, at, j0, j1, j2);
+      bc[(J0 + j0) + (long)a.nc[0] * ((J1 + j1) + (long)a.nc[1] * (J2 + j2))] = v;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ the tail: one workgroup, vectors in LDS, the
+// coefficient arrays from global memory (14 kTailT doubles for the top tail level alone do not fit LDS)
+
+__device__ __forceinline__ void gtail_sweep(const GLevel &L, int N, double *xs, const double *bs) {
+  auto X = [&](long k) { return xs[k]; };
+  double xn[kTailPts];
+#pragma unroll
+  for (int p = 0; p < kTailPts; ++p) {
+    const int i = threadIdx.x + p * kTailThreads;
+    xn[p] = 0.0;
+    if (i < N) {
+      int i0, i1, i2;
+      mg_split(L.a, i, i0, i1, i2);
+      xn[p] = xs[i] + L.w[i] * (bs[i] - g_ax_rt(L, X, i, i0, i1, i2));
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < kTailPts; ++p) {
+    const int i = threadIdx.x + p * kTailThreads;
+    if (i < N) xs[i] = xn[p];
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kTailThreads) void mg_gtail_kernel(const GTailArg *__restrict__ T,
+                                                                const double *__restrict__ minv,
+                                                                const double *__restrict__ bin,
+                                                                double *__restrict__ xout) {
+  __shared__ double sh[kTailLds];
+  double *const scr = sh + 4 * kTailT;
+  double *const mi = sh + 5 * kTailT;
+  const int nl = T->nlev, steps = T->steps, tid = threadIdx.x;
+  {
+    const MgLevelArg &L = T->lev[0].a;
+    const int N = L.n[0] * L.n[1] * L.n[2];
+    double *bs = sh + 2 * kTailT + T->off[0];
+    for (int i = tid; i < N; i += kTailThreads) bs[i] = bin[i];
+    const MgLevelArg &C = T->lev[nl - 1].a;
+    const int nc = C.n[0] * C.n[1] * C.n[2];
+    for (int i = tid; i < nc * nc; i += kTailThreads) mi[i] = minv[i];
+  }
+  __syncthreads();
+  // down
+  for (int l = 0; l < nl - 1; ++l) {
+    const GLevel &G = T->lev[l];
+    const MgLevelArg L = G.a;
+    const int N = L.n[0] * L.n[1] * L.n[2], Nc = L.nc[0] * L.nc[1] * L.nc[2];
+    double *xs = sh + T->off[l], *bs = sh + 2 * kTailT + T->off[l], *bn = sh + 2 * kTailT + T->off[l + 1];
+    for (int i = tid; i < N; i += kTailThreads) xs[i] = G.w[i] * bs[i];
+    __syncthreads();
+    for (int k = 1; k < steps; ++k) gtail_sweep(G, N, xs, bs);
+    auto X = [&](long k) { return xs[k]; };
+    for (int i = tid; i < N; i += kTailThreads) {
+      int i0, i1, i2;
+      mg_split(L, i, i0, i1, i2);
+      scr[i] = bs[i] - g_ax_rt(G, X, i, i0, i1, i2);
+    }
+    __syncthreads();
+    auto at = [&](int a0, int a1, int a2) {
+      return (a0 < L.n[0] && a1 < L.n[1] && a2 < L.n[2]) ? scr[a0 + L.n[0] * (a1 + L.n[1] * a2)] : 0.0;
+    };
+    for (int j = tid; j < Nc; j += kTailThreads) {
+      const int j0 = j % L.nc[0], q = j / L.nc[0], j1 = q % L.nc[1], j2 = q / L.nc[1];
+      bn[j] = mg_restrict_point(L, at, j0, j1, j2);
+    }
+    __syncthreads();
+  }
+  // the coarsest level: x = A^-1 b with the inverse formed at creation
+  {
+    const MgLevelArg &C = T->lev[nl - 1].a;
+    const int nc = C.n[0] * C.n[1] * C.n[2];
+    double *xs = sh + T->off[nl - 1];
+    const double *bs = sh + 2 * kTailT + T->off[nl - 1];
+    if (tid < nc) {
+      double s = 0.0;
+      for (int j = 0; j < nc; ++j) s += mi[tid * nc + j] * bs[j];
+      xs[tid] = s;
+    }
+    __syncthreads();
+  }
+  // up
+  for (int l = nl - 2; l >= 0; --l) {
+    const GLevel &G = T->lev[l];
+    const MgLevelArg L = G.a;
+    const int N = L.n[0] * L.n[1] * L.n[2];
+    double *xs = sh + T->off[l];
+    const double *bs = sh + 2 * kTailT + T->off[l], *en = sh + T->off[l + 1];
+    auto E = [&](long k) { return en[k]; };
+    for (int i = tid; i < N; i += kTailThreads) {
+      int i0, i1, i2;
+      mg_split(L, i, i0, i1, i2);
+      xs[i] = xs[i] + mg_prolong_point(L, E, i0, i1, i2);
+    }
+    __syncthreads();
+    for (int k = 0; k < steps; ++k) gtail_sweep(G, N, xs, bs);
+  }
+  {
+    const MgLevelArg &L = T->lev[0].a;
+    const int N = L.n[0] * L.n[1] * L.n[2];
+    const double *xs = sh + T->off[0];
+    for (int i = tid; i < N; i += kTailThreads) xout[i] = xs[i];
+  }
+}
+
+}  // namespace

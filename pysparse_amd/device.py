@@ -554,10 +554,14 @@ def _check_einval(rc):
 
 
 class DeviceMultigrid:
-    """precon.multigrid(A, grid, omega=0.8, steps=2): a matrix-free geometric V-cycle for the constant-coefficient grid
-    operators A = sum_a c_a T_a + s I (psp_mg.hip; no reference analogue).  `levels` are the level grids, finest first."""
+    """precon.multigrid(A, grid, omega=0.8, steps=2, galerkin=False): a matrix-free geometric V-cycle for the
+    constant-coefficient grid operators A = sum_a c_a T_a + s I (psp_mg.hip; no reference analogue).  `levels` are the
+    level grids, finest first.  galerkin=True: the same cycle for any symmetric 3- / 5- / 7-point operator on the grid
+    (varying coefficients) with stored level operators A_{l+1} = R A_l P."""
 
-    def __init__(self, A, grid, omega=0.8, steps=2):
+    def __init__(self, A, grid, omega=0.8, steps=2, galerkin=False):
+        if not isinstance(galerkin, bool):
+            raise TypeError("galerkin must be a bool")
         if not isinstance(A, (DeviceCSR, DeviceSSS)):
             raise TypeError("multigrid() argument 1 must be a csr_mat or sss_mat handle")
         if isinstance(grid, (str, bytes)) or not hasattr(grid, "__len__") or not hasattr(grid, "__getitem__"):
@@ -585,7 +589,10 @@ class DeviceMultigrid:
             raise ValueError("steps must be >= 1")
         h = C.c_void_p()
         g = (C.c_int * len(dims))(*dims)
-        create = lib().psp_mg_create_csr if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss
+        if galerkin:
+            create = lib().psp_mg_create_csr_galerkin if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss_galerkin
+        else:
+            create = lib().psp_mg_create_csr if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss
         _check_einval(create(A._h, len(dims), g, omega, steps, C.byref(h)))
         self._A = A
         self._h = h
@@ -595,13 +602,25 @@ class DeviceMultigrid:
 
     def info(self):
         """levels, first level of the single-workgroup tail launch, kernel launches per application, level dimensions
-        (three per level, 1 on absent axes)"""
-        nl, tf, la = C.c_int(), C.c_int(), C.c_int()
+        (three per level, 1 on absent axes), and whether the handle stores Galerkin level operators"""
+        nl, tf, la, gk = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(lib().psp_mg_is_galerkin(self._h, C.byref(gk)))
         check(lib().psp_mg_info(self._h, C.byref(nl), C.byref(tf), C.byref(la), None))
         d = (C.c_int * (3 * nl.value))()
         check(lib().psp_mg_info(self._h, None, None, None, d))
         return {"levels": nl.value, "tail_first_level": tf.value, "launches_per_apply": la.value,
-                "dims": tuple(tuple(d[3 * l:3 * l + 3]) for l in range(nl.value))}
+                "dims": tuple(tuple(d[3 * l:3 * l + 3]) for l in range(nl.value)), "galerkin": bool(gk.value)}
+
+    def level_operator(self, level):
+        """test hook (galerkin=True): ((d0, d1, d2) per stored array, values[array, point]) of a level's symmetric stencil,
+        the diagonal first; array o holds A_l[K, K+o] at point K, 0 where that neighbour does not exist"""
+        cnt = C.c_int(0)
+        _check_einval(lib().psp_mg_level_operator(self._h, int(level), None, C.byref(cnt), None))
+        offs = (C.c_int * (3 * cnt.value))()
+        npts = int(np.prod(self.info()["dims"][level]))
+        vals = np.empty((cnt.value, npts))
+        check(lib().psp_mg_level_operator(self._h, int(level), offs, C.byref(cnt), _ptr(vals)))
+        return tuple(tuple(offs[3 * k:3 * k + 3]) for k in range(cnt.value)), vals
 
     def precon(self, x, y):
         n = self.shape[0]

@@ -250,7 +250,8 @@ static PyGetSetDef SSOR_getset[] = {{"shape", (getter)SSOR_get_shape, NULL, "(n,
 
 /* ------------------------------------------------------------------------- multigrid */
 
-/* multigrid(A, grid, omega=0.8, steps=2): geometric V-cycle for the constant-coefficient grid operators (psp_mg.hip);
+/* multigrid(A, grid, omega=0.8, steps=2, galerkin=False): geometric V-cycle for the constant-coefficient grid operators
+ * and, with the keyword galerkin=True (a real bool), for any symmetric 3- / 5- / 7-point operator on the grid (psp_mg.hip);
  * no reference analogue */
 #define MG_MAX_LEVELS 40
 
@@ -266,14 +267,20 @@ typedef struct {
 static PyTypeObject MGType;
 
 static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
-  static char *kwlist[] = {"A", "grid", "omega", "steps", NULL};
-  PyObject *matrix, *grid, *seq, *cap;
+  static char *kwlist[] = {"A", "grid", "omega", "steps", "galerkin", NULL};
+  PyObject *matrix, *grid, *seq, *cap, *galerkin_obj = Py_False;
+  int galerkin;
   double omega = 0.8;
   int steps = 2, ndim, a, rc, shape[2], dims[3] = {1, 1, 1};
   int is_csr, is_sss, is_ll;
   long long prod = 1;
   MGObject *op;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|di", kwlist, &matrix, &grid, &omega, &steps)) return NULL;
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|di$O", kwlist, &matrix, &grid, &omega, &steps, &galerkin_obj)) return NULL;
+  if (!PyBool_Check(galerkin_obj)) {
+    PyErr_SetString(PyExc_TypeError, "multigrid() argument 'galerkin' must be a bool");
+    return NULL;
+  }
+  galerkin = galerkin_obj == Py_True;
   is_csr = PyObject_TypeCheck(matrix, &CSRMatType);
   is_sss = PyObject_TypeCheck(matrix, &SSSMatType);
   is_ll = PyObject_TypeCheck(matrix, &LLMatType);
@@ -343,7 +350,12 @@ static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
   op->dev = NULL;
   op->op = NULL;
   Py_BEGIN_ALLOW_THREADS
-  if (is_sss)
+  if (is_sss && galerkin)
+    rc = psp_mg_create_sss_galerkin(((SSSMatObject *)matrix)->dev, ndim, dims, omega, steps, &op->dev);
+  else if (galerkin)
+    rc = psp_mg_create_csr_galerkin(is_csr ? ((CSRMatObject *)matrix)->dev : ((LLMatObject *)matrix)->mirror, ndim, dims,
+                                    omega, steps, &op->dev);
+  else if (is_sss)
     rc = psp_mg_create_sss(((SSSMatObject *)matrix)->dev, ndim, dims, omega, steps, &op->dev);
   else
     rc = psp_mg_create_csr(is_csr ? ((CSRMatObject *)matrix)->dev : ((LLMatObject *)matrix)->mirror, ndim, dims, omega,
@@ -413,6 +425,12 @@ static PyObject *MG_get_levels(MGObject *self, void *c) {
   return out;
 }
 
+static PyObject *MG_get_galerkin(MGObject *self, void *c) {
+  int g = 0, rc = psp_mg_is_galerkin(self->dev, &g);
+  if (rc != PSP_OK) return raise_psp(rc);
+  return PyBool_FromLong(g);
+}
+
 static PyMethodDef MG_methods[] = {
     {"precon", (PyCFunction)MG_precon, METH_VARARGS,
      "self.precon(x, y)\n\napply preconditioner self on x, store result in y. x is unchanged."},
@@ -420,6 +438,7 @@ static PyMethodDef MG_methods[] = {
 
 static PyGetSetDef MG_getset[] = {{"shape", (getter)MG_get_shape, NULL, "(n, n)", NULL},
                                   {"levels", (getter)MG_get_levels, NULL, "the level grids, finest first", NULL},
+                                  {"galerkin", (getter)MG_get_galerkin, NULL, "stored Galerkin level operators", NULL},
                                   {"_psp_op", (getter)MG_get_psp_op, NULL, "device operator", NULL},
                                   {NULL, NULL, NULL, NULL, NULL}};
 
@@ -433,12 +452,14 @@ static PyMethodDef precon_methods[] = {
      "omega  relaxation parameter (default value: 1.0)\n"
      "steps  number of SSOR steps"},
     {"multigrid", (PyCFunction)multigrid_prec, METH_VARARGS | METH_KEYWORDS,
-     "multigrid(A, grid, omega=0.8, steps=2) -- return geometric multigrid preconditioner object\n\n"
+     "multigrid(A, grid, omega=0.8, steps=2, galerkin=False) -- return geometric multigrid preconditioner object\n\n"
      "One V-cycle with damped-Jacobi smoothing for A = sum_a c_a T_a + s I on a grid (no reference analogue).\n\n"
      "A      'csr_mat', 'sss_mat' or 'll_mat': the constant-coefficient [-1 2 -1] stencil on the grid\n"
      "grid   (n0[, n1[, n2]]), prod(grid) == n, row k = i0 + n0*i1 + n0*n1*i2\n"
      "omega  damping of the Jacobi sweeps, 0 < omega <= 1 (default value: 0.8)\n"
-     "steps  sweeps before and after the coarse-grid correction (default value: 2)"},
+     "steps  sweeps before and after the coarse-grid correction (default value: 2)\n"
+     "galerkin  keyword, a bool: True takes any symmetric 3- / 5- / 7-point operator on the grid (varying\n"
+     "       coefficients) and stores the level operators R A P (default value: False)"},
     {NULL, NULL, 0, NULL}};
 
 static struct PyModuleDef precon_module = {PyModuleDef_HEAD_INIT, "precon",
