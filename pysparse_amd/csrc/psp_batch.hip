@@ -19,6 +19,12 @@
 // what the single solve of such a system computes; p.q is then a batched dot of its own behind the block product (six
 // launches per iteration).  The brick loop of psp_mid.hip (3-D grids of middle size) deals its points out in bricks and
 // agrees with every other loop to rounding only; so does a column of this loop beside it.
+// Which loop the single solve is, by size (tests/test_gpu_block_sizes.py asserts each name): pcg_coop or, from 2^15 rows of
+// an offset-structured system, pcg_mid / pcg_brick; where none of them applies -- varying coefficients beyond 2^20 rows,
+// another kernel family, a handle without CSR arrays (psp_csr_poisson_big, psp_csr_release_arrays) at any size, or
+// psp_set_single_kernel_loops(0) -- the lazy launch-per-phase loop pcg_lazy, and pcg_lazy_pf (p and x updates folded into
+// the product) from 2^21 rows.  Those two put off the x update by one phase and, beyond 4096 partial sums, fold them in two
+// launches; the operands and the order of every sum are the eager loop's, so this loop's columns carry their bits as well.
 //
 // Freezing: a column whose exit is decided (info 0, -2, -5, -6, or -1 with iter = maxit + 1) sets its flag on the device;
 // every kernel skips flagged columns, so nothing of a frozen column is written again.  The loop ends when all are frozen.

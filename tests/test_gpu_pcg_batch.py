@@ -47,24 +47,27 @@ def csr_arrays(M):
 
 
 class System:
-    """a handle, its B / X0 blocks (n x KMAX) and the single solves, each computed once"""
+    """a handle, its B / X0 blocks (n x ncols) and the single solves, each computed once"""
 
-    def __init__(self, A, n, smooth=None, seed=0):
+    def __init__(self, A, n, smooth=None, seed=0, ncols=KMAX):
         self.A, self.n = A, n
         rng = np.random.default_rng(seed)
-        B = rng.standard_normal((n, KMAX))
-        X0 = np.zeros((n, KMAX))
+        B = rng.standard_normal((n, ncols))
+        X0 = np.zeros((n, ncols))
         y = np.empty(n)
         A.matvec(np.ones(n), y)
         B[:, 0] = y
-        B[:, 2] = 0.0
-        X0[:, 2] = rng.standard_normal(n)  # must come back as zeros
-        X0[:, 3] = rng.standard_normal(n)
-        A.matvec(np.ascontiguousarray(X0[:, 3]), y)
-        B[:, 3] = y
-        if smooth is not None:
+        if ncols > 2:
+            B[:, 2] = 0.0
+            X0[:, 2] = rng.standard_normal(n)  # must come back as zeros
+        if ncols > 3:
+            X0[:, 3] = rng.standard_normal(n)
+            A.matvec(np.ascontiguousarray(X0[:, 3]), y)
+            B[:, 3] = y
+        if smooth is not None and ncols > 4:
             B[:, 4] = smooth
-        X0[:, 6] = rng.standard_normal(n)  # a nonzero initial guess
+        if ncols > 6:
+            X0[:, 6] = rng.standard_normal(n)  # a nonzero initial guess
         self.B, self.X0 = B, X0
         self.single = {}
 
