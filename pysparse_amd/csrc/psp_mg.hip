@@ -19,8 +19,10 @@
 // it, down and up, dense solve included, in ONE launch of one workgroup with the vectors in LDS).
 //
 // galerkin = True (psp_mg_create_*_galerkin) is the same cycle for any symmetric 3- / 5- / 7-point
-// operator on the grid, with stored level operators A_{l+1} = R A_l P: its kernels are in psp_mg_galerkin.h, which this file
-// includes; its creation and its schedule are below, next to the matrix-free ones.
+// operator on the grid, with stored level operators A_{l+1} = R A_l P.  The cycle kernels exist once: each is written
+// against a level-operator policy Op that supplies the level's geometry, (A_l x)[i], omega / diagonal and the index
+// split -- MfOp here (c_a and d are kernel arguments), GOp / GTailOp in psp_mg_galerkin.h (stored arrays), which this
+// file includes and which holds what only the stored mode has; its creation is below, next to the matrix-free one.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -57,11 +59,12 @@ struct MgLevelArg {
   double rs;    // 1 / 2^(coarsened axes)
 };
 
-struct MgTailArg {
+template <class LevelT>  // what the mode keeps of a level: MgLevelArg, or psp_mg_galerkin.h's GLevel
+struct TailArg {
   int nlev;
   int steps;
   int off[kTailMaxLev];  // offset of the level's x (and, kTailT * 2 further, b) in the tail's LDS
-  MgLevelArg lev[kTailMaxLev];
+  LevelT lev[kTailMaxLev];
 };
 
 // (A_l x)[i]: the diagonal first, then axis by axis the lower and the upper neighbour -- one fixed order everywhere
@@ -85,12 +88,46 @@ __device__ __forceinline__ double mg_ax(const MgLevelArg &L, const X &x, long i,
   return acc;
 }
 
+// ND: axes the level's index is split into
+template <int ND = 3>
 __device__ __forceinline__ void mg_split(const MgLevelArg &L, long i, int &i0, int &i1, int &i2) {
-  i0 = (int)(i % L.n[0]);
-  const long q = i / L.n[0];
-  i1 = (int)(q % L.n[1]);
-  i2 = (int)(q / L.n[1]);
+  i0 = (int)i, i1 = 0, i2 = 0;
+  if constexpr (ND == 2) {
+    i0 = (int)(i % L.n[0]);
+    i1 = (int)(i / L.n[0]);
+  } else if constexpr (ND == 3) {
+    i0 = (int)(i % L.n[0]);
+    const long q = i / L.n[0];
+    i1 = (int)(q % L.n[1]);
+    i2 = (int)(q / L.n[1]);
+  }
 }
+
+// The level-operator policy of the matrix-free mode: the level is its MgLevelArg, held by value (a kernel argument, or
+// the tail's copy of its table entry in registers).  With ND < 3 the dead axes are set to length 1 so that their terms
+// of mg_ax compile away; MfOp<3> takes any level as it is (the restriction and the tail, whose shapes are run-time).
+template <int ND>
+struct MfOp {
+  using Level = MgLevelArg;
+  MgLevelArg L;
+  __device__ __forceinline__ explicit MfOp(const MgLevelArg &a) : L(a) {
+    if constexpr (ND < 3) L.n[2] = 1;
+    if constexpr (ND < 2) L.n[1] = 1;
+  }
+  __device__ __forceinline__ const MgLevelArg &geo() const { return L; }
+  template <class X>
+  __device__ __forceinline__ double ax(const X &x, long i, int i0, int i1, int i2) const {
+    return mg_ax(L, x, i, i0, i1, i2);
+  }
+  __device__ __forceinline__ double w(long) const { return L.w; }
+  __device__ __forceinline__ void split(long i, int &i0, int &i1, int &i2) const { mg_split<ND>(L, i, i0, i1, i2); }
+};
+// omega / d as mg_scale_kernel takes it
+struct MfW {
+  double w;
+  __device__ __forceinline__ double operator()(long) const { return w; }
+};
+__host__ __device__ inline const MgLevelArg &level_geo(const MgLevelArg &a) { return a; }
 
 // (R r)[j] for the coarse point (j0, j1, j2); r is indexed through `at(l0, l1, l2)` with fine coordinates, which returns 0
 // outside the grid.  Weights 1/2, 1, 1/2 along a coarsened axis at fine 2j, 2j+1, 2j+2; axis 2 outermost, ascending.
@@ -159,43 +196,40 @@ __device__ __forceinline__ double mg_prolong_point(const MgLevelArg &L, const E 
 
 // ------------------------------------------------------------------ the launch-per-step kernels of the large levels
 
-// the first sweep from x = 0: x = 0 + (omega / d)(b - 0) = (omega / d) b
-__global__ __launch_bounds__(256) void mg_scale_kernel(long N, double w, const double *__restrict__ b,
-                                                       double *__restrict__ x) {
+// the first sweep from x = 0: x = 0 + (omega / d)(b - 0) = (omega / d) b; W: MfW (a scalar) or GW (an array)
+template <class W>
+__global__ __launch_bounds__(256) void mg_scale_kernel(long N, W w, const double *__restrict__ b, double *__restrict__ x) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < N) x[i] = w * b[i];
+  if (i < N) x[i] = w(i) * b[i];
 }
 
-// one sweep, out of place: xout = xin + (omega / d)(b - A xin); reads xin and b once, writes xout once (the neighbours
-// come from the caches).  FROMB: xin is the first sweep's (omega / d) b, formed on the fly -- sweeps one and two of a
-// cycle in one pass.  ND: axes the level's index is split into.
-template <int ND, bool FROMB>
-__global__ __launch_bounds__(256) void mg_smooth_kernel(MgLevelArg L, long N, const double *__restrict__ xin,
+// one sweep, out of place: xout = xin + (omega / d)(b - A xin); reads xin and b (and, with a stored stencil, w and every
+// coefficient array) once, writes xout once; the neighbours (of xin, and the neighbours' rows of the lower arrays: the
+// upper couplings) come from the caches.  FROMB: xin is the first sweep's (omega / d) b, formed on the fly -- sweeps one
+// and two of a cycle in one pass.
+template <class Op, bool FROMB>
+__global__ __launch_bounds__(256) void mg_smooth_kernel(typename Op::Level A, long N, const double *__restrict__ xin,
                                                         const double *__restrict__ b, double *__restrict__ xout) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
-  int i0 = (int)i, i1 = 0, i2 = 0;
-  if constexpr (ND == 2) {
-    i0 = (int)(i % L.n[0]);
-    i1 = (int)(i / L.n[0]);
-  } else if constexpr (ND == 3) {
-    mg_split(L, i, i0, i1, i2);
-  }
-  if constexpr (ND < 3) L.n[2] = 1;
-  if constexpr (ND < 2) L.n[1] = 1;
-  const double w = L.w;
-  auto X = [&](long k) { return FROMB ? w * b[k] : xin[k]; };
-  const double ax = mg_ax(L, X, i, i0, i1, i2);
-  xout[i] = X(i) + w * (b[i] - ax);
+  const Op op(A);
+  int i0, i1, i2;
+  op.split(i, i0, i1, i2);
+  auto X = [&](long k) { return FROMB ? op.w(k) * b[k] : xin[k]; };
+  const double ax = op.ax(X, i, i0, i1, i2);
+  xout[i] = X(i) + op.w(i) * (b[i] - ax);
 }
 
 // b_c = R (b - A x): blockIdx.x = the tile of coarse points (t[0] x t[1] x t[2] = 256 of them), `r` = the fine residuals
-// the tile's restriction reads; a fine point outside the grid counts as 0
-__global__ __launch_bounds__(kResThreads) void mg_restrict_kernel(MgLevelArg L, int t0, int t1, int t2, int g0n, int g1n,
-                                                                  const double *__restrict__ x,
+// the tile's restriction reads; a fine point outside the grid counts as 0.  The fine residual never reaches memory.
+template <class Op>
+__global__ __launch_bounds__(kResThreads) void mg_restrict_kernel(typename Op::Level A, int t0, int t1, int t2, int g0n,
+                                                                  int g1n, const double *__restrict__ x,
                                                                   const double *__restrict__ b,
                                                                   double *__restrict__ bc) {
   __shared__ double r[kResLds];
+  const Op op(A);
+  const MgLevelArg &L = op.geo();
   // the tile's three indices ride in blockIdx.x (g0n x g1n x g2n tiles, axis 0 fastest): a long second or third axis
   // would not fit gridDim.y / gridDim.z
   const unsigned bq = blockIdx.x / (unsigned)g0n;
@@ -211,7 +245,7 @@ __global__ __launch_bounds__(kResThreads) void mg_restrict_kernel(MgLevelArg L, 
     double v = 0.0;
     if (g0 < L.n[0] && g1 < L.n[1] && g2 < L.n[2]) {
       const long i = g0 + (long)L.n[0] * (g1 + (long)L.n[1] * g2);
-      v = b[i] - mg_ax(L, X, i, g0, g1, g2);
+      v = b[i] - op.ax(X, i, g0, g1, g2);
     }
     r[t] = v;
   }
@@ -242,7 +276,8 @@ __global__ __launch_bounds__(256) void mg_prolong_kernel(MgLevelArg L, long N, c
 // ------------------------------------------------------------------ the tail: one workgroup, vectors in LDS
 
 // one sweep of a level in LDS: every thread forms its points' new values, then all are written
-__device__ __forceinline__ void tail_sweep(const MgLevelArg &L, int N, double *xs, const double *bs) {
+template <class Op>
+__device__ __forceinline__ void tail_sweep(const Op &op, int N, double *xs, const double *bs) {
   auto X = [&](long k) { return xs[k]; };
   double xn[kTailPts];
 #pragma unroll
@@ -251,8 +286,8 @@ __device__ __forceinline__ void tail_sweep(const MgLevelArg &L, int N, double *x
     xn[p] = 0.0;
     if (i < N) {
       int i0, i1, i2;
-      mg_split(L, i, i0, i1, i2);
-      xn[p] = xs[i] + L.w * (bs[i] - mg_ax(L, X, i, i0, i1, i2));
+      op.split(i, i0, i1, i2);
+      xn[p] = xs[i] + op.w(i) * (bs[i] - op.ax(X, i, i0, i1, i2));
     }
   }
   __syncthreads();
@@ -264,7 +299,10 @@ __device__ __forceinline__ void tail_sweep(const MgLevelArg &L, int N, double *x
   __syncthreads();
 }
 
-__global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const MgTailArg *__restrict__ T,
+// Op: MfOp<3> (each level's MgLevelArg copied into registers) or GTailOp (the level's GLevel stays in global memory, and
+// so do its coefficient arrays: 14 kTailT doubles for the top tail level alone do not fit LDS)
+template <class Op>
+__global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const TailArg<typename Op::Level> *__restrict__ T,
                                                                const double *__restrict__ minv,
                                                                const double *__restrict__ bin,
                                                                double *__restrict__ xout) {
@@ -273,28 +311,29 @@ __global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const MgTailArg *
   double *const mi = sh + 5 * kTailT;
   const int nl = T->nlev, steps = T->steps, tid = threadIdx.x;
   {
-    const MgLevelArg &L = T->lev[0];
+    const MgLevelArg &L = level_geo(T->lev[0]);
     const int N = L.n[0] * L.n[1] * L.n[2];
     double *bs = sh + 2 * kTailT + T->off[0];
     for (int i = tid; i < N; i += kTailThreads) bs[i] = bin[i];
-    const MgLevelArg &C = T->lev[nl - 1];
+    const MgLevelArg &C = level_geo(T->lev[nl - 1]);
     const int nc = C.n[0] * C.n[1] * C.n[2];
     for (int i = tid; i < nc * nc; i += kTailThreads) mi[i] = minv[i];
   }
   __syncthreads();
   // down
   for (int l = 0; l < nl - 1; ++l) {
-    const MgLevelArg L = T->lev[l];
+    const Op op(T->lev[l]);
+    const MgLevelArg &L = op.geo();
     const int N = L.n[0] * L.n[1] * L.n[2], Nc = L.nc[0] * L.nc[1] * L.nc[2];
     double *xs = sh + T->off[l], *bs = sh + 2 * kTailT + T->off[l], *bn = sh + 2 * kTailT + T->off[l + 1];
-    for (int i = tid; i < N; i += kTailThreads) xs[i] = L.w * bs[i];
+    for (int i = tid; i < N; i += kTailThreads) xs[i] = op.w(i) * bs[i];
     __syncthreads();
-    for (int k = 1; k < steps; ++k) tail_sweep(L, N, xs, bs);
+    for (int k = 1; k < steps; ++k) tail_sweep(op, N, xs, bs);
     auto X = [&](long k) { return xs[k]; };
     for (int i = tid; i < N; i += kTailThreads) {
       int i0, i1, i2;
-      mg_split(L, i, i0, i1, i2);
-      scr[i] = bs[i] - mg_ax(L, X, i, i0, i1, i2);
+      op.split(i, i0, i1, i2);
+      scr[i] = bs[i] - op.ax(X, i, i0, i1, i2);
     }
     __syncthreads();
     auto at = [&](int a0, int a1, int a2) {
@@ -308,7 +347,7 @@ __global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const MgTailArg *
   }
   // the coarsest level: x = A^-1 b with the inverse formed at creation
   {
-    const MgLevelArg &C = T->lev[nl - 1];
+    const MgLevelArg &C = level_geo(T->lev[nl - 1]);
     const int nc = C.n[0] * C.n[1] * C.n[2];
     double *xs = sh + T->off[nl - 1];
     const double *bs = sh + 2 * kTailT + T->off[nl - 1];
@@ -321,7 +360,8 @@ __global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const MgTailArg *
   }
   // up
   for (int l = nl - 2; l >= 0; --l) {
-    const MgLevelArg L = T->lev[l];
+    const Op op(T->lev[l]);
+    const MgLevelArg &L = op.geo();
     const int N = L.n[0] * L.n[1] * L.n[2];
     double *xs = sh + T->off[l];
     const double *bs = sh + 2 * kTailT + T->off[l], *en = sh + T->off[l + 1];
@@ -332,10 +372,10 @@ __global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const MgTailArg *
       xs[i] = xs[i] + mg_prolong_point(L, E, i0, i1, i2);
     }
     __syncthreads();
-    for (int k = 0; k < steps; ++k) tail_sweep(L, N, xs, bs);
+    for (int k = 0; k < steps; ++k) tail_sweep(op, N, xs, bs);
   }
   {
-    const MgLevelArg &L = T->lev[0];
+    const MgLevelArg &L = level_geo(T->lev[0]);
     const int N = L.n[0] * L.n[1] * L.n[2];
     const double *xs = sh + T->off[0];
     for (int i = tid; i < N; i += kTailThreads) xout[i] = xs[i];
@@ -431,13 +471,12 @@ struct psp_mg {
   int tail_first = 0;  // first level of the tail launch
   int launches = 0;    // kernel launches of one application
   double *minv = nullptr;
-  MgTailArg *tail = nullptr;
+  void *tail = nullptr;  // the mode's TailArg on the device
   // galerkin = True (psp_mg_galerkin.h): the stored level operators; `coef` owns each level's arrays in one allocation
   // (diagonal, omega / diagonal, the lower arrays)
   bool galerkin = false;
   std::vector<GLevel> glev;
   std::vector<double *> coef;
-  GTailArg *gtail = nullptr;
 };
 
 namespace {
@@ -515,6 +554,21 @@ int read_flag(int *bad_dev, int *bad) {
   return PSP_OK;
 }
 
+// one checking pass: launch(flag) with a zeroed device flag, then the flag read back into *bad
+template <class Launch>
+int run_check(int *bad, Launch &&launch) {
+  int *bad_dev = nullptr;
+  PSP_HIP(hipMalloc((void **)&bad_dev, sizeof(int)));
+  hipError_t e = hipMemsetAsync(bad_dev, 0, sizeof(int), stream());
+  if (e == hipSuccess) {
+    launch(bad_dev);
+    e = hipGetLastError();
+  }
+  const int rc = e == hipSuccess ? read_flag(bad_dev, bad) : fail(PSP_ENODEV, "multigrid: %s", hipGetErrorString(e));
+  (void)hipFree(bad_dev);
+  return rc;
+}
+
 // c_a, d0 of A and the exact check that A is that stencil on that grid -- from the CSR arrays, or, for a handle that only
 // kept its index-free layout, from that layout's offsets, values and row masks
 int read_stencil(const psp_csr *A, const int n[3], MgStencil *S) {
@@ -525,7 +579,6 @@ int read_stencil(const psp_csr *A, const int n[3], MgStencil *S) {
   }
   S->d0 = 0.0;
   bool have_d = false, have_c[3] = {false, false, false};
-  int *bad_dev = nullptr;
   int bad = 0;
   const char *why = "multigrid: the matrix is not a constant-coefficient [-1 2 -1] stencil on this grid";
   if (A->ind && A->col && A->val && !A->w4_only) {
@@ -585,32 +638,19 @@ int read_stencil(const psp_csr *A, const int n[3], MgStencil *S) {
     for (int a = 0; a < 3; ++a)
       if (n[a] > 1 && (!have_c[a] || !have_l[a] || !(lower[a] == S->c[a]))) return fail(PSP_EINVAL, "%s", why);
     if (!have_d) return fail(PSP_EINVAL, "%s", why);
-    PSP_HIP(hipMalloc((void **)&bad_dev, sizeof(int)));
-    hipError_t e = hipMemsetAsync(bad_dev, 0, sizeof(int), stream());
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(mg_check_w4_kernel, dim3((A->nrows + 255) / 256), dim3(256), 0, stream(), A->nrows, *S, Q, v.mask,
-                         bad_dev);
-      e = hipGetLastError();
-    }
-    int rc = e == hipSuccess ? read_flag(bad_dev, &bad) : fail(PSP_ENODEV, "multigrid: %s", hipGetErrorString(e));
-    (void)hipFree(bad_dev);
-    PSP_TRY(rc);
+    PSP_TRY(run_check(&bad, [&](int *flag) {
+      hipLaunchKernelGGL(mg_check_w4_kernel, dim3((A->nrows + 255) / 256), dim3(256), 0, stream(), A->nrows, *S, Q, v.mask, flag);
+    }));
     if (bad) return fail(PSP_EINVAL, "%s", why);
     return PSP_OK;
   }
   if (!have_d) return fail(PSP_EINVAL, "%s (row 0 has no diagonal)", why);
   for (int a = 0; a < 3; ++a)
     if (n[a] > 1 && !have_c[a]) return fail(PSP_EINVAL, "%s (row 0 has no neighbour along axis %d)", why, a);
-  PSP_HIP(hipMalloc((void **)&bad_dev, sizeof(int)));
-  hipError_t e = hipMemsetAsync(bad_dev, 0, sizeof(int), stream());
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(mg_check_csr_kernel, dim3((A->nrows + 255) / 256), dim3(256), 0, stream(), A->nrows, *S, A->ind,
-                       A->col, A->val, bad_dev);
-    e = hipGetLastError();
-  }
-  int rc = e == hipSuccess ? read_flag(bad_dev, &bad) : fail(PSP_ENODEV, "multigrid: %s", hipGetErrorString(e));
-  (void)hipFree(bad_dev);
-  PSP_TRY(rc);
+  PSP_TRY(run_check(&bad, [&](int *flag) {
+    hipLaunchKernelGGL(mg_check_csr_kernel, dim3((A->nrows + 255) / 256), dim3(256), 0, stream(), A->nrows, *S, A->ind, A->col,
+                       A->val, flag);
+  }));
   if (bad) return fail(PSP_EINVAL, "%s", why);
   return PSP_OK;
 }
@@ -666,6 +706,67 @@ int mg_level_grids(psp_mg *K, const int n[3], int steps) {
   return PSP_OK;
 }
 
+// level vectors: the finest level works in the caller's vectors and one spare; a level that heads the tail needs its
+// b and x in memory (the restriction above it writes b, the prolongation reads x); the levels inside the tail have none
+int mg_alloc_vectors(psp_mg *K) {
+  for (int l = 0; l <= K->tail_first; ++l) {
+    psp_mg::Level &L = K->lev[l];
+    const size_t bytes = sizeof(double) * (size_t)L.N;
+    hipError_t e = hipSuccess;
+    if (l < K->tail_first) e = hipMalloc((void **)&L.t, bytes);
+    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&L.x, bytes);
+    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&L.b, bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(PSP_ENOMEM, "multigrid: level vector allocation failed");
+    }
+  }
+  return PSP_OK;
+}
+
+// the tail's table (level(l) = what the mode keeps of level l) and the coarsest level's inverse, to the device
+template <class LevelOf>
+int mg_upload_tail(psp_mg *K, const std::vector<double> &inv, LevelOf &&level) {
+  TailArg<std::decay_t<decltype(level(0))>> T;
+  memset(&T, 0, sizeof T);
+  const int nl = (int)K->lev.size();
+  T.nlev = nl - K->tail_first;
+  T.steps = K->steps;
+  int off = 0;
+  for (int l = K->tail_first; l < nl; ++l) {
+    T.off[l - K->tail_first] = off;
+    T.lev[l - K->tail_first] = level(l);
+    off += (int)K->lev[l].N;
+  }
+  if (off > 2 * kTailT) return fail(PSP_EINVAL, "multigrid: the tail does not fit");
+  if (hipMalloc((void **)&K->minv, sizeof(double) * inv.size()) != hipSuccess ||
+      hipMalloc(&K->tail, sizeof T) != hipSuccess ||
+      hipMemcpy(K->minv, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(K->tail, &T, sizeof T, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PSP_ENOMEM, "multigrid: tail table allocation failed");
+  }
+  return PSP_OK;
+}
+
+// the handle of either mode: build(K) is everything that can fail once it exists (it is destroyed then)
+template <class Build>
+int mg_make(const psp_csr *A, int ndim, double omega, int steps, bool galerkin, psp_mg **out, Build &&build) {
+  psp_mg *K = new psp_mg();
+  K->n = A->nrows;
+  K->ndim = ndim;
+  K->omega = omega;
+  K->steps = steps;
+  K->galerkin = galerkin;
+  const int rc = build(K);
+  if (rc != PSP_OK) {
+    psp_mg_destroy(K);
+    return rc;
+  }
+  *out = K;
+  return PSP_OK;
+}
+
 int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, psp_mg **out) {
   int n[3];
   PSP_TRY(mg_check_args(A, ndim, grid, omega, steps, out, n));
@@ -682,14 +783,9 @@ int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, ps
     return fail(PSP_EINVAL, "multigrid: the shift s = diagonal - 2 sum c = %g is negative", s);
   if (s < 0.0) s = 0.0;
 
-  psp_mg *K = new psp_mg();
-  K->n = A->nrows;
-  K->ndim = ndim;
-  K->omega = omega;
-  K->steps = steps;
-  // the levels: c_a / 4 on the axes coarsened above, d = 2 sum c + s
-  int rc = mg_level_grids(K, n, steps);
-  {
+  return mg_make(A, ndim, omega, steps, false, out, [&](psp_mg *K) {
+    // the levels: c_a / 4 on the axes coarsened above, d = 2 sum c + s
+    PSP_TRY(mg_level_grids(K, n, steps));
     double c[3] = {S.c[0], S.c[1], S.c[2]};
     for (psp_mg::Level &L : K->lev) {
       double sum = 0.0;
@@ -702,51 +798,11 @@ int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, ps
       for (int a = 0; a < 3; ++a)
         if (L.a.co[a]) c[a] /= 4.0;
     }
-  }
-  const int nl = (int)K->lev.size();
-  // level vectors: the finest level works in the caller's vectors and one spare; a level that heads the tail needs its
-  // b and x in memory (the restriction above it writes b, the prolongation reads x)
-  for (int l = 0; l <= K->tail_first && rc == PSP_OK; ++l) {
-    psp_mg::Level &L = K->lev[l];
-    const size_t bytes = sizeof(double) * (size_t)L.N;
-    hipError_t e = hipSuccess;
-    if (l < K->tail_first) e = hipMalloc((void **)&L.t, bytes);
-    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&L.x, bytes);
-    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&L.b, bytes);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      rc = fail(PSP_ENOMEM, "multigrid: level vector allocation failed");
-    }
-  }
-  std::vector<double> inv;
-  if (rc == PSP_OK) rc = coarsest_inverse(K->lev[nl - 1].a, &inv);
-  if (rc == PSP_OK) {
-    MgTailArg T;
-    memset(&T, 0, sizeof T);
-    T.nlev = nl - K->tail_first;
-    T.steps = steps;
-    int off = 0;
-    for (int l = K->tail_first; l < nl; ++l) {
-      T.off[l - K->tail_first] = off;
-      T.lev[l - K->tail_first] = K->lev[l].a;
-      off += (int)K->lev[l].N;
-    }
-    if (off > 2 * kTailT) rc = fail(PSP_EINVAL, "multigrid: the tail does not fit");
-    if (rc == PSP_OK &&
-        (hipMalloc((void **)&K->minv, sizeof(double) * inv.size()) != hipSuccess ||
-         hipMalloc((void **)&K->tail, sizeof(MgTailArg)) != hipSuccess ||
-         hipMemcpy(K->minv, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess ||
-         hipMemcpy(K->tail, &T, sizeof T, hipMemcpyHostToDevice) != hipSuccess)) {
-      (void)hipGetLastError();
-      rc = fail(PSP_ENOMEM, "multigrid: tail table allocation failed");
-    }
-  }
-  if (rc != PSP_OK) {
-    psp_mg_destroy(K);
-    return rc;
-  }
-  *out = K;
-  return PSP_OK;
+    PSP_TRY(mg_alloc_vectors(K));
+    std::vector<double> inv;
+    PSP_TRY(coarsest_inverse(K->lev.back().a, &inv));
+    return mg_upload_tail(K, inv, [&](int l) { return K->lev[l].a; });
+  });
 }
 
 // ------------------------------------------------------------------ galerkin = True: creation
@@ -771,17 +827,29 @@ int g_bad_shape(const GLevel &G) {
   return fail(PSP_EINVAL, "multigrid: internal error (a level of %d axes with %d lower arrays)", G.nd, G.noff);
 }
 
-int launch_galerkin(const GLevel &S, long Nc, double omega, const GOut &o, int *flag) {
-  const dim3 g((unsigned)((Nc + 255) / 256)), t(256);
-  switch (S.nd * 16 + S.noff) {
-    case 1 * 16 + 1: hipLaunchKernelGGL((mg_galerkin_kernel<1, 1>), g, t, 0, stream(), S, Nc, omega, o, flag); break;
-    case 2 * 16 + 2: hipLaunchKernelGGL((mg_galerkin_kernel<2, 2>), g, t, 0, stream(), S, Nc, omega, o, flag); break;
-    case 2 * 16 + 4: hipLaunchKernelGGL((mg_galerkin_kernel<2, 4>), g, t, 0, stream(), S, Nc, omega, o, flag); break;
-    case 3 * 16 + 3: hipLaunchKernelGGL((mg_galerkin_kernel<3, 3>), g, t, 0, stream(), S, Nc, omega, o, flag); break;
-    case 3 * 16 + 13: hipLaunchKernelGGL((mg_galerkin_kernel<3, 13>), g, t, 0, stream(), S, Nc, omega, o, flag); break;
-    default: return g_bad_shape(S);
+// f(GShape<ND, NOFF>{}) for the level's shape: the one place that turns (nd, noff) into template arguments
+template <int ND, int NOFF>
+struct GShape {
+  static constexpr int nd = ND, noff = NOFF;
+};
+template <class F>
+int g_dispatch(const GLevel &G, F &&f) {
+  switch (G.nd * 16 + G.noff) {
+    case 1 * 16 + 1: f(GShape<1, 1>{}); break;
+    case 2 * 16 + 2: f(GShape<2, 2>{}); break;
+    case 2 * 16 + 4: f(GShape<2, 4>{}); break;
+    case 3 * 16 + 3: f(GShape<3, 3>{}); break;
+    case 3 * 16 + 13: f(GShape<3, 13>{}); break;
+    default: return g_bad_shape(G);
   }
   return PSP_OK;
+}
+
+int launch_galerkin(const GLevel &S, long Nc, double omega, const GOut &o, int *flag) {
+  return g_dispatch(S, [&](auto sh) {
+    hipLaunchKernelGGL((mg_galerkin_kernel<sh.nd, sh.noff>), dim3((unsigned)((Nc + 255) / 256)), dim3(256), 0, stream(), S,
+                       Nc, omega, o, flag);
+  });
 }
 
 // the dense matrix of a (small) level from its downloaded arrays: blk = diagonal, omega / diagonal, the lower arrays
@@ -803,14 +871,14 @@ void g_dense(const GLevel &G, const std::vector<double> &blk, std::vector<double
   }
 }
 
-// everything of mg_create_galerkin that can fail after the handle exists (the caller destroys it then)
+// mg_create_galerkin's part of mg_make
 int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
   const double omega = K->omega;
-  const int steps = K->steps;
   const int nd = n[2] > 1 ? 3 : n[1] > 1 ? 2 : 1;
-  PSP_TRY(mg_level_grids(K, n, steps));  // section 9c's
+  PSP_TRY(mg_level_grids(K, n, K->steps));  // section 9c's
   const int nl = (int)K->lev.size();
-  // the level operators' arrays and the level vectors
+  // the level vectors and the level operators' arrays
+  PSP_TRY(mg_alloc_vectors(K));
   K->glev.resize(nl);
   K->coef.assign(nl, nullptr);
   for (int l = 0; l < nl; ++l) {
@@ -829,15 +897,6 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
     for (int k = 0; k < G.noff; ++k) {
       G.lo[k] = K->coef[l] + (size_t)(2 + k) * (size_t)L.N;
       for (int a = 0; a < 3; ++a) G.od[k][a] = g_d(nd, G.noff, k, a);
-    }
-    const size_t bytes = sizeof(double) * (size_t)L.N;
-    hipError_t e = hipSuccess;
-    if (l < K->tail_first) e = hipMalloc((void **)&L.t, bytes);
-    if (l > 0 && l <= K->tail_first && e == hipSuccess) e = hipMalloc((void **)&L.x, bytes);
-    if (l > 0 && l <= K->tail_first && e == hipSuccess) e = hipMalloc((void **)&L.b, bytes);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(PSP_ENOMEM, "multigrid: level vector allocation failed");
     }
   }
   // level 0: the checking pass writes it
@@ -866,25 +925,7 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
   PSP_HIP(hipStreamSynchronize(stream()));
   g_dense(C, blk, &M);
   PSP_TRY(dense_inverse(m, M, &inv));
-  GTailArg T;
-  memset(&T, 0, sizeof T);
-  T.nlev = nl - K->tail_first;
-  T.steps = steps;
-  int off = 0;
-  for (int l = K->tail_first; l < nl; ++l) {
-    T.off[l - K->tail_first] = off;
-    T.lev[l - K->tail_first] = K->glev[l];
-    off += (int)K->lev[l].N;
-  }
-  if (off > 2 * kTailT) return fail(PSP_EINVAL, "multigrid: the tail does not fit");
-  if (hipMalloc((void **)&K->minv, sizeof(double) * inv.size()) != hipSuccess ||
-      hipMalloc((void **)&K->gtail, sizeof(GTailArg)) != hipSuccess ||
-      hipMemcpy(K->minv, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(K->gtail, &T, sizeof T, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(PSP_ENOMEM, "multigrid: tail table allocation failed");
-  }
-  return PSP_OK;
+  return mg_upload_tail(K, inv, [&](int l) { return K->glev[l]; });
 }
 
 int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int steps, psp_mg **out) {
@@ -895,121 +936,87 @@ int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int 
   PSP_TRY(ensure_device());
   int *flags = nullptr;
   PSP_HIP(hipMalloc((void **)&flags, 2 * sizeof(int)));
-  psp_mg *K = new psp_mg();
-  K->n = A->nrows;
-  K->ndim = ndim;
-  K->omega = omega;
-  K->steps = steps;
-  K->galerkin = true;
-  const int rc = g_build(K, A, n, flags);
+  const int rc = mg_make(A, ndim, omega, steps, true, out, [&](psp_mg *K) { return g_build(K, A, n, flags); });
   (void)hipFree(flags);
-  if (rc != PSP_OK) {
-    psp_mg_destroy(K);
-    return rc;
-  }
-  *out = K;
-  return PSP_OK;
+  return rc;
 }
 
-template <bool FROMB>
-int launch_vsmooth(const GLevel &G, long N, const double *xin, const double *b, double *xout) {
-  const dim3 g((unsigned)((N + 255) / 256)), t(256);
-  switch (G.nd * 16 + G.noff) {
-    case 1 * 16 + 1: hipLaunchKernelGGL((mg_vsmooth_kernel<1, 1, FROMB>), g, t, 0, stream(), G, N, xin, b, xout); break;
-    case 2 * 16 + 2: hipLaunchKernelGGL((mg_vsmooth_kernel<2, 2, FROMB>), g, t, 0, stream(), G, N, xin, b, xout); break;
-    case 2 * 16 + 4: hipLaunchKernelGGL((mg_vsmooth_kernel<2, 4, FROMB>), g, t, 0, stream(), G, N, xin, b, xout); break;
-    case 3 * 16 + 3: hipLaunchKernelGGL((mg_vsmooth_kernel<3, 3, FROMB>), g, t, 0, stream(), G, N, xin, b, xout); break;
-    case 3 * 16 + 13: hipLaunchKernelGGL((mg_vsmooth_kernel<3, 13, FROMB>), g, t, 0, stream(), G, N, xin, b, xout); break;
-    default: return g_bad_shape(G);
-  }
-  return PSP_OK;
+template <class Op, bool FROMB>
+void launch_smooth(const typename Op::Level &A, long N, const double *xin, const double *b, double *xout) {
+  hipLaunchKernelGGL((mg_smooth_kernel<Op, FROMB>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream(), A, N, xin, b,
+                     xout);
 }
 
-int launch_vrestrict(const GLevel &G, const double *x, const double *b, double *bc) {
+template <class Op>
+void launch_restrict(const typename Op::Level &A, const double *x, const double *b, double *bc) {
+  const MgLevelArg &a = level_geo(A);
   int tile[3];
-  mg_tile(G.a, tile);
-  const long g0n = (G.a.nc[0] + tile[0] - 1) / tile[0], g1n = (G.a.nc[1] + tile[1] - 1) / tile[1],
-             g2n = (G.a.nc[2] + tile[2] - 1) / tile[2];
-  const dim3 g((unsigned)(g0n * g1n * g2n)), t(kResThreads);
-#define PSP_VRES(ND, NOFF) \
-  hipLaunchKernelGGL((mg_vrestrict_kernel<ND, NOFF>), g, t, 0, stream(), G, tile[0], tile[1], tile[2], (int)g0n, (int)g1n, x, b, bc)
-  switch (G.nd * 16 + G.noff) {
-    case 1 * 16 + 1: PSP_VRES(1, 1); break;
-    case 2 * 16 + 2: PSP_VRES(2, 2); break;
-    case 2 * 16 + 4: PSP_VRES(2, 4); break;
-    case 3 * 16 + 3: PSP_VRES(3, 3); break;
-    case 3 * 16 + 13: PSP_VRES(3, 13); break;
-    default: return g_bad_shape(G);
-  }
-#undef PSP_VRES
-  return PSP_OK;
-}
-
-template <bool FROMB>
-void launch_smooth(const psp_mg::Level &L, const double *xin, const double *b, double *xout) {
-  const dim3 g((unsigned)((L.N + 255) / 256)), t(256);
-  switch (level_nd(L.a)) {
-    case 1: hipLaunchKernelGGL((mg_smooth_kernel<1, FROMB>), g, t, 0, stream(), L.a, L.N, xin, b, xout); break;
-    case 2: hipLaunchKernelGGL((mg_smooth_kernel<2, FROMB>), g, t, 0, stream(), L.a, L.N, xin, b, xout); break;
-    default: hipLaunchKernelGGL((mg_smooth_kernel<3, FROMB>), g, t, 0, stream(), L.a, L.N, xin, b, xout); break;
-  }
-}
-
-void launch_restrict(const psp_mg::Level &L, const double *x, const double *b, double *bc) {
-  int tile[3];
-  mg_tile(L.a, tile);
+  mg_tile(a, tile);
   // at most ceil(nc0 / t0) ceil(nc1 / t1) ceil(nc2 / t2) <= 2^31 / 256 + a few tiles: fits gridDim.x
-  const long g0n = (L.a.nc[0] + tile[0] - 1) / tile[0], g1n = (L.a.nc[1] + tile[1] - 1) / tile[1],
-             g2n = (L.a.nc[2] + tile[2] - 1) / tile[2];
-  hipLaunchKernelGGL(mg_restrict_kernel, dim3((unsigned)(g0n * g1n * g2n)), dim3(kResThreads), 0, stream(), L.a, tile[0],
+  const long g0n = (a.nc[0] + tile[0] - 1) / tile[0], g1n = (a.nc[1] + tile[1] - 1) / tile[1],
+             g2n = (a.nc[2] + tile[2] - 1) / tile[2];
+  hipLaunchKernelGGL((mg_restrict_kernel<Op>), dim3((unsigned)(g0n * g1n * g2n)), dim3(kResThreads), 0, stream(), A, tile[0],
                      tile[1], tile[2], (int)g0n, (int)g1n, x, b, bc);
 }
 
-// what the two modes launch for the steps of the schedule below: the first pass from x = 0 (x = w b when steps = 1, else
-// sweeps one and two in one pass over b), a further sweep, b_c = R (b - A x), the tail
-struct MatrixFreeOps {
+// what the steps of the schedule below launch: the first pass from x = 0 (x = w b when steps = 1, else sweeps one and two
+// in one pass over b), a further sweep, b_c = R (b - A x), the tail -- the cycle kernels with the mode's policy
+struct LevelOps {
   psp_mg *K;
+  template <bool FROMB>
+  int smooth(int l, const double *xin, const double *b, double *xout) const {
+    const long N = K->lev[l].N;
+    if (K->galerkin) {
+      const GLevel &G = K->glev[l];
+      return g_dispatch(G, [&](auto sh) { launch_smooth<GOp<sh.nd, sh.noff>, FROMB>(G, N, xin, b, xout); });
+    }
+    const MgLevelArg &a = K->lev[l].a;
+    switch (level_nd(a)) {
+      case 1: launch_smooth<MfOp<1>, FROMB>(a, N, xin, b, xout); break;
+      case 2: launch_smooth<MfOp<2>, FROMB>(a, N, xin, b, xout); break;
+      default: launch_smooth<MfOp<3>, FROMB>(a, N, xin, b, xout); break;
+    }
+    return PSP_OK;
+  }
   int first(int l, const double *b, double *dst) const {
-    const psp_mg::Level &L = K->lev[l];
-    if (K->steps == 1)
-      hipLaunchKernelGGL(mg_scale_kernel, dim3((unsigned)((L.N + 255) / 256)), dim3(256), 0, stream(), L.N, L.a.w, b, dst);
+    if (K->steps > 1) return smooth<true>(l, nullptr, b, dst);
+    const long N = K->lev[l].N;
+    const dim3 g((unsigned)((N + 255) / 256)), t(256);
+    if (K->galerkin)
+      hipLaunchKernelGGL(mg_scale_kernel<GW>, g, t, 0, stream(), N, GW{K->glev[l].w}, b, dst);
     else
-      launch_smooth<true>(L, nullptr, b, dst);
+      hipLaunchKernelGGL(mg_scale_kernel<MfW>, g, t, 0, stream(), N, MfW{K->lev[l].a.w}, b, dst);
     return PSP_OK;
   }
-  int sweep(int l, const double *xin, const double *b, double *xout) const {
-    launch_smooth<false>(K->lev[l], xin, b, xout);
-    return PSP_OK;
-  }
+  int sweep(int l, const double *xin, const double *b, double *xout) const { return smooth<false>(l, xin, b, xout); }
   int restrict_to(int l, const double *x, const double *b, double *bc) const {
-    launch_restrict(K->lev[l], x, b, bc);
+    if (K->galerkin) {
+      const GLevel &G = K->glev[l];
+      return g_dispatch(G, [&](auto sh) { launch_restrict<GOp<sh.nd, sh.noff>>(G, x, b, bc); });
+    }
+    launch_restrict<MfOp<3>>(K->lev[l].a, x, b, bc);
     return PSP_OK;
   }
   void tail(const double *b, double *x) const {
-    hipLaunchKernelGGL(mg_tail_kernel, dim3(1), dim3(kTailThreads), 0, stream(), (const MgTailArg *)K->tail,
-                       (const double *)K->minv, b, x);
+    if (K->galerkin)
+      hipLaunchKernelGGL(mg_tail_kernel<GTailOp>, dim3(1), dim3(kTailThreads), 0, stream(),
+                         (const TailArg<GLevel> *)K->tail, (const double *)K->minv, b, x);
+    else
+      hipLaunchKernelGGL(mg_tail_kernel<MfOp<3>>, dim3(1), dim3(kTailThreads), 0, stream(),
+                         (const TailArg<MgLevelArg> *)K->tail, (const double *)K->minv, b, x);
   }
 };
 
-struct GalerkinOps {
-  psp_mg *K;
-  int first(int l, const double *b, double *dst) const {
-    const long N = K->lev[l].N;
-    if (K->steps > 1) return launch_vsmooth<true>(K->glev[l], N, nullptr, b, dst);
-    hipLaunchKernelGGL(mg_vscale_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream(), N, K->glev[l].w, b, dst);
-    return PSP_OK;
-  }
-  int sweep(int l, const double *xin, const double *b, double *xout) const {
-    return launch_vsmooth<false>(K->glev[l], K->lev[l].N, xin, b, xout);
-  }
-  int restrict_to(int l, const double *x, const double *b, double *bc) const {
-    return launch_vrestrict(K->glev[l], x, b, bc);
-  }
-  void tail(const double *b, double *x) const {
-    hipLaunchKernelGGL(mg_gtail_kernel, dim3(1), dim3(kTailThreads), 0, stream(), (const GTailArg *)K->gtail,
-                       (const double *)K->minv, b, x);
-  }
-};
+// the sss entry points: an sss_mat is read through its full device mirror
+int mg_create_sss(psp_sss_t *A, const char *fn, int (*create)(psp_csr *, int, const int *, double, int, psp_mg **), int ndim,
+                  const int *grid, double omega, int steps, psp_mg **out) {
+  PSP_API_GUARD_H(A, A ? A->full : nullptr);
+  if (!A) return fail(PSP_EINVAL, "%s: NULL argument", fn);
+  if (A->host || cpu_mode())
+    return fail(PSP_ENODEV, "precon.multigrid: not available with PSP_DEVICE=cpu (host mode covers csr / sss / jacobi / pcg / minres)");
+  if (!A->full) return fail(PSP_EINVAL, "%s: the matrix has no device mirror", fn);
+  return create(A->full, ndim, grid, omega, steps, out);
+}
 
 // one V-cycle: the schedule of launches and buffers, the same in both modes
 template <class Ops>
@@ -1069,7 +1076,7 @@ namespace psp {
 
 // y = V(0, b) on device vectors; y must not alias b.  The handle is locked by the caller.
 int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
-  return K->galerkin ? mg_schedule(K, b_dev, y_dev, GalerkinOps{K}) : mg_schedule(K, b_dev, y_dev, MatrixFreeOps{K});
+  return mg_schedule(K, b_dev, y_dev, LevelOps{K});
 }
 
 }  // namespace psp
@@ -1082,12 +1089,7 @@ int psp_mg_create_csr(psp_csr_t *A, int ndim, const int *grid, double omega, int
 }
 
 int psp_mg_create_sss(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
-  PSP_API_GUARD_H(A, A ? A->full : nullptr);
-  if (!A) return fail(PSP_EINVAL, "psp_mg_create_sss: NULL argument");
-  if (A->host || cpu_mode())
-    return fail(PSP_ENODEV, "precon.multigrid: not available with PSP_DEVICE=cpu (host mode covers csr / sss / jacobi / pcg / minres)");
-  if (!A->full) return fail(PSP_EINVAL, "psp_mg_create_sss: the matrix has no device mirror");
-  return mg_create(A->full, ndim, grid, omega, steps, out);
+  return mg_create_sss(A, "psp_mg_create_sss", mg_create, ndim, grid, omega, steps, out);
 }
 
 int psp_mg_create_csr_galerkin(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
@@ -1096,12 +1098,7 @@ int psp_mg_create_csr_galerkin(psp_csr_t *A, int ndim, const int *grid, double o
 }
 
 int psp_mg_create_sss_galerkin(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
-  PSP_API_GUARD_H(A, A ? A->full : nullptr);
-  if (!A) return fail(PSP_EINVAL, "psp_mg_create_sss_galerkin: NULL argument");
-  if (A->host || cpu_mode())
-    return fail(PSP_ENODEV, "precon.multigrid: not available with PSP_DEVICE=cpu (host mode covers csr / sss / jacobi / pcg / minres)");
-  if (!A->full) return fail(PSP_EINVAL, "psp_mg_create_sss_galerkin: the matrix has no device mirror");
-  return mg_create_galerkin(A->full, ndim, grid, omega, steps, out);
+  return mg_create_sss(A, "psp_mg_create_sss_galerkin", mg_create_galerkin, ndim, grid, omega, steps, out);
 }
 
 int psp_mg_is_galerkin(const psp_mg_t *K, int *galerkin) {
@@ -1139,7 +1136,6 @@ int psp_mg_level_operator(psp_mg_t *K, int level, int *offsets_out, int *noff_in
 int psp_mg_destroy(psp_mg_t *K) {
   if (!K) return PSP_OK;
   for (double *p : K->coef) (void)hipFree(p);
-  (void)hipFree(K->gtail);
   for (psp_mg::Level &L : K->lev)
     for (void *p : {(void *)L.x, (void *)L.b, (void *)L.t}) (void)hipFree(p);
   (void)hipFree(K->minv);

@@ -1,5 +1,7 @@
 // psp_mg_galerkin.h -- the second mode of precon.multigrid: galerkin=True (DESIGN.md section 9d is the normative text).
-// Part of psp_mg.hip's translation unit (included after the matrix-free kernels, whose transfer operators it reuses).
+// Part of psp_mg.hip's translation unit (included after the cycle kernels, which both modes share).  What only the
+// stored mode has: the level's arrays (GLevel), the offset tables, (A_l x)[i] from the arrays (g_ax / g_ax_rt) with the
+// level-operator policies GOp / GTailOp that hand them to the cycle kernels, the extraction and the Galerkin product.
 //
 // A is any symmetric 3- / 5- / 7-point operator on the grid (varying coefficients); the level operators are
 // A_0 = A, A_{l+1} = R_l A_l P_l with section 9c's P and R, stored as symmetric stencils, offset-major: the diagonal
@@ -26,12 +28,7 @@ struct GOut {
   double *diag, *w, *lo[kGMaxOff];
 };
 
-struct GTailArg {
-  int nlev;
-  int steps;
-  int off[kTailMaxLev];
-  GLevel lev[kTailMaxLev];
-};
+__host__ __device__ inline const MgLevelArg &level_geo(const GLevel &G) { return G.a; }
 
 constexpr int g_full_noff(int nd) { return nd == 1 ? 1 : nd == 2 ? 4 : 13; }
 constexpr int g_pow3(int nd) { return nd == 1 ? 3 : nd == 2 ? 9 : 27; }
@@ -115,16 +112,39 @@ __device__ __forceinline__ double g_ax_rt(const GLevel &L, const X &x, int i, in
   return acc;
 }
 
-template <int ND>
-__device__ __forceinline__ void g_split(const MgLevelArg &a, long i, int &i0, int &i1, int &i2) {
-  i0 = (int)i, i1 = 0, i2 = 0;
-  if constexpr (ND == 2) {
-    i0 = (int)(i % a.n[0]);
-    i1 = (int)(i / a.n[0]);
-  } else if constexpr (ND == 3) {
-    mg_split(a, i, i0, i1, i2);
+// The level-operator policies of the stored mode.  GOp: the launch-per-step kernels, the level's shape in the type (g_ax).
+template <int ND, int NOFF>
+struct GOp {
+  using Level = GLevel;
+  const GLevel &G;
+  __device__ __forceinline__ explicit GOp(const GLevel &g) : G(g) {}
+  __device__ __forceinline__ const MgLevelArg &geo() const { return G.a; }
+  template <class X>
+  __device__ __forceinline__ double ax(const X &x, long i, int i0, int i1, int i2) const {
+    return g_ax<ND, NOFF>(G, x, i, i0, i1, i2);
   }
-}
+  __device__ __forceinline__ double w(long i) const { return G.w[i]; }
+  __device__ __forceinline__ void split(long i, int &i0, int &i1, int &i2) const { mg_split<ND>(G.a, i, i0, i1, i2); }
+};
+// GTailOp: the tail, where the level stays in global memory (g_ax_rt) and only its geometry is copied into registers
+struct GTailOp {
+  using Level = GLevel;
+  const GLevel &G;
+  const MgLevelArg L;
+  __device__ __forceinline__ explicit GTailOp(const GLevel &g) : G(g), L(g.a) {}
+  __device__ __forceinline__ const MgLevelArg &geo() const { return L; }
+  template <class X>
+  __device__ __forceinline__ double ax(const X &x, long i, int i0, int i1, int i2) const {
+    return g_ax_rt(G, x, (int)i, i0, i1, i2);
+  }
+  __device__ __forceinline__ double w(long i) const { return G.w[i]; }
+  __device__ __forceinline__ void split(long i, int &i0, int &i1, int &i2) const { mg_split(L, i, i0, i1, i2); }
+};
+// omega / diagonal as mg_scale_kernel takes it
+struct GW {
+  const double *__restrict__ w;
+  __device__ __forceinline__ double operator()(long i) const { return w[i]; }
+};
 
 // ------------------------------------------------------------------ creation: extraction and the Galerkin product
 
@@ -261,173 +281,6 @@ __global__ __launch_bounds__(256) void mg_galerkin_kernel(GLevel S, long Nc, dou
       out.lo[dk - 1][K] = acc;
     }
   });
-}
-
-// ------------------------------------------------------------------ the launch-per-step kernels of the large levels
-
-// the first sweep from x = 0: x = w o b
-__global__ __launch_bounds__(256) void mg_vscale_kernel(long N, const double *__restrict__ w, const double *__restrict__ b,
-                                                        double *__restrict__ x) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < N) x[i] = w[i] * b[i];
-}
-
-// one sweep, out of place, with the stored stencil: xout = xin + w o (b - A_l xin).  Reads xin, b, w and every
-// coefficient array once, writes xout once; the neighbours' rows of the lower arrays (the upper couplings) and of xin are
-// cache hits.  FROMB as in mg_smooth_kernel: xin = w o b formed on the fly.
-template <int ND, int NOFF, bool FROMB>
-__global__ __launch_bounds__(256) void mg_vsmooth_kernel(GLevel L, long N, const double *__restrict__ xin,
-                                                         const double *__restrict__ b, double *__restrict__ xout) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
-  int i0, i1, i2;
-  g_split<ND>(L.a, i, i0, i1, i2);
-  const double *__restrict__ w = L.w;
-  auto X = [&](long k) { return FROMB ? w[k] * b[k] : xin[k]; };
-  const double ax = g_ax<ND, NOFF>(L, X, i, i0, i1, i2);
-  xout[i] = X(i) + w[i] * (b[i] - ax);
-}
-
-// b_c = R (b - A_l x): mg_restrict_kernel's tile in LDS with the stored stencil; the fine residual never reaches memory
-template <int ND, int NOFF>
-__global__ __launch_bounds__(kResThreads) void mg_vrestrict_kernel(GLevel L, int t0, int t1, int t2, int g0n, int g1n,
-                                                                   const double *__restrict__ x,
-                                                                   const double *__restrict__ b,
-                                                                   double *__restrict__ bc) {
-  __shared__ double r[kResLds];
-  const MgLevelArg &a = L.a;
-  const unsigned bq = blockIdx.x / (unsigned)g0n;
-  const int J0 = (int)(blockIdx.x % (unsigned)g0n) * t0, J1 = (int)(bq % (unsigned)g1n) * t1, J2 = (int)(bq / (unsigned)g1n) * t2;
-  const int f0 = a.co[0] ? 2 * J0 : J0, F0 = a.co[0] ? 2 * t0 + 1 : t0;
-  const int f1 = a.co[1] ? 2 * J1 : J1, F1 = a.co[1] ? 2 * t1 + 1 : t1;
-  const int f2 = a.co[2] ? 2 * J2 : J2, F2 = a.co[2] ? 2 * t2 + 1 : t2;
-  const int total = F0 * F1 * F2;  // <= kResLds (mg_tile)
-  auto X = [&](long k) { return x[k]; };
-  for (int t = threadIdx.x; t < total; t += kResThreads) {
-    const int l0 = t % F0, q = t / F0, l1 = q % F1, l2 = q / F1;
-    const int g0 = f0 + l0, g1 = f1 + l1, g2 = f2 + l2;
-    double v = 0.0;
-    if (g0 < a.n[0] && g1 < a.n[1] && g2 < a.n[2]) {
-      const long i = g0 + (long)a.n[0] * (g1 + (long)a.n[1] * g2);
-      v = b[i] - g_ax<ND, NOFF>(L, X, i, g0, g1, g2);
-    }
-    r[t] = v;
-  }
-  __syncthreads();
-  const int t = threadIdx.x;
-  if (t < t0 * t1 * t2) {
-    const int j0 = t % t0, q = t / t0, j1 = q % t1, j2 = q / t1;
-    if (J0 + j0 < a.nc[0] && J1 + j1 < a.nc[1] && J2 + j2 < a.nc[2]) {
-      auto at = [&](int a0, int a1, int a2) { return r[a0 + F0 * (a1 + F1 * a2)]; };
-      const double v = mg_restrict_point(a, at, j0, j1, j2);
-      bc[(J0 + j0) + (long)a.nc[0] * ((J1 + j1) + (long)a.nc[1] * (J2 + j2))] = v;
-    }
-  }
-}
-
-// ------------------------------------------------------------------ the tail: one workgroup, vectors in LDS, the
-// coefficient arrays from global memory (14 kTailT doubles for the top tail level alone do not fit LDS)
-
-__device__ __forceinline__ void gtail_sweep(const GLevel &L, int N, double *xs, const double *bs) {
-  auto X = [&](long k) { return xs[k]; };
-  double xn[kTailPts];
-#pragma unroll
-  for (int p = 0; p < kTailPts; ++p) {
-    const int i = threadIdx.x + p * kTailThreads;
-    xn[p] = 0.0;
-    if (i < N) {
-      int i0, i1, i2;
-      mg_split(L.a, i, i0, i1, i2);
-      xn[p] = xs[i] + L.w[i] * (bs[i] - g_ax_rt(L, X, i, i0, i1, i2));
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int p = 0; p < kTailPts; ++p) {
-    const int i = threadIdx.x + p * kTailThreads;
-    if (i < N) xs[i] = xn[p];
-  }
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(kTailThreads) void mg_gtail_kernel(const GTailArg *__restrict__ T,
-                                                                const double *__restrict__ minv,
-                                                                const double *__restrict__ bin,
-                                                                double *__restrict__ xout) {
-  __shared__ double sh[kTailLds];
-  double *const scr = sh + 4 * kTailT;
-  double *const mi = sh + 5 * kTailT;
-  const int nl = T->nlev, steps = T->steps, tid = threadIdx.x;
-  {
-    const MgLevelArg &L = T->lev[0].a;
-    const int N = L.n[0] * L.n[1] * L.n[2];
-    double *bs = sh + 2 * kTailT + T->off[0];
-    for (int i = tid; i < N; i += kTailThreads) bs[i] = bin[i];
-    const MgLevelArg &C = T->lev[nl - 1].a;
-    const int nc = C.n[0] * C.n[1] * C.n[2];
-    for (int i = tid; i < nc * nc; i += kTailThreads) mi[i] = minv[i];
-  }
-  __syncthreads();
-  // down
-  for (int l = 0; l < nl - 1; ++l) {
-    const GLevel &G = T->lev[l];
-    const MgLevelArg L = G.a;
-    const int N = L.n[0] * L.n[1] * L.n[2], Nc = L.nc[0] * L.nc[1] * L.nc[2];
-    double *xs = sh + T->off[l], *bs = sh + 2 * kTailT + T->off[l], *bn = sh + 2 * kTailT + T->off[l + 1];
-    for (int i = tid; i < N; i += kTailThreads) xs[i] = G.w[i] * bs[i];
-    __syncthreads();
-    for (int k = 1; k < steps; ++k) gtail_sweep(G, N, xs, bs);
-    auto X = [&](long k) { return xs[k]; };
-    for (int i = tid; i < N; i += kTailThreads) {
-      int i0, i1, i2;
-      mg_split(L, i, i0, i1, i2);
-      scr[i] = bs[i] - g_ax_rt(G, X, i, i0, i1, i2);
-    }
-    __syncthreads();
-    auto at = [&](int a0, int a1, int a2) {
-      return (a0 < L.n[0] && a1 < L.n[1] && a2 < L.n[2]) ? scr[a0 + L.n[0] * (a1 + L.n[1] * a2)] : 0.0;
-    };
-    for (int j = tid; j < Nc; j += kTailThreads) {
-      const int j0 = j % L.nc[0], q = j / L.nc[0], j1 = q % L.nc[1], j2 = q / L.nc[1];
-      bn[j] = mg_restrict_point(L, at, j0, j1, j2);
-    }
-    __syncthreads();
-  }
-  // the coarsest level: x = A^-1 b with the inverse formed at creation
-  {
-    const MgLevelArg &C = T->lev[nl - 1].a;
-    const int nc = C.n[0] * C.n[1] * C.n[2];
-    double *xs = sh + T->off[nl - 1];
-    const double *bs = sh + 2 * kTailT + T->off[nl - 1];
-    if (tid < nc) {
-      double s = 0.0;
-      for (int j = 0; j < nc; ++j) s += mi[tid * nc + j] * bs[j];
-      xs[tid] = s;
-    }
-    __syncthreads();
-  }
-  // up
-  for (int l = nl - 2; l >= 0; --l) {
-    const GLevel &G = T->lev[l];
-    const MgLevelArg L = G.a;
-    const int N = L.n[0] * L.n[1] * L.n[2];
-    double *xs = sh + T->off[l];
-    const double *bs = sh + 2 * kTailT + T->off[l], *en = sh + T->off[l + 1];
-    auto E = [&](long k) { return en[k]; };
-    for (int i = tid; i < N; i += kTailThreads) {
-      int i0, i1, i2;
-      mg_split(L, i, i0, i1, i2);
-      xs[i] = xs[i] + mg_prolong_point(L, E, i0, i1, i2);
-    }
-    __syncthreads();
-    for (int k = 0; k < steps; ++k) gtail_sweep(G, N, xs, bs);
-  }
-  {
-    const MgLevelArg &L = T->lev[0].a;
-    const int N = L.n[0] * L.n[1] * L.n[2];
-    const double *xs = sh + T->off[0];
-    for (int i = tid; i < N; i += kTailThreads) xout[i] = xs[i];
-  }
 }
 
 }  // namespace
