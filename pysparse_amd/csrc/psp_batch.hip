@@ -452,8 +452,10 @@ int pcg_batch_dev(const psp_op *A, const psp_op *K, int n, int k, double *X, lon
   // Which order the single solve adds in: systems that psp_pcg hands to the one-kernel loop of psp_coop.hip (small, rows of
   // at most 8 entries, neither of the psp_mid.hip loops taking them first) are reduced in THAT loop's order -- a row per
   // thread, wave sums, workgroups of 1024 rows -- which differs from the launch-per-phase order at rounding level.
-  const bool coop_order = fused && maxit >= 1 && single_kernel_loops_enabled() && !mid_applicable(Acsr, n, dinv) &&
-                          !brick_applicable(Acsr, n) && coop_applicable(Acsr, n);
+  // The question is put for rho != 0: the residuals are not formed yet.  A single solve whose first rho IS 0 skips the
+  // psp_mid.hip loops (PcgSkLoop::needs_rho) and may go to psp_coop.hip where this says it would not; that solve ends in
+  // its first iteration (pcg.c:101-104) before anything is added, so the two answers are kept as they are.
+  const bool coop_order = fused && maxit >= 1 && single_kernel_loops_enabled() && pcg_sk_choice(Acsr, n, true) == pcg_coop_loop;
   const int cgrid = (n + kBlock - 1) / kBlock, cwaves = cgrid * (kBlock / 64), cnwg = (n + 1023) / 1024;
   const long pstride = std::max(std::max(spans, w4 ? view.grid : 0), coop_order ? cwaves : 0);
   BatchScratch *bs;

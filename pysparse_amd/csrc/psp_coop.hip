@@ -26,6 +26,10 @@
 // Round 4: the range went from 2^17 to 2^18 rows once the launch was cooperative and checked against the device's capacity:
 // poisson2d(512), 256 workgroups: 21.8 / 19.0 us per PCG / MINRES iteration against 27 / 26 with one launch per phase
 // (tools/coop_range_probe.py, profiles/r4_coop_range.txt).
+//
+// Host side: the launch protocol (zeroed control block and partial sums, history scratch, what is saved / staged /
+// restored around the cooperative launch, kCoopFallback) is sk_run in psp_internal.h, shared with psp_mid.hip; here are
+// the kernels, coop_applicable, and sk_capacity -- the (device, kernel) cache of co-resident workgroups all loops ask.
 #include <algorithm>
 #include <map>
 #include <mutex>
@@ -394,37 +398,6 @@ __global__ __launch_bounds__(kCoopBlock) void minres_coop_kernel(int n, int nwg,
   }
 }
 
-struct CoopMem {
-  // control block and partial sums: the thread's slab (psp_internal.h: no allocation per solve); the history: the
-  // solvers' vector pool
-  CoopCtl *ctl = nullptr;
-  double *part = nullptr, *hist = nullptr;
-  size_t nhist = 0;
-  ~CoopMem() { scratch_put(hist, nhist); }
-  int init(int maxit, bool want_hist) {
-    static_assert(sizeof(CoopCtl) <= kStateBytes && 4 * (size_t)kCoopMaxWg <= kCtlPartDoubles, "state slab");
-    Workspace *ws;
-    PSP_TRY(workspace(&ws));
-    ctl = static_cast<CoopCtl *>(ws->state_dev);
-    part = ws->ctl_part;
-    PSP_HIP(hipMemsetAsync(ctl, 0, sizeof(CoopCtl), stream()));
-    PSP_HIP(hipMemsetAsync(part, 0, sizeof(double) * 4 * kCoopMaxWg, stream()));
-    if (want_hist) {
-      nhist = (size_t)maxit + 2;
-      PSP_TRY(scratch_get(nhist, &hist));
-      PSP_HIP(hipMemsetAsync(hist, 0xff, sizeof(double) * nhist, stream()));
-    }
-    return PSP_OK;
-  }
-  // PSP_OK, kCoopFallback (a grid barrier gave up: the caller restores its vectors and runs the launch-per-phase loop)
-  // or an error
-  int fetch(CoopCtl *out) {
-    PSP_HIP(hipMemcpyAsync(out, ctl, sizeof(CoopCtl), hipMemcpyDeviceToHost, stream()));
-    PSP_HIP(hipStreamSynchronize(stream()));
-    return out->error ? kCoopFallback : PSP_OK;
-  }
-};
-
 // one row per thread, workgroups of 1024 (as few arrivals per barrier as the hardware allows).  Measured (MI355X,
 // profiles/r3_small_solvers.txt): poisson2d(100) 9.0 us per PCG iteration / 6.4 per MINRES iteration against 25 / 19 with
 // one launch per phase; poisson2d(300), 88 workgroups: 12.1 / 9.7 against 22 / 16
@@ -438,49 +411,35 @@ bool coop_enabled() {
   return on;
 }
 
-// How many workgroups of the two kernels the current device can hold AT ONCE (occupancy x compute units; the smaller
-// of the two kernels): a grid barrier among more workgroups than that cannot complete.  A partitioned (CPX) device
-// reports its own CU count here.  Cached per device; 0 when the runtime cannot tell (the single-kernel loops are
-// then not used).  PSP_COOP_CAPACITY (tuning switch) overrides the figure -- the tests use it to force the refusal.
+// The grid must fit both kernels at once (sk_capacity; the smaller of the two).  PSP_COOP_CAPACITY (tuning switch)
+// overrides the figure -- the tests use it to force the refusal.
 int coop_capacity() {
-  static std::mutex mu;
-  static std::map<int, int> cap;
   if (const char *e = tuning_env("PSP_COOP_CAPACITY")) return atoi(e);
-  std::lock_guard<std::mutex> lk(mu);
-  const int dev = current_device();
-  auto it = cap.find(dev);
-  if (it != cap.end()) return it->second;
-  int c = 0;
-  Workspace *w = nullptr;
-  if (workspace(&w) == PSP_OK && w->num_cu > 0) {
-    int a = 0, b = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, (const void *)pcg_coop_kernel, kCoopBlock, 0) == hipSuccess &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (const void *)minres_coop_kernel, kCoopBlock, 0) == hipSuccess)
-      c = std::min(a, b) * w->num_cu;
-    else
-      (void)hipGetLastError();
-  }
-  cap[dev] = c;
-  return c;
-}
-
-// Cooperative launch: the runtime refuses a grid it cannot make co-resident (hipErrorCooperativeLaunchTooLarge)
-// instead of letting its barriers spin.  A refusal is not an error of the solve: kCoopFallback.
-int coop_launch(const void *kernel, int nwg, void **args) {
-  hipError_t e = hipLaunchCooperativeKernel(kernel, dim3(nwg), dim3(kCoopBlock), args, 0, stream());
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return kCoopFallback;
-  }
-  return PSP_OK;
-}
-
-bool coop_force_fail() {  // tests: behave as if a grid barrier had given up (PSP_TUNING=1 PSP_COOP_FAIL=1)
-  const char *e = tuning_env("PSP_COOP_FAIL");
-  return e && atoi(e) == 1;
+  return std::min(sk_capacity((const void *)pcg_coop_kernel, kCoopBlock, 0),
+                  sk_capacity((const void *)minres_coop_kernel, kCoopBlock, 0));
 }
 
 }  // namespace
+
+int sk_capacity(const void *kernel, int block, size_t lds) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void *>, int> cap;
+  std::lock_guard<std::mutex> lk(mu);
+  const auto key = std::make_pair(current_device(), kernel);
+  auto it = cap.find(key);
+  if (it == cap.end()) {
+    int c = 0, per = 0;
+    Workspace *w = nullptr;
+    if ((lds == 0 || hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) &&
+        workspace(&w) == PSP_OK && w->num_cu > 0 &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, block, lds) == hipSuccess)
+      c = per * w->num_cu;
+    else
+      (void)hipGetLastError();
+    it = cap.emplace(key, c).first;
+  }
+  return it->second;
+}
 
 // the operator as plain CSR arrays on this device, small enough for the single-kernel loops, and the grid fits the
 // device at once?
@@ -490,88 +449,36 @@ bool coop_applicable(const psp_csr *A, int n) {
          coop_grid(n) <= std::min(kCoopMaxWg, coop_capacity());
 }
 
-// On kCoopFallback x and r are what they were on entry and the caller continues with its other loops: the kernel leaves
-// its x in a staging vector (p, which the single-kernel loop does not use otherwise) that is copied over x only after a
-// launch in which no workgroup gave up -- a time-out that strikes in the last iteration lets some workgroups store and
-// others not (round-4 advisor finding) -- and r is restored from the copy kept in q.
+// The launch protocol -- what is saved, staged and restored so that kCoopFallback leaves x, r and y as on entry -- is sk_run
+// (psp_internal.h).
 int pcg_coop_loop(const psp_csr *A, const double *dinv, int n, double *x, double *r, double *p, double *q, double n2b,
                   double tolb, double normr0, double rho0, int maxit, int *info, int *iter, double *relres,
                   double *hist) {
-  CoopMem m;
-  PSP_TRY(m.init(maxit, hist != nullptr));
   int nwg = coop_grid(n);
-  PSP_HIP(hipMemcpyAsync(q, r, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
   const int *ind = A->ind, *col = A->col;
   const double *val = A->val;
   const double *xin = x;
-  void *args[] = {&n, &nwg, &ind, &col, &val, &dinv, &xin, &p, &r, &n2b, &tolb, &normr0, &rho0, &maxit, &m.ctl, &m.part, &m.hist};
-  int rc = coop_force_fail() ? kCoopFallback : coop_launch((const void *)pcg_coop_kernel, nwg, args);
-  CoopCtl c;
-  if (rc == PSP_OK) rc = m.fetch(&c);
-  if (rc == kCoopFallback)
-    PSP_HIP(hipMemcpyAsync(r, q, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  if (rc != PSP_OK) return rc;
-  PSP_HIP(hipMemcpyAsync(x, p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  PSP_HIP(hipStreamSynchronize(stream()));  // x is final when the call returns
-  *info = c.info;
-  *iter = c.iter;
-  *relres = c.relres;
-  if (hist) {
-    const int cnt = std::min(c.iter, maxit);
-    if (cnt >= 1) {
-      std::vector<double> h((size_t)cnt);
-      PSP_HIP(hipMemcpy(h.data(), m.hist + 1, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-      for (int i = 0; i < cnt; ++i)
-        if (h[i] == h[i]) hist[1 + i] = h[i];  // the iteration that broke down wrote nothing
-    }
-  }
-  return PSP_OK;
+  CoopCtl *ctl;
+  double *part, *hd;
+  void *args[] = {&n, &nwg, &ind, &col, &val, &dinv, &xin, &p, &r, &n2b, &tolb, &normr0, &rho0, &maxit, &ctl, &part, &hd};
+  const SkLaunch<CoopCtl> L{(const void *)pcg_coop_kernel, nwg, kCoopBlock, 0, args, &ctl, &part, &hd};
+  return sk_run<CoopCtl, 4 * kCoopMaxWg>(L, sk_pcg_vectors(n, x, r, p, q), maxit, info, iter, relres, hist);
 }
 
-// On kCoopFallback x, v_hat and y are what they were on entry (x: staged in w, as in pcg_coop_loop; y is restored from the
-// copy kept in av).
-int minres_coop_loop(const psp_csr *A, const double *dinv, int n, double *x, double *v_hat, double *v_hat_old,
-                     double *y, double *w, double *w_old, double *v, double *av, double norm_r0, double beta0,
-                     double errtol, int it_max, int *info, int *iter, double *relres, double *hist) {
-  CoopMem m;
-  PSP_TRY(m.init(it_max, hist != nullptr));
+int minres_coop_loop(const psp_csr *A, const double *dinv, int n, double *x, double *v_hat, double *y, double *w, double *v,
+                     double *av, double norm_r0, double beta0, double errtol, int it_max, int *info, int *iter,
+                     double *relres, double *hist) {
   int nwg = coop_grid(n);
-  (void)v_hat_old;
-  (void)w_old;
-  double *yv = y;  // the vector that crosses workgroups: K v_hat, or v_hat itself without a preconditioner
-  if (!dinv) {
-    yv = v;
-    PSP_HIP(hipMemcpyAsync(yv, v_hat, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  } else {
-    PSP_HIP(hipMemcpyAsync(av, y, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  }
+  double *yv;
+  const SkVectors V = sk_minres_vectors(dinv, n, x, v_hat, y, w, v, av, &yv);
   const int *ind = A->ind, *col = A->col;
   const double *val = A->val;
   const double *vh = v_hat, *xin = x;
-  void *args[] = {&n, &nwg, &ind, &col, &val, &dinv, &xin, &w, &vh, &yv, &norm_r0, &beta0, &errtol, &it_max, &m.ctl, &m.part, &m.hist};
-  int rc = coop_force_fail() ? kCoopFallback : coop_launch((const void *)minres_coop_kernel, nwg, args);
-  CoopCtl c;
-  if (rc == PSP_OK) rc = m.fetch(&c);
-  if (rc == kCoopFallback) {
-    if (dinv) PSP_HIP(hipMemcpyAsync(y, av, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-    PSP_HIP(hipMemsetAsync(w, 0, sizeof(double) * (size_t)n, stream()));  // the staging vector is the caller's w = 0 again
-  }
-  if (rc != PSP_OK) return rc;
-  PSP_HIP(hipMemcpyAsync(x, w, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  PSP_HIP(hipStreamSynchronize(stream()));  // x is final when the call returns
-  *info = c.info;
-  *iter = c.iter;
-  if (c.info == 0 || c.info == -1) *relres = c.relres;
-  if (hist) {
-    const int cnt = std::min(c.iter, it_max);
-    if (cnt >= 1) {
-      std::vector<double> h((size_t)cnt);
-      PSP_HIP(hipMemcpy(h.data(), m.hist + 1, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-      for (int i = 0; i < cnt; ++i)
-        if (h[i] == h[i]) hist[1 + i] = h[i];
-    }
-  }
-  return PSP_OK;
+  CoopCtl *ctl;
+  double *part, *hd;
+  void *args[] = {&n, &nwg, &ind, &col, &val, &dinv, &xin, &w, &vh, &yv, &norm_r0, &beta0, &errtol, &it_max, &ctl, &part, &hd};
+  const SkLaunch<CoopCtl> L{(const void *)minres_coop_kernel, nwg, kCoopBlock, 0, args, &ctl, &part, &hd};
+  return sk_run<CoopCtl, 4 * kCoopMaxWg>(L, V, it_max, info, iter, relres, hist);
 }
 
 }  // namespace psp

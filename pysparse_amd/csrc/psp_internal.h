@@ -2,12 +2,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <initializer_list>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "pysparse_hip.h"
 
@@ -620,35 +624,127 @@ struct W4View {
   int stripe, grid;            // XCD stripe and grid of the launch-per-phase product (order of its dot partials)
 };
 int csr_w4_view(const psp_csr *A, W4View *out, int *available);
-// psp_mid.hip: the whole PCG loop as one cooperative kernel for mid-size offset-structured systems (vectors in
-// registers, the direction vector exchanged through LDS); kCoopFallback as for the small-system loops
-bool mid_applicable(const psp_csr *A, int n, const double *dinv);
-int pcg_mid_loop(const psp_csr *A, const double *dinv, int n, double *x, double *r, double *p, double *q, double n2b,
-                 double tolb, double normr0, double rho0, int maxit, int *info, int *iter, double *relres, double *hist);
-// psp_mid.hip: the same for the 7-offset operators of 3-D grids, the points dealt out in bricks (iterates agree with the
-// launch-per-phase loops' to rounding)
-bool brick_applicable(const psp_csr *A, int n);
-int pcg_brick_loop(const psp_csr *A, const double *dinv, int n, double *x, double *r, double *p, double *q, double n2b,
-                   double tolb, double normr0, double rho0, int maxit, int *info, int *iter, double *relres, double *hist);
-bool brick_minres_applicable(const psp_csr *A, int n);
-int minres_brick_loop(const psp_csr *A, const double *dinv, int n, double *x, double *v_hat, double *v_hat_old, double *y,
-                      double *w, double *w_old, double *v, double *av, double norm_r0, double beta0, double errtol, int it_max,
-                      int *info, int *iter, double *relres, double *hist);
-bool mid_minres_applicable(const psp_csr *A, int n);
-int minres_mid_loop(const psp_csr *A, const double *dinv, int n, double *x, double *v_hat, double *v_hat_old, double *y,
-                    double *w, double *w_old, double *v, double *av, double norm_r0, double beta0, double errtol, int it_max,
-                    int *info, int *iter, double *relres, double *hist);
-// psp_coop.hip: the whole loop as one kernel for small systems (grid barriers instead of dependent launches).
-// The two loops return kCoopFallback (not an error; nothing was changed) when the cooperative launch is refused or a
-// grid barrier gives up: the caller then runs its launch-per-phase loop from the same vectors.
+// The single-kernel loops (psp_coop.hip: one row per thread, small systems; psp_mid.hip: contiguous row blocks of mid-size
+// offset-structured systems, and the 7-offset operators of 3-D grids dealt out in bricks): a whole PCG / MINRES solve as
+// one cooperative kernel.  A loop returns kCoopFallback (not an error) when its plan declines, the cooperative launch is
+// refused or a grid barrier gives up: x and the caller's vectors are then what they were on entry and the caller goes on
+// with its next loop.  The launch protocol that guarantees this is sk_run below.
 constexpr int kCoopFallback = 1;
+using PcgSkFn = int(const psp_csr *A, const double *dinv, int n, double *x, double *r, double *p, double *q, double n2b,
+                     double tolb, double normr0, double rho0, int maxit, int *info, int *iter, double *relres, double *hist);
+using MinresSkFn = int(const psp_csr *A, const double *dinv, int n, double *x, double *v_hat, double *y, double *w, double *v,
+                        double *av, double norm_r0, double beta0, double errtol, int it_max, int *info, int *iter,
+                        double *relres, double *hist);
+bool mid_applicable(const psp_csr *A, int n);
+bool mid_minres_applicable(const psp_csr *A, int n);
+bool brick_applicable(const psp_csr *A, int n);
+bool brick_minres_applicable(const psp_csr *A, int n);
 bool coop_applicable(const psp_csr *A, int n);
-int pcg_coop_loop(const psp_csr *A, const double *dinv, int n, double *x, double *r, double *p, double *q, double n2b,
-                  double tolb, double normr0, double rho0, int maxit, int *info, int *iter, double *relres,
-                  double *hist);
-int minres_coop_loop(const psp_csr *A, const double *dinv, int n, double *x, double *v_hat, double *v_hat_old,
-                     double *y, double *w, double *w_old, double *v, double *av, double norm_r0, double beta0,
-                     double errtol, int it_max, int *info, int *iter, double *relres, double *hist);
+PcgSkFn pcg_mid_loop, pcg_brick_loop, pcg_coop_loop;
+MinresSkFn minres_mid_loop, minres_brick_loop, minres_coop_loop;
+// psp_solvers.hip states the order in which a solve tries them (mid, brick, coop) once; this is the run function of the
+// first one that takes a PCG solve on this operator (nullptr: none).  rho_nonzero: see PcgSkLoop there.
+PcgSkFn *pcg_sk_choice(const psp_csr *A, int n, bool rho_nonzero);
+// psp_coop.hip: how many workgroups of `kernel` (block threads, lds bytes of dynamic LDS) the current device holds AT ONCE
+// (occupancy x compute units; a partitioned device reports its own CU count) -- a grid barrier among more cannot
+// complete.  Cached per (device, kernel); 0 when the runtime cannot tell (the single-kernel loops are then not used).
+// What PSP_COOP_CAPACITY (tuning switch) does with the figure is the callers' business.
+int sk_capacity(const void *kernel, int block, size_t lds);
+
+// ---- the launch protocol of the six loops, once.
+// SkLaunch: the kernel and where its packed arguments want the three buffers sk_run owns.
+template <class Ctl>
+struct SkLaunch {
+  const void *kernel;
+  int nwg, block;
+  size_t lds;
+  void **args;
+  Ctl **ctl;                  // <- the control block (the thread's state slab, zeroed)
+  double **part, **hist_dev;  // <- the partial sums (the slab, zeroed) and the history (vector pool, NaN; nullptr without)
+  std::atomic<long long> *solves = nullptr, *fallbacks = nullptr;  // psp_debug_*_count
+};
+// SkVectors: which vector the kernel overwrites and where it leaves x.
+struct SkVectors {
+  int n;
+  double *x, *stage;       // the kernel's x: copied over the caller's only after a launch in which NO workgroup gave up -- a
+                           // time-out in the last iteration lets some workgroups store and others not (round 4)
+  double *copy_src, *copy_dst;  // copied before the launch ...
+  bool restore;                 // ... and back on a fallback
+  double *zero;            // set to zero again on a fallback (nullptr: nothing)
+  bool relres_always;      // false: relres only with info 0 / -1, as the reference leaves it untouched otherwise
+};
+// PCG: r is saved in q, x staged in p (neither is used by the single-kernel loops otherwise)
+inline SkVectors sk_pcg_vectors(int n, double *x, double *r, double *p, double *q) { return {n, x, p, r, q, true, nullptr, true}; }
+// MINRES: *yv, the vector that crosses workgroups, is y = K v_hat (saved in av) or, without a preconditioner, a copy of
+// v_hat in v; x is staged in w, which is the caller's w = 0 again after a fallback
+inline SkVectors sk_minres_vectors(const double *dinv, int n, double *x, double *v_hat, double *y, double *w, double *v,
+                                   double *av, double **yv) {
+  *yv = dinv ? y : v;
+  if (dinv) return {n, x, w, y, av, true, w, false};
+  return {n, x, w, v_hat, v, false, w, false};
+}
+// kPart: partial-sum doubles to zero; Ctl has error / info / iter / relres.  PSP_OK: the stream is synchronised, x final.
+// kCoopFallback: info / iter / relres / hist are untouched, the restoring copies are enqueued.
+template <class Ctl, size_t kPart>
+int sk_run(const SkLaunch<Ctl> &L, const SkVectors &V, int maxit, int *info, int *iter, double *relres, double *hist) {
+  static_assert(sizeof(Ctl) <= kStateBytes && kPart <= kCtlPartDoubles, "state slab");
+  const size_t bytes = sizeof(double) * (size_t)V.n;
+  Workspace *ws;
+  PSP_TRY(workspace(&ws));
+  struct Hist {
+    double *dev = nullptr;
+    size_t n = 0;
+    ~Hist() { scratch_put(dev, n); }
+  } h;
+  Ctl *ctl = static_cast<Ctl *>(ws->state_dev);
+  PSP_HIP(hipMemsetAsync(ctl, 0, sizeof(Ctl), stream()));
+  PSP_HIP(hipMemsetAsync(ws->ctl_part, 0, sizeof(double) * kPart, stream()));
+  if (hist) {
+    h.n = (size_t)maxit + 2;
+    PSP_TRY(scratch_get(h.n, &h.dev));
+    PSP_HIP(hipMemsetAsync(h.dev, 0xff, sizeof(double) * h.n, stream()));
+  }
+  *L.ctl = ctl;
+  *L.part = ws->ctl_part;
+  *L.hist_dev = h.dev;
+  PSP_HIP(hipMemcpyAsync(V.copy_dst, V.copy_src, bytes, hipMemcpyDeviceToDevice, stream()));
+  int rc = PSP_OK;
+  const char *ff = tuning_env("PSP_COOP_FAIL");  // tests: behave as if a grid barrier had given up
+  if (ff && atoi(ff) == 1) {
+    rc = kCoopFallback;
+  } else if (hipLaunchCooperativeKernel(L.kernel, dim3(L.nwg), dim3(L.block), L.args, (unsigned)L.lds, stream()) != hipSuccess) {
+    (void)hipGetLastError();  // the runtime refuses a grid it cannot make co-resident instead of letting its barriers spin
+    rc = kCoopFallback;
+  }
+  Ctl c;
+  if (rc == PSP_OK) {
+    PSP_HIP(hipMemcpyAsync(&c, ctl, sizeof(Ctl), hipMemcpyDeviceToHost, stream()));
+    PSP_HIP(hipStreamSynchronize(stream()));
+    if (c.error) rc = kCoopFallback;
+  }
+  if (rc == kCoopFallback) {
+    if (L.fallbacks) L.fallbacks->fetch_add(1);
+    if (V.restore) PSP_HIP(hipMemcpyAsync(V.copy_src, V.copy_dst, bytes, hipMemcpyDeviceToDevice, stream()));
+    if (V.zero) PSP_HIP(hipMemsetAsync(V.zero, 0, bytes, stream()));
+  }
+  if (rc != PSP_OK) return rc;
+  if (L.solves) L.solves->fetch_add(1);
+  PSP_HIP(hipMemcpyAsync(V.x, V.stage, bytes, hipMemcpyDeviceToDevice, stream()));
+  PSP_HIP(hipStreamSynchronize(stream()));  // x is final when the call returns
+  *info = c.info;
+  *iter = c.iter;
+  if (V.relres_always || c.info == 0 || c.info == -1) *relres = c.relres;
+  if (hist) {
+    const int cnt = std::min(c.iter, maxit);
+    if (cnt >= 1) {
+      std::vector<double> hh((size_t)cnt);
+      PSP_HIP(hipMemcpy(hh.data(), h.dev + 1, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
+      for (int i = 0; i < cnt; ++i)
+        if (hh[i] == hh[i]) hist[1 + i] = hh[i];  // the iteration that broke down wrote nothing
+    }
+  }
+  return PSP_OK;
+}
 // psp_cpu.hip: the host loops behind the entry points when PSP_DEVICE=cpu
 namespace cpu {
 int csr_create(int nrows, int ncols, int nnz, const int *ind, const int *col, const double *val, psp_csr **out);

@@ -2,8 +2,10 @@
 //
 // Contents: pcg_mid_kernel / minres_mid_kernel (contiguous row blocks: 2-D grids and slim 3-D ones, up to 9 offsets, bit-exact
 // with the launch-per-phase loops; CV = constant-coefficient forms), pcg_brick_kernel / minres_brick_kernel (the 7-offset
-// operators of 3-D grids, the points dealt out in bricks; oracle parity), their plans and host loops.  What follows describes
-// the row-block PCG kernel; the others say where they differ.
+// operators of 3-D grids, the points dealt out in bricks; oracle parity), their plans and host loops.  The host loops only
+// plan and pack arguments: the launch protocol (what is zeroed, saved, staged and restored around the cooperative launch,
+// kCoopFallback) is sk_run in psp_internal.h, shared with psp_coop.hip.  What follows describes the row-block PCG kernel; the
+// others say where they differ.
 //
 // Between 2^18 and 2^20 unknowns an iteration of the launch-per-phase loops (psp_solvers.hip) is five kernels that each
 // sit on the ~5 us floor of a dependent launch: 47 us per PCG iteration at 1024^2 for 128 MB of traffic that the memory
@@ -34,8 +36,7 @@
 // Reference loop: pysparse/itsolvers/src/pcg.c:91-166.
 #include <algorithm>
 #include <atomic>
-#include <map>
-#include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "psp_internal.h"
@@ -1492,24 +1493,28 @@ int mid_block_threads(int rows, int no, bool cv) {
 
 // the grid must be resident at once: one workgroup per CU with this much LDS
 bool mid_capacity_ok(const MidPlan *P) {
-  static std::mutex mu;
-  static std::map<std::pair<int, const void *>, int> cap;  // (device, kernel) -> workgroups the device holds at once
-  std::lock_guard<std::mutex> lk(mu);
   if (const char *e = tuning_env("PSP_COOP_CAPACITY")) return P->nwg <= atoi(e);
-  const auto key = std::make_pair(current_device(), P->kernel);
-  auto it = cap.find(key);
-  if (it == cap.end()) {
-    int c = 0, per = 0;
-    Workspace *w = nullptr;
-    if (hipFuncSetAttribute(P->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMidMaxLds) == hipSuccess &&
-        workspace(&w) == PSP_OK && w->num_cu > 0 &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, P->kernel, P->blk, kMidMaxLds) == hipSuccess)
-      c = per * w->num_cu;
-    else
-      (void)hipGetLastError();
-    it = cap.emplace(key, c).first;
+  return P->nwg <= sk_capacity(P->kernel, P->blk, kMidMaxLds);
+}
+
+// The operator and Jacobi fields that the four argument structs share (the brick structs have no offs / np_w4 / stripe /
+// nspans: their reductions go by workgroup).  pre: 0 no preconditioner, 1 jacobi (dinv array), 2 jacobi with a constant
+// diagonal (dc).  cval: read by the constant-coefficient kernels only.
+template <class Args>
+void fill_operator(Args &a, const W4View &w4, const double *dinv, int n) {
+  a.n = n;
+  for (size_t i = 0; i < sizeof(a.cval) / sizeof(a.cval[0]); ++i) a.cval[i] = w4.constv ? w4.cval[i] : 0.0;
+  a.valT = w4.valT;
+  a.mask = w4.mask;
+  a.dinv = dinv;
+  a.dc = 0.0;
+  a.pre = !dinv ? 0 : (dinv_constant(dinv, n, &a.dc) ? 2 : 1);
+  if constexpr (std::is_same<Args, MidArgs>::value || std::is_same<Args, MidMinresArgs>::value) {
+    for (int i = 0; i < 12; ++i) a.offs[i] = w4.offs[i];
+    a.np_w4 = w4.grid;
+    a.stripe = w4.stripe;
+    a.nspans = (n + kMidSpan - 1) / kMidSpan;
   }
-  return P->nwg <= it->second;
 }
 
 // the plan for this operator, or false: no index-free layout of <= 9 offsets, too many rows, a halo that does not fit
@@ -1562,8 +1567,7 @@ bool mid_plan(const psp_csr *A, int n, MidPlan *P, bool minres = false) {
 
 }  // namespace
 
-bool mid_applicable(const psp_csr *A, int n, const double *dinv) {
-  (void)dinv;
+bool mid_applicable(const psp_csr *A, int n) {
   MidPlan P;
   return mid_plan(A, n, &P);
 }
@@ -1573,143 +1577,38 @@ bool mid_minres_applicable(const psp_csr *A, int n) {
   return mid_plan(A, n, &P, true);
 }
 
-// On kCoopFallback x, v_hat and y are what they were on entry (x: staged in w, which is zeroed again; y -- whose
-// block-boundary rows the kernel overwrites -- restored from the copy kept in av); as minres_coop_loop (psp_coop.hip).
-int minres_mid_loop(const psp_csr *A, const double *dinv, int n, double *x, double *v_hat, double *v_hat_old, double *y,
-                    double *w, double *w_old, double *v, double *av, double norm_r0, double beta0, double errtol, int it_max,
-                    int *info, int *iter, double *relres, double *hist) {
+// The launch protocol of the four loops here -- what is saved, staged and restored so that kCoopFallback leaves x, r and y
+// (whose block-boundary rows the kernels overwrite) as on entry -- is sk_run (psp_internal.h).
+int minres_mid_loop(const psp_csr *A, const double *dinv, int n, double *x, double *v_hat, double *y, double *w, double *v,
+                    double *av, double norm_r0, double beta0, double errtol, int it_max, int *info, int *iter,
+                    double *relres, double *hist) {
   MidPlan P;
   if (!mid_plan(A, n, &P, true)) return kCoopFallback;
-  (void)v_hat_old;
-  (void)w_old;
-  // control block and partial sums: the thread's slab (psp_internal.h); the history: the solvers' vector pool
-  static_assert(sizeof(MidCtl) <= kStateBytes && 4 * (size_t)kMidMaxSpans <= kCtlPartDoubles, "state slab");
-  Workspace *ws;
-  PSP_TRY(workspace(&ws));
-  struct Mem {
-    MidCtl *ctl = nullptr;
-    double *part = nullptr, *hist = nullptr;
-    size_t nhist = 0;
-    ~Mem() { scratch_put(hist, nhist); }
-  } m;
-  m.ctl = static_cast<MidCtl *>(ws->state_dev);
-  m.part = ws->ctl_part;
-  PSP_HIP(hipMemsetAsync(m.ctl, 0, sizeof(MidCtl), stream()));
-  PSP_HIP(hipMemsetAsync(m.part, 0, sizeof(double) * 2 * kMidMaxSpans, stream()));
-  if (hist) {
-    m.nhist = (size_t)it_max + 2;
-    PSP_TRY(scratch_get(m.nhist, &m.hist));
-    PSP_HIP(hipMemsetAsync(m.hist, 0xff, sizeof(double) * m.nhist, stream()));
-  }
-  double *yv = y;  // the vector that crosses workgroups: K v_hat, or v_hat itself without a preconditioner
-  if (!dinv) {
-    yv = v;
-    PSP_HIP(hipMemcpyAsync(yv, v_hat, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  } else {
-    PSP_HIP(hipMemcpyAsync(av, y, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  }
   MidMinresArgs a;
-  a.n = n;
+  const SkVectors V = sk_minres_vectors(dinv, n, x, v_hat, y, w, v, av, &a.yv);
+  fill_operator(a, P.w4, dinv, n);
   a.nwg = P.nwg;
   a.H = P.H;
-  for (int i = 0; i < 12; ++i) a.offs[i] = P.w4.offs[i];
-  for (int i = 0; i < 12; ++i) a.cval[i] = P.w4.constv ? P.w4.cval[i] : 0.0;
-  a.valT = P.w4.valT;
-  a.mask = P.w4.mask;
-  a.dinv = dinv;
-  a.dc = 0.0;
-  a.pre = !dinv ? 0 : (dinv_constant(dinv, n, &a.dc) ? 2 : 1);
   a.x = x;
   a.xout = w;
   a.v_hat = v_hat;
-  a.yv = yv;
   a.norm_r0 = norm_r0;
   a.beta0 = beta0;
   a.errtol = errtol;
   a.it_max = it_max;
-  a.ctl = m.ctl;
-  a.part = m.part;
-  a.hist = m.hist;
-  a.np_w4 = P.w4.grid;
-  a.stripe = P.w4.stripe;
-  a.nspans = (n + kMidSpan - 1) / kMidSpan;
   void *args[] = {&a};
-  int rc = PSP_OK;
-  const char *ff = tuning_env("PSP_COOP_FAIL");
-  if (ff && atoi(ff) == 1) {
-    rc = kCoopFallback;
-  } else if (hipLaunchCooperativeKernel(P.kernel, dim3(P.nwg), dim3(P.blk), args, (unsigned)P.lds, stream()) != hipSuccess) {
-    (void)hipGetLastError();
-    rc = kCoopFallback;
-  }
-  MidCtl c;
-  if (rc == PSP_OK) {
-    PSP_HIP(hipMemcpyAsync(&c, m.ctl, sizeof(MidCtl), hipMemcpyDeviceToHost, stream()));
-    PSP_HIP(hipStreamSynchronize(stream()));
-    if (c.error) rc = kCoopFallback;
-  }
-  if (rc == kCoopFallback) {
-    g_mid_fallbacks.fetch_add(1);
-    if (dinv) PSP_HIP(hipMemcpyAsync(y, av, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-    PSP_HIP(hipMemsetAsync(w, 0, sizeof(double) * (size_t)n, stream()));
-  }
-  if (rc != PSP_OK) return rc;
-  g_mid_solves.fetch_add(1);
-  PSP_HIP(hipMemcpyAsync(x, w, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  PSP_HIP(hipStreamSynchronize(stream()));
-  *info = c.info;
-  *iter = c.iter;
-  if (c.info == 0 || c.info == -1) *relres = c.relres;
-  if (hist) {
-    const int cnt = std::min(c.iter, it_max);
-    if (cnt >= 1) {
-      std::vector<double> h((size_t)cnt);
-      PSP_HIP(hipMemcpy(h.data(), m.hist + 1, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-      for (int i = 0; i < cnt; ++i)
-        if (h[i] == h[i]) hist[1 + i] = h[i];
-    }
-  }
-  return PSP_OK;
+  const SkLaunch<MidCtl> L{P.kernel, P.nwg, P.blk, P.lds, args, &a.ctl, &a.part, &a.hist, &g_mid_solves, &g_mid_fallbacks};
+  return sk_run<MidCtl, 2 * kMidMaxSpans>(L, V, it_max, info, iter, relres, hist);
 }
 
-// On kCoopFallback x and r are what they were on entry: the kernel leaves its x in a staging vector (p) that is copied
-// over x only after a launch in which no workgroup gave up; r (whose block-boundary rows the kernel overwrites) is
-// restored from the copy kept in q.
 int pcg_mid_loop(const psp_csr *A, const double *dinv, int n, double *x, double *r, double *p, double *q, double n2b,
                  double tolb, double normr0, double rho0, int maxit, int *info, int *iter, double *relres, double *hist) {
   MidPlan P;
   if (!mid_plan(A, n, &P)) return kCoopFallback;
-  // control block and partial sums: the thread's slab (psp_internal.h); the history: the solvers' vector pool
-  static_assert(sizeof(MidCtl) <= kStateBytes && 4 * (size_t)kMidMaxSpans <= kCtlPartDoubles, "state slab");
-  Workspace *ws;
-  PSP_TRY(workspace(&ws));
-  struct Mem {
-    MidCtl *ctl = nullptr;
-    double *part = nullptr, *hist = nullptr;
-    size_t nhist = 0;
-    ~Mem() { scratch_put(hist, nhist); }
-  } m;
-  m.ctl = static_cast<MidCtl *>(ws->state_dev);
-  m.part = ws->ctl_part;
-  PSP_HIP(hipMemsetAsync(m.ctl, 0, sizeof(MidCtl), stream()));
-  PSP_HIP(hipMemsetAsync(m.part, 0, sizeof(double) * 4 * kMidMaxSpans, stream()));
-  if (hist) {
-    m.nhist = (size_t)maxit + 2;
-    PSP_TRY(scratch_get(m.nhist, &m.hist));
-    PSP_HIP(hipMemsetAsync(m.hist, 0xff, sizeof(double) * m.nhist, stream()));
-  }
-  PSP_HIP(hipMemcpyAsync(q, r, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
   MidArgs a;
-  a.n = n;
+  fill_operator(a, P.w4, dinv, n);
   a.nwg = P.nwg;
   a.H = P.H;
-  for (int i = 0; i < 12; ++i) a.offs[i] = P.w4.offs[i];
-  for (int i = 0; i < 12; ++i) a.cval[i] = P.w4.constv ? P.w4.cval[i] : 0.0;
-  a.valT = P.w4.valT;
-  a.mask = P.w4.mask;
-  a.dinv = dinv;
-  a.dc = 0.0;
-  a.pre = !dinv ? 0 : (dinv_constant(dinv, n, &a.dc) ? 2 : 1);
   a.x = x;
   a.xout = p;
   a.r = r;
@@ -1718,12 +1617,6 @@ int pcg_mid_loop(const psp_csr *A, const double *dinv, int n, double *x, double 
   a.normr0 = normr0;
   a.rho0 = rho0;
   a.maxit = maxit;
-  a.ctl = m.ctl;
-  a.part = m.part;
-  a.hist = m.hist;
-  a.np_w4 = P.w4.grid;
-  a.stripe = P.w4.stripe;
-  a.nspans = (n + kMidSpan - 1) / kMidSpan;
   a.stamps = nullptr;
   long long *stamps_dev = nullptr;
   const char *se = tuning_env("PSP_MID_STAMPS");  // workgroup to stamp
@@ -1735,20 +1628,8 @@ int pcg_mid_loop(const psp_csr *A, const double *dinv, int n, double *x, double 
     a.stamps = stamps_dev;
   }
   void *args[] = {&a};
-  int rc = PSP_OK;
-  const char *ff = tuning_env("PSP_COOP_FAIL");
-  if (ff && atoi(ff) == 1) {
-    rc = kCoopFallback;
-  } else if (hipLaunchCooperativeKernel(P.kernel, dim3(P.nwg), dim3(P.blk), args, (unsigned)P.lds, stream()) != hipSuccess) {
-    (void)hipGetLastError();
-    rc = kCoopFallback;
-  }
-  MidCtl c;
-  if (rc == PSP_OK) {
-    PSP_HIP(hipMemcpyAsync(&c, m.ctl, sizeof(MidCtl), hipMemcpyDeviceToHost, stream()));
-    PSP_HIP(hipStreamSynchronize(stream()));
-    if (c.error) rc = kCoopFallback;
-  }
+  const SkLaunch<MidCtl> L{P.kernel, P.nwg, P.blk, P.lds, args, &a.ctl, &a.part, &a.hist, &g_mid_solves, &g_mid_fallbacks};
+  const int rc = sk_run<MidCtl, 4 * kMidMaxSpans>(L, sk_pcg_vectors(n, x, r, p, q), maxit, info, iter, relres, hist);
   if (stamps_dev) {
     long long st[8 + 16 * 8];
     (void)hipMemcpy(st, stamps_dev, sizeof(st), hipMemcpyDeviceToHost);
@@ -1762,27 +1643,7 @@ int pcg_mid_loop(const psp_csr *A, const double *dinv, int n, double *x, double 
       fprintf(stderr, " %5lld | total %lld\n", q1[0] - q0[7], q1[0] - q0[0]);
     }
   }
-  if (rc == kCoopFallback) {
-    g_mid_fallbacks.fetch_add(1);
-    PSP_HIP(hipMemcpyAsync(r, q, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  }
-  if (rc != PSP_OK) return rc;
-  g_mid_solves.fetch_add(1);
-  PSP_HIP(hipMemcpyAsync(x, p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  PSP_HIP(hipStreamSynchronize(stream()));  // x is final when the call returns, as after the other loops
-  *info = c.info;
-  *iter = c.iter;
-  *relres = c.relres;
-  if (hist) {
-    const int cnt = std::min(c.iter, maxit);
-    if (cnt >= 1) {
-      std::vector<double> h((size_t)cnt);
-      PSP_HIP(hipMemcpy(h.data(), m.hist + 1, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-      for (int i = 0; i < cnt; ++i)
-        if (h[i] == h[i]) hist[1 + i] = h[i];  // the iteration that broke down wrote nothing
-    }
-  }
-  return PSP_OK;
+  return rc;
 }
 
 // ---- 3-D grid operators in bricks (pcg_brick_kernel)
@@ -1829,30 +1690,8 @@ bool brick_plan(const psp_csr *A, int n, BrickPlan *P, bool minres = false) {
   if ((long)nx * ny * nz != n) return false;
   P->kernel = kernel = minres ? (P->w4.constv ? (const void *)minres_brick_kernel<true> : (const void *)minres_brick_kernel<false>)
                               : (P->w4.constv ? (const void *)pcg_brick_kernel<true> : (const void *)pcg_brick_kernel<false>);
-  static std::mutex mu;
-  static std::map<std::pair<int, const void *>, int> cap;  // (device, kernel) -> workgroups the device holds at once
-  int capacity;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (const char *e = tuning_env("PSP_COOP_CAPACITY")) {
-      capacity = atoi(e);
-    } else {
-      const auto key = std::make_pair(current_device(), kernel);
-      auto it = cap.find(key);
-      if (it == cap.end()) {
-        int c = 0, per = 0;
-        Workspace *w = nullptr;
-        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMidMaxLds) == hipSuccess &&
-            workspace(&w) == PSP_OK && w->num_cu > 0 &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, kBrickBlock, kMidMaxLds) == hipSuccess)
-          c = per * w->num_cu;
-        else
-          (void)hipGetLastError();
-        it = cap.emplace(key, c).first;
-      }
-      capacity = it->second;
-    }
-  }
+  const char *ce = tuning_env("PSP_COOP_CAPACITY");
+  int capacity = ce ? atoi(ce) : sk_capacity(kernel, kBrickBlock, kMidMaxLds);
   capacity = std::min(capacity, kMidMaxWg);
   // bricks: as many as the device holds, as close to cubes as the grid allows -- least work (points + halo cells) per
   // workgroup among the decompositions that fit
@@ -1878,6 +1717,14 @@ bool brick_plan(const psp_csr *A, int n, BrickPlan *P, bool minres = false) {
   return true;
 }
 
+template <class Args>
+void fill_bricks(Args &a, const BrickPlan &P) {
+  a.nwg = P.nwg;
+  a.nx = P.nx; a.ny = P.ny; a.nz = P.nz;
+  a.bx = P.bx; a.by = P.by; a.bz = P.bz;
+  a.cx = P.cx; a.cy = P.cy;
+}
+
 }  // namespace
 
 bool brick_applicable(const psp_csr *A, int n) {
@@ -1890,132 +1737,34 @@ bool brick_minres_applicable(const psp_csr *A, int n) {
   return brick_plan(A, n, &P, true);
 }
 
-// as minres_mid_loop: on kCoopFallback x, v_hat and y are what they were on entry
-int minres_brick_loop(const psp_csr *A, const double *dinv, int n, double *x, double *v_hat, double *v_hat_old, double *y,
-                      double *w, double *w_old, double *v, double *av, double norm_r0, double beta0, double errtol, int it_max,
-                      int *info, int *iter, double *relres, double *hist) {
+int minres_brick_loop(const psp_csr *A, const double *dinv, int n, double *x, double *v_hat, double *y, double *w, double *v,
+                      double *av, double norm_r0, double beta0, double errtol, int it_max, int *info, int *iter,
+                      double *relres, double *hist) {
   BrickPlan P;
   if (!brick_plan(A, n, &P, true)) return kCoopFallback;
-  (void)v_hat_old;
-  (void)w_old;
-  Workspace *ws;
-  PSP_TRY(workspace(&ws));
-  struct Mem {
-    double *hist = nullptr;
-    size_t nhist = 0;
-    ~Mem() { scratch_put(hist, nhist); }
-  } m;
-  MidCtl *ctl = static_cast<MidCtl *>(ws->state_dev);
-  PSP_HIP(hipMemsetAsync(ctl, 0, sizeof(MidCtl), stream()));
-  PSP_HIP(hipMemsetAsync(ws->ctl_part, 0, sizeof(double) * 2 * kMidMaxWg, stream()));
-  if (hist) {
-    m.nhist = (size_t)it_max + 2;
-    PSP_TRY(scratch_get(m.nhist, &m.hist));
-    PSP_HIP(hipMemsetAsync(m.hist, 0xff, sizeof(double) * m.nhist, stream()));
-  }
-  double *yv = y;
-  if (!dinv) {
-    yv = v;
-    PSP_HIP(hipMemcpyAsync(yv, v_hat, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  } else {
-    PSP_HIP(hipMemcpyAsync(av, y, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  }
   BrickMinresArgs a;
-  a.n = n;
-  a.nwg = P.nwg;
-  a.nx = P.nx; a.ny = P.ny; a.nz = P.nz;
-  a.bx = P.bx; a.by = P.by; a.bz = P.bz;
-  a.cx = P.cx; a.cy = P.cy;
-  for (int o = 0; o < 7; ++o) a.cval[o] = P.w4.cval[o];
-  a.valT = P.w4.valT;
-  a.mask = P.w4.mask;
-  a.dinv = dinv;
-  a.dc = 0.0;
-  a.pre = !dinv ? 0 : (dinv_constant(dinv, n, &a.dc) ? 2 : 1);
+  const SkVectors V = sk_minres_vectors(dinv, n, x, v_hat, y, w, v, av, &a.yv);
+  fill_operator(a, P.w4, dinv, n);
+  fill_bricks(a, P);
   a.x = x;
   a.xout = w;
   a.v_hat = v_hat;
-  a.yv = yv;
   a.norm_r0 = norm_r0;
   a.beta0 = beta0;
   a.errtol = errtol;
   a.it_max = it_max;
-  a.ctl = ctl;
-  a.part = ws->ctl_part;
-  a.hist = m.hist;
   void *args[] = {&a};
-  int rc = PSP_OK;
-  const char *ff = tuning_env("PSP_COOP_FAIL");
-  if (ff && atoi(ff) == 1) {
-    rc = kCoopFallback;
-  } else if (hipLaunchCooperativeKernel(P.kernel, dim3(P.nwg), dim3(kBrickBlock), args,
-                                        (unsigned)P.lds, stream()) != hipSuccess) {
-    (void)hipGetLastError();
-    rc = kCoopFallback;
-  }
-  MidCtl c;
-  if (rc == PSP_OK) {
-    PSP_HIP(hipMemcpyAsync(&c, ctl, sizeof(MidCtl), hipMemcpyDeviceToHost, stream()));
-    PSP_HIP(hipStreamSynchronize(stream()));
-    if (c.error) rc = kCoopFallback;
-  }
-  if (rc == kCoopFallback) {
-    g_brick_fallbacks.fetch_add(1);
-    if (dinv) PSP_HIP(hipMemcpyAsync(y, av, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-    PSP_HIP(hipMemsetAsync(w, 0, sizeof(double) * (size_t)n, stream()));
-  }
-  if (rc != PSP_OK) return rc;
-  g_brick_solves.fetch_add(1);
-  PSP_HIP(hipMemcpyAsync(x, w, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  PSP_HIP(hipStreamSynchronize(stream()));
-  *info = c.info;
-  *iter = c.iter;
-  if (c.info == 0 || c.info == -1) *relres = c.relres;
-  if (hist) {
-    const int cnt = std::min(c.iter, it_max);
-    if (cnt >= 1) {
-      std::vector<double> h((size_t)cnt);
-      PSP_HIP(hipMemcpy(h.data(), m.hist + 1, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-      for (int i = 0; i < cnt; ++i)
-        if (h[i] == h[i]) hist[1 + i] = h[i];
-    }
-  }
-  return PSP_OK;
+  const SkLaunch<MidCtl> L{P.kernel, P.nwg, kBrickBlock, P.lds, args, &a.ctl, &a.part, &a.hist, &g_brick_solves, &g_brick_fallbacks};
+  return sk_run<MidCtl, 2 * kMidMaxWg>(L, V, it_max, info, iter, relres, hist);
 }
 
 int pcg_brick_loop(const psp_csr *A, const double *dinv, int n, double *x, double *r, double *p, double *q, double n2b,
                    double tolb, double normr0, double rho0, int maxit, int *info, int *iter, double *relres, double *hist) {
   BrickPlan P;
   if (!brick_plan(A, n, &P)) return kCoopFallback;
-  static_assert(3 * (size_t)kMidMaxWg <= kCtlPartDoubles, "state slab");
-  Workspace *ws;
-  PSP_TRY(workspace(&ws));
-  struct Mem {
-    double *hist = nullptr;
-    size_t nhist = 0;
-    ~Mem() { scratch_put(hist, nhist); }
-  } m;
-  MidCtl *ctl = static_cast<MidCtl *>(ws->state_dev);
-  PSP_HIP(hipMemsetAsync(ctl, 0, sizeof(MidCtl), stream()));
-  PSP_HIP(hipMemsetAsync(ws->ctl_part, 0, sizeof(double) * 3 * kMidMaxWg, stream()));
-  if (hist) {
-    m.nhist = (size_t)maxit + 2;
-    PSP_TRY(scratch_get(m.nhist, &m.hist));
-    PSP_HIP(hipMemsetAsync(m.hist, 0xff, sizeof(double) * m.nhist, stream()));
-  }
-  PSP_HIP(hipMemcpyAsync(q, r, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));  // r as it is, for a fall-back
   BrickArgs a;
-  a.n = n;
-  a.nwg = P.nwg;
-  a.nx = P.nx; a.ny = P.ny; a.nz = P.nz;
-  a.bx = P.bx; a.by = P.by; a.bz = P.bz;
-  a.cx = P.cx; a.cy = P.cy;
-  for (int o = 0; o < 7; ++o) a.cval[o] = P.w4.cval[o];
-  a.valT = P.w4.valT;
-  a.mask = P.w4.mask;
-  a.dinv = dinv;
-  a.dc = 0.0;
-  a.pre = !dinv ? 0 : (dinv_constant(dinv, n, &a.dc) ? 2 : 1);
+  fill_operator(a, P.w4, dinv, n);
+  fill_bricks(a, P);
   a.x = x;
   a.xout = p;
   a.r = r;
@@ -2024,46 +1773,9 @@ int pcg_brick_loop(const psp_csr *A, const double *dinv, int n, double *x, doubl
   a.normr0 = normr0;
   a.rho0 = rho0;
   a.maxit = maxit;
-  a.ctl = ctl;
-  a.part = ws->ctl_part;
-  a.hist = m.hist;
   void *args[] = {&a};
-  int rc = PSP_OK;
-  const char *ff = tuning_env("PSP_COOP_FAIL");
-  if (ff && atoi(ff) == 1) {
-    rc = kCoopFallback;
-  } else if (hipLaunchCooperativeKernel(P.kernel, dim3(P.nwg), dim3(kBrickBlock), args, (unsigned)P.lds,
-                                        stream()) != hipSuccess) {
-    (void)hipGetLastError();
-    rc = kCoopFallback;
-  }
-  MidCtl c;
-  if (rc == PSP_OK) {
-    PSP_HIP(hipMemcpyAsync(&c, ctl, sizeof(MidCtl), hipMemcpyDeviceToHost, stream()));
-    PSP_HIP(hipStreamSynchronize(stream()));
-    if (c.error) rc = kCoopFallback;
-  }
-  if (rc == kCoopFallback) {
-    g_brick_fallbacks.fetch_add(1);
-    PSP_HIP(hipMemcpyAsync(r, q, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  }
-  if (rc != PSP_OK) return rc;
-  g_brick_solves.fetch_add(1);
-  PSP_HIP(hipMemcpyAsync(x, p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream()));
-  PSP_HIP(hipStreamSynchronize(stream()));
-  *info = c.info;
-  *iter = c.iter;
-  *relres = c.relres;
-  if (hist) {
-    const int cnt = std::min(c.iter, maxit);
-    if (cnt >= 1) {
-      std::vector<double> h((size_t)cnt);
-      PSP_HIP(hipMemcpy(h.data(), m.hist + 1, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-      for (int i = 0; i < cnt; ++i)
-        if (h[i] == h[i]) hist[1 + i] = h[i];
-    }
-  }
-  return PSP_OK;
+  const SkLaunch<MidCtl> L{P.kernel, P.nwg, kBrickBlock, P.lds, args, &a.ctl, &a.part, &a.hist, &g_brick_solves, &g_brick_fallbacks};
+  return sk_run<MidCtl, 3 * kMidMaxWg>(L, sk_pcg_vectors(n, x, r, p, q), maxit, info, iter, relres, hist);
 }
 
 }  // namespace psp

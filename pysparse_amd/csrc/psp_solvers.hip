@@ -17,6 +17,7 @@
 //            jacobi with steps > 1): same kernels with an explicit z vector; callback
 //            operators are bridged with one D2H + one H2D copy per application.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -716,6 +717,42 @@ int robust_norm2(int n, const double *v, double sq, double *out) {
 }
 }  // namespace psp
 
+// The single-kernel loops in the order a solve tries them.  mid: mid-size offset-structured systems, the launch-per-phase
+// loops' bits; brick: 3-D grid operators whose slabs mid declines; coop: small systems, one row per thread.
+// needs_rho: PCG enters the loop only with rho = r.z != 0 (pcg.c:101-104 is left to the loops below); needs_dinv: MINRES
+// enters it only without a preconditioner or with a jacobi whose dinv it can read.
+struct PcgSkLoop {
+  const char *name;  // for note_solve
+  bool needs_rho;
+  bool (*applicable)(const psp_csr *A, int n);
+  PcgSkFn *run;
+};
+struct MinresSkLoop {
+  const char *name;
+  bool needs_dinv;
+  bool (*applicable)(const psp_csr *A, int n);
+  MinresSkFn *run;
+};
+static const std::array<PcgSkLoop, 3> &pcg_sk_loops() {
+  static const std::array<PcgSkLoop, 3> t = {{{"pcg_mid", true, mid_applicable, pcg_mid_loop},
+                                              {"pcg_brick", true, brick_applicable, pcg_brick_loop},
+                                              {"pcg_coop", false, coop_applicable, pcg_coop_loop}}};
+  return t;
+}
+static const std::array<MinresSkLoop, 3> &minres_sk_loops() {
+  static const std::array<MinresSkLoop, 3> t = {{{"minres_mid", true, mid_minres_applicable, minres_mid_loop},
+                                                 {"minres_brick", true, brick_minres_applicable, minres_brick_loop},
+                                                 {"minres_coop", false, coop_applicable, minres_coop_loop}}};
+  return t;
+}
+namespace psp {
+PcgSkFn *pcg_sk_choice(const psp_csr *A, int n, bool rho_nonzero) {
+  for (const PcgSkLoop &L : pcg_sk_loops())
+    if ((rho_nonzero || !L.needs_rho) && L.applicable(A, n)) return L.run;
+  return nullptr;
+}
+}  // namespace psp
+
 static int pcg_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_forced, const double *dinv_forced,
                            int n, double *x, const double *b, double tol, int maxit, int *info, int *iter,
                            double *relres, double *hist) {
@@ -780,33 +817,16 @@ static int pcg_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_force
   const bool sk = single_kernel_loops_enabled();  // psp_set_single_kernel_loops(0): launch-per-phase loops only
   double dcst;
   const int dstream = (dinv && !dinv_constant(dinv, n, &dcst)) ? 1 : 0;
-  if (sk && fused && maxit >= 1 && rho_next != 0.0 && mid_applicable(Acsr, n, dinv)) {
-    // mid-size offset-structured system: the whole loop is one cooperative kernel, vectors in registers, p through LDS
-    // (psp_mid.hip) -- the launch-per-phase loops' bits
-    const int rc = pcg_mid_loop(Acsr, dinv, n, x, r, p, q, n2b, tolb, normr, rho_next, maxit, info, iter, relres, hist);
-    if (rc != kCoopFallback) {
-      note_solve("pcg_mid", 1, 0, dstream);
-      return rc;
+  if (sk && fused && maxit >= 1)
+    for (const PcgSkLoop &L : pcg_sk_loops()) {  // the whole loop as one kernel: mid, brick, coop (psp_mid.hip, psp_coop.hip)
+      if ((L.needs_rho && rho_next == 0.0) || !L.applicable(Acsr, n)) continue;
+      const int rc = L.run(Acsr, dinv, n, x, r, p, q, n2b, tolb, normr, rho_next, maxit, info, iter, relres, hist);
+      if (rc != kCoopFallback) {
+        note_solve(L.name, 1, 0, dstream);
+        return rc;
+      }
+      note_fallback();  // refused / gave up: x and r are untouched, the loops below take over
     }
-    note_fallback();  // refused / gave up: x and r are untouched, the loops below take over
-  }
-  if (sk && fused && maxit >= 1 && rho_next != 0.0 && brick_applicable(Acsr, n)) {
-    // 3-D grid operator whose slabs the loop above declines: the same loop with the points dealt out in bricks (psp_mid.hip)
-    const int rc = pcg_brick_loop(Acsr, dinv, n, x, r, p, q, n2b, tolb, normr, rho_next, maxit, info, iter, relres, hist);
-    if (rc != kCoopFallback) {
-      note_solve("pcg_brick", 1, 0, dstream);
-      return rc;
-    }
-    note_fallback();
-  }
-  if (sk && fused && maxit >= 1 && coop_applicable(Acsr, n)) {  // small system: the whole loop is one kernel (psp_coop.hip)
-    const int rc = pcg_coop_loop(Acsr, dinv, n, x, r, p, q, n2b, tolb, normr, rho_next, maxit, info, iter, relres, hist);
-    if (rc != kCoopFallback) {
-      note_solve("pcg_coop", 1, 0, dstream);
-      return rc;
-    }
-    note_fallback();  // refused / gave up: x and r are untouched, the loops below take over
-  }
   if (fused && maxit >= 1 && pcg_async_enabled() && csr_spmv_has_skip(Acsr)) {
     if (rho_next == 0.0) {  // pcg.c:101-104 in iteration 1
       *info = -2;
@@ -1228,36 +1248,17 @@ static int minres_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_fo
   const bool sk = single_kernel_loops_enabled();  // psp_set_single_kernel_loops(0): launch-per-phase loops only
   double dcst;
   const int dstream = (hasK && dinv && !dinv_constant(dinv, n, &dcst)) ? 1 : 0;
-  if (sk && Acsr && kfused && it_max >= 1 && !(norm_rmr < errtol * norm_r0) && (!hasK || dinv) && mid_minres_applicable(Acsr, n)) {
-    // mid-size offset-structured system: the whole loop is one cooperative kernel (psp_mid.hip), the launch-per-phase bits
-    const int rc = minres_mid_loop(Acsr, hasK ? dinv : nullptr, n, x, v_hat, v_hat_old, y, wv, w_old, v, av, norm_r0,
-                                   beta, errtol, it_max, info, iter, relres, hist);
-    if (rc != kCoopFallback) {
-      note_solve("minres_mid", 1, 0, dstream);
-      return rc;
+  if (sk && Acsr && kfused && it_max >= 1 && !(norm_rmr < errtol * norm_r0))
+    for (const MinresSkLoop &L : minres_sk_loops()) {  // the whole loop as one kernel: mid, brick, coop
+      if ((L.needs_dinv && hasK && !dinv) || !L.applicable(Acsr, n)) continue;
+      const int rc = L.run(Acsr, hasK ? dinv : nullptr, n, x, v_hat, y, wv, v, av, norm_r0, beta, errtol, it_max, info, iter,
+                           relres, hist);
+      if (rc != kCoopFallback) {
+        note_solve(L.name, 1, 0, dstream);
+        return rc;
+      }
+      note_fallback();  // refused / gave up: x, v_hat, y are untouched, the loops below take over
     }
-    note_fallback();
-  }
-  if (sk && Acsr && kfused && it_max >= 1 && !(norm_rmr < errtol * norm_r0) && (!hasK || dinv) && brick_minres_applicable(Acsr, n)) {
-    // 3-D grid operator: the same with the points dealt out in bricks
-    const int rc = minres_brick_loop(Acsr, hasK ? dinv : nullptr, n, x, v_hat, v_hat_old, y, wv, w_old, v, av, norm_r0,
-                                     beta, errtol, it_max, info, iter, relres, hist);
-    if (rc != kCoopFallback) {
-      note_solve("minres_brick", 1, 0, dstream);
-      return rc;
-    }
-    note_fallback();
-  }
-  if (sk && Acsr && kfused && it_max >= 1 && !(norm_rmr < errtol * norm_r0) && coop_applicable(Acsr, n)) {
-    // small system: the whole loop is one kernel (psp_coop.hip)
-    const int rc = minres_coop_loop(Acsr, hasK ? dinv : nullptr, n, x, v_hat, v_hat_old, y, wv, w_old, v, av, norm_r0,
-                                    beta, errtol, it_max, info, iter, relres, hist);
-    if (rc != kCoopFallback) {
-      note_solve("minres_coop", 1, 0, dstream);
-      return rc;
-    }
-    note_fallback();  // refused / gave up: x, v_hat, y are untouched, the loops below take over
-  }
   if (Acsr && kfused && minres_async_enabled() && it_max >= 1 && !(norm_rmr < errtol * norm_r0)) {
     // scaled product (reads y, writes Av) + lanczos (Av, v_hat, v_hat_old read; v_hat, y written: 40, + 8 when K streams
     // dinv) + w / x update (y, w, w_old, x read; w, x written: 48): 88 bytes per row beside the product

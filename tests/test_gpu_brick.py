@@ -97,8 +97,10 @@ def test_sss_form_and_the_launch_per_phase_loops(oracle):
         "    for K in (None, dev.DeviceJacobi(A)):\n"
         "        for tol, mx in ((1e-9, 4000), (0.0, 11)):\n"
         "          for s in (dev.pcg, dev.minres):\n"
-        "            x = np.zeros(n); r = s(A, b, x, tol, mx, K)\n"
-        "            out.append([r[0], r[1], r[2], float(np.abs(x).max()), x[::max(1, n // 97)].tolist()])\n"
+        "            x = np.zeros(n); r = s(A, b, x, tol, mx, K, hist=True)\n"
+        "            h = np.asarray(r[3], dtype=np.float64); m = np.isfinite(h)\n"
+        "            out.append([r[0], r[1], r[2], float(np.abs(x).max()), x[::max(1, n // 97)].tolist(),\n"
+        "                        np.flatnonzero(m).tolist(), h[m].tolist()])\n"
         "s, f = C.c_longlong(), C.c_longlong(); L.psp_debug_brick_count(C.byref(s), C.byref(f)); out.append([s.value, f.value])\n"
         "print(json.dumps(out))"
     ) % ROOT
@@ -115,7 +117,9 @@ def test_sss_form_and_the_launch_per_phase_loops(oracle):
         assert a[:2] == b[:2], (a[:3], b[:3])
         assert abs(a[2] - b[2]) <= 1e-6 * b[2]
         assert np.abs(np.array(a[4]) - np.array(b[4])).max() <= 1e-12 * b[3]
-    assert res[2][:-1] == res[1][:-1]  # a refused launch IS the launch-per-phase loop from the same vectors
+        assert a[5] == b[5] and np.allclose(a[6], b[6], rtol=1e-5, atol=0)  # the history: the same slots, to rounding
+    # a refused launch IS the launch-per-phase loop from the same vectors: the same bits, the history included
+    assert res[2][:-1] == res[1][:-1]
 
 
 def test_operators_the_bricks_do_not_take(oracle):

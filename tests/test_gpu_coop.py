@@ -88,8 +88,10 @@ def test_single_kernel_loops_against_the_launch_per_phase_loops():
         "    A = dev.DeviceCSR.poisson(*grid); n = A.shape[0]; b = np.random.default_rng(5).standard_normal(n)\n"
         "    for K in (None, dev.DeviceJacobi(A)):\n"
         "        for s in (dev.pcg, dev.minres):\n"
-        "            x = np.zeros(n); r = s(A, b, x, 1e-9, 4000, K)\n"
-        "            out.append([r[0], r[1], r[2], float(np.abs(x).max()), x[::max(1, n // 97)].tolist()])\n"
+        "            x = np.zeros(n); r = s(A, b, x, 1e-9, 4000, K, hist=True)\n"
+        "            h = np.asarray(r[3], dtype=np.float64); m = np.isfinite(h)\n"
+        "            out.append([r[0], r[1], r[2], float(np.abs(x).max()), x[::max(1, n // 97)].tolist(),\n"
+        "                        np.flatnonzero(m).tolist(), h[m].tolist()])\n"
         "print(json.dumps(out))"
     ) % ROOT
     res = []
@@ -107,7 +109,9 @@ def test_single_kernel_loops_against_the_launch_per_phase_loops():
         assert a[:2] == b[:2], (a[:3], b[:3])
         assert abs(a[2] - b[2]) <= 1e-6 * b[2]
         assert np.abs(np.array(a[4]) - np.array(b[4])).max() <= 1e-12 * b[3]
-    # a refused / failed single-kernel loop IS the launch-per-phase loop from the same vectors: the same bits
+        assert a[5] == b[5] and np.allclose(a[6], b[6], rtol=1e-5, atol=0)  # the history: the same slots, to rounding
+    # a refused / failed single-kernel loop IS the launch-per-phase loop from the same vectors: the same bits, the
+    # history (rows [5], [6]) included
     assert res[2] == res[1]
     # capacity 4: every system here has more than 4096 rows -> launch-per-phase loops throughout
     assert res[3] == res[1]
