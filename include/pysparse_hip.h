@@ -392,6 +392,18 @@ int psp_mg_precon_dev(psp_mg_t *K, const double *x_dev, double *y_dev);
  * vectors in LDS), kernel launches per application, and the level dimensions (3 ints per level, 1 on absent axes;
  * dims may be NULL) */
 int psp_mg_info(const psp_mg_t *K, int *levels, int *tail_first_level, int *launches_per_apply, int *dims);
+/* Y[:, c] := K X[:, c] for c < k in ONE block cycle (either mode): column-major blocks, column c at X + c*ldx and
+ * Y + c*ldy, ldx, ldy >= n, k >= 1; Y must not overlap X (PSP_EINVAL).  Column c has the bits of psp_mg_precon on that
+ * column; the cycle is launches_per_apply launches whatever k is, and the level operators of a Galerkin handle are
+ * streamed once per group of columns instead of once per column.  PSP_ENODEV with PSP_DEVICE=cpu. */
+int psp_mg_precon_block(psp_mg_t *K, int k, const double *X_host, long ldx, double *Y_host, long ldy);
+int psp_mg_precon_block_dev(psp_mg_t *K, int k, const double *X_dev, long ldx, double *Y_dev, long ldy);
+/* The block cycle's level vectors: a second set on the handle, about (1 + 3/7) n 8 k bytes on a 3-D grid, allocated by
+ * the first block call for its k and grown on demand.  psp_mg_block_reserve allocates them ahead of time for at least k
+ * columns (k = 0 frees them); psp_mg_block_info reports the columns they hold and their bytes (either may be NULL).
+ * psp_mg_destroy frees them, psp_trim does not touch them. */
+int psp_mg_block_reserve(psp_mg_t *K, int k);
+int psp_mg_block_info(psp_mg_t *K, int *columns, long long *bytes);
 
 /* precon.multigrid(A, grid, omega, steps, galerkin=True): the same cycle (level grids, P, R, smoother, tail, dense
  * coarsest solve) for ANY symmetric 3- / 5- / 7-point operator on the grid, e.g. -div(kappa grad u) + s u with kappa varying
@@ -493,8 +505,9 @@ int psp_bv_rotate(int n, int j, double *V_dev, int64_t ld, const double *U_host,
  * its expanded mirror.  PSP_EINVAL: a multi-device matrix, a matrix stored in parts, a released handle with more than 9
  * offsets, X and Y overlapping, k < 1, a leading dimension below the vector length.  PSP_DEVICE=cpu: PSP_ENODEV.
  * The *_dev forms enqueue on the calling thread's stream and return without synchronising.
- * psp_op_apply_block_dev: the same for any operator -- csr / sss as above, jacobi with steps = 1 one scaling kernel, every
- * other kind (ssor, host callback, jacobi with more steps) column by column. */
+ * psp_op_apply_block_dev: the same for any operator -- csr / sss as above, jacobi with steps = 1 one scaling kernel, a
+ * multigrid handle one block cycle (psp_mg_precon_block_dev), every other kind (ssor, host callback, jacobi with more
+ * steps) column by column. */
 int psp_csr_matmat(psp_csr_t *A, int k, const double *X_host, long ldx, double *Y_host, long ldy);
 int psp_csr_matmat_dev(psp_csr_t *A, int k, const double *X_dev, long ldx, double *Y_dev, long ldy);
 int psp_sss_matmat(psp_sss_t *S, int k, const double *X_host, long ldx, double *Y_host, long ldy);
@@ -510,8 +523,11 @@ int psp_op_apply_block_dev(const psp_op_t *op, int k, const double *X_dev, long 
  * of it is written again while the loop goes on for the others.  The loop always runs in the stored numbering of A: on an
  * irregular handle whose single solves go through the renumbered copy the two differ at rounding level, like the two
  * numberings themselves.  Launches and host read-backs per iteration do not grow with k when A is native with an
- * index-free product and K is absent or a jacobi with steps = 1 (psp_last_solve_info names "pcg_batch"); other products
- * and preconditioners are applied column by column inside the same loop.  A multi-device matrix gives PSP_EINVAL,
+ * index-free product and K is absent, a jacobi with steps = 1, or a multigrid handle (psp_last_solve_info names
+ * "pcg_batch" and the launches of an iteration).  A multigrid K is applied as ONE block cycle that skips the frozen
+ * columns by their device flags: an iteration is the cycle's launches_per_apply plus seven, and 16 iterations are
+ * enqueued between two looks at the flags; with another product family only K is the block call.  Other products and
+ * preconditioners are applied column by column inside the same loop.  A multi-device matrix gives PSP_EINVAL,
  * PSP_DEVICE=cpu PSP_ENODEV.  ldx, ldb >= n. */
 int psp_pcg_batch(const psp_op_t *A, const psp_op_t *K, int n, int k, double *X_host, long ldx, const double *B_host,
                   long ldb, double tol, int maxit, int *info, int *iter, double *relres);

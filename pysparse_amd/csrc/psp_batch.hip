@@ -8,7 +8,12 @@
 //     finish    one workgroup per column: pcg.c:127-162 and the head of the next iteration (pcg.c:99-112)
 // Other operators keep the same loop and the same arithmetic; what cannot be batched is done column by column in its place:
 // a native product with another kernel family runs the single-vector product (its fused dot has that kernel's own order
-// of partial sums), any other preconditioner goes through op_apply_block and a batched r.z dot.
+// of partial sums), any other preconditioner is applied column by column and followed by a batched r.z dot.
+// K = precon.multigrid: z = K r is ONE block cycle (psp_mg.hip) that skips the frozen columns by
+// the device flags; with the block product beside it the loop enqueues 16 iterations between two looks at the flags,
+// as the fused path does, and an iteration is the cycle's launches plus seven (r.z, head, pupdate, product, finish, xr,
+// finish) whatever k is.  With another product family only K becomes the block call; the rest stays column by column
+// with a look at the flags after every iteration.
 //
 // Bit equality with psp_pcg, column by column: the element a thread owns (2t, 2t+1 of a 512-row span), the order in which
 // it adds, the wave tree, the four waves left to right and reduce_block over the spans are those of dot_kernel,
@@ -550,9 +555,15 @@ int pcg_batch_dev(const psp_op *A, const psp_op *K, int n, int k, double *X, lon
   // what the loop can do for all columns at once
   const bool block_product = Acsr != nullptr && w4 != 0;
   const bool batched = fused && (block_product || coop_order);
+  // a multigrid K is one block cycle (psp_mg.hip) that reads the device flags itself; with the block product beside it
+  // nothing in an iteration depends on the host's view of the flags, and the launches do not depend on k: the cycle's, then
+  // r.z, head, pupdate, product, finish, xr, finish
+  const bool mg_block = !fused && K && K->kind == PSP_OP_MG && K->mg && mg_block_routed(K->mg);
+  const bool mg_batched = mg_block && block_product;
   // launches per iteration where they do not depend on k: pupdate, product (+ its dot in the one-kernel order), finish, xr, finish
-  note_solve("pcg_batch", batched ? (coop_order ? 6 : 5) : -1, batched ? 72 + (dinv ? 16 : 0) : -1, dinv ? 1 : 0);
-  const int kBatch = batched ? 16 : 1;  // iterations enqueued between two looks at the states
+  note_solve("pcg_batch", batched ? (coop_order ? 6 : 5) : mg_batched ? mg_launches(K->mg) + 7 : -1,
+             batched ? 72 + (dinv ? 16 : 0) : -1, dinv ? 1 : 0);
+  const int kBatch = batched || mg_batched ? 16 : 1;  // iterations enqueued between two looks at the states
   int enqueued = 0;
   std::vector<int> live(k);
   for (int c = 0; c < k; ++c) live[c] = !fh[c];
@@ -562,8 +573,12 @@ int pcg_batch_dev(const psp_op *A, const psp_op *K, int n, int k, double *X, lon
       const double *zsrc = R;
       if (!fused) {  // z = K r (pcg.c:93-96), rho = r.z (pcg.c:100), then the head of the iteration
         if (K) {
-          for (int c = 0; c < k; ++c)
-            if (live[c]) PSP_TRY(op_apply(K, R + (size_t)c * n, Z + (size_t)c * n));
+          if (mg_block) {
+            PSP_TRY(op_apply_block(K, k, R, n, Z, n, frozen));
+          } else {
+            for (int c = 0; c < k; ++c)
+              if (live[c]) PSP_TRY(op_apply(K, R + (size_t)c * n, Z + (size_t)c * n));
+          }
           zsrc = Z;
         }
         hipLaunchKernelGGL(bdot_kernel, vgrid, dim3(kBlock), 0, stream(), (long)n, k, (const double *)R, (long)n, zsrc,

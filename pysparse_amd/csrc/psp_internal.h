@@ -553,9 +553,13 @@ struct KryArg {
 // y = op(x) on device vectors; y must not alias x
 int op_apply(const psp_op *op, const double *x_dev, double *y_dev);
 // psp_spmm.hip: Y[:, c] = op(X[:, c]), c < k, on column-major device blocks (column c at X + c*ldx / Y + c*ldy); Y must not
-// overlap X.  Native csr / sss: the block product kernels; jacobi with steps == 1: one scaling kernel; every other kind:
-// op_apply column by column -- so the result is defined for every operator, with the bits of op_apply on each column
-int op_apply_block(const psp_op *op, int k, const double *X, long ldx, double *Y, long ldy);
+// overlap X.  Native csr / sss: the block product kernels; jacobi with steps == 1: one scaling kernel; multigrid: one block
+// cycle (mg_apply_block_dev, where mg_block_routed says so); every other kind: op_apply column by column -- so the
+// result is defined for every operator, with the bits of op_apply on each column.
+// frozen != nullptr (a device array): the block cycle skips the columns it flags (the batched PCG loop); other kinds ignore it
+int op_apply_block(const psp_op *op, int k, const double *X, long ldx, double *Y, long ldy, const int *frozen = nullptr);
+// the argument rules of every block entry point: k >= 1, leading dimensions, X and Y must not overlap
+int block_args(const char *what, int nrows, int ncols, int k, const double *X, long ldx, const double *Y, long ldy);
 // the block product at its device-pointer level.  skip: per-column flags on the device (nullptr: every column); a column
 // whose flag is not 0 is neither computed nor written.  partials != nullptr: the X[:, c] . Y[:, c] partial sums of column c at
 // partials + c*pstride in the order of the single-vector product's fused dot; *nparts = their count per column, or 0 when
@@ -790,4 +794,8 @@ int ssor_apply_dev(psp_ssor *K, const double *b, double *x);  // psp_ssor.hip
 int ssor_error_check(psp_ssor *K);
 int ssor_apply_host(psp_ssor *K, const double *b, double *x);  // psp_ssor.hip: PSP_DEVICE=cpu, host arrays
 int mg_apply_dev(psp_mg *K, const double *b, double *y);  // psp_mg.hip: one V-cycle, y must not alias b
+// the block cycle: column c gets mg_apply_dev's bits, columns with frozen[c] != 0 are skipped
+int mg_apply_block_dev(psp_mg *K, int k, const double *X, long ldx, double *Y, long ldy, const int *frozen);
+int mg_launches(const psp_mg *K);        // kernel launches of one application, of one vector or of a block
+bool mg_block_routed(const psp_mg *K);   // op_apply_block / psp_pcg_batch run the block cycle for this handle's mode
 }  // namespace psp

@@ -23,6 +23,10 @@
 // against a level-operator policy Op that supplies the level's geometry, (A_l x)[i], omega / diagonal and the index
 // split -- MfOp here (c_a and d are kernel arguments), GOp / GTailOp in psp_mg_galerkin.h (stored arrays), which this
 // file includes and which holds what only the stored mode has; its creation is below, next to the matrix-free one.
+//
+// Blocks of k vectors (psp_mg_precon_block): block forms of the five cycle kernels, one thread per
+// point and up to KC columns, the row's coefficients loaded once per point (Op::load_row / ax_row); the same schedule, the
+// same launches whatever k is, column c with the bits of the single cycle on column c.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -121,6 +125,20 @@ struct MfOp {
   }
   __device__ __forceinline__ double w(long) const { return L.w; }
   __device__ __forceinline__ void split(long i, int &i0, int &i1, int &i2) const { mg_split<ND>(L, i, i0, i1, i2); }
+  // the block kernels' pair (GOp in psp_mg_galerkin.h has the real one): this mode's row is kernel arguments, nothing is
+  // loaded; x(j, w_j) is the column's value at j
+  struct Row {
+    double w;
+  };
+  template <bool WN>
+  __device__ __forceinline__ Row load_row(long, int, int, int) const {
+    return Row{L.w};
+  }
+  template <class X>
+  __device__ __forceinline__ double ax_row(const Row &r, const X &x, long i, int i0, int i1, int i2) const {
+    auto X1 = [&](long j) { return x(j, r.w); };
+    return mg_ax(L, X1, i, i0, i1, i2);
+  }
 };
 // omega / d as mg_scale_kernel takes it
 struct MfW {
@@ -273,6 +291,140 @@ __global__ __launch_bounds__(256) void mg_prolong_kernel(MgLevelArg L, long N, c
   x[i] = x[i] + mg_prolong_point(L, E, i0, i1, i2);
 }
 
+// ------------------------------------------------------------------ the block forms: k columns at once (section 9e)
+// Column c of a vector block starts at base + c * ld.  A thread owns one point and up to KC columns (blockIdx.y = the
+// group of KC columns): the index split, omega / diagonal and the row's coefficients are formed or loaded once
+// (Op::load_row), then each column gets the single kernel's arithmetic in the single kernel's order (Op::ax_row).
+// frozen != nullptr: a column with frozen[c] != 0 is skipped -- nothing of it is read or written; the branch is uniform
+// across the workgroup.
+
+// live columns of the group that starts at c0, as a bit mask
+template <int KC>
+__device__ __forceinline__ unsigned mg_live(int c0, int k, const int *__restrict__ frozen) {
+  unsigned m = 0u;
+#pragma unroll
+  for (int c = 0; c < KC; ++c)
+    if (c0 + c < k && !(frozen && frozen[c0 + c])) m |= 1u << c;
+  return m;
+}
+
+template <class W, int KC>
+__global__ __launch_bounds__(256) void mg_scale_block_kernel(long N, W w, int k, const double *__restrict__ b, long ldb,
+                                                             double *__restrict__ x, long ldx,
+                                                             const int *__restrict__ frozen) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const int c0 = blockIdx.y * KC;
+  const unsigned live = mg_live<KC>(c0, k, frozen);
+  if (i >= N || !live) return;
+  const double wi = w(i);
+#pragma unroll
+  for (int c = 0; c < KC; ++c)
+    if ((live >> c) & 1u) x[(size_t)(c0 + c) * ldx + i] = wi * b[(size_t)(c0 + c) * ldb + i];
+}
+
+template <class Op, bool FROMB, int KC>
+__global__ __launch_bounds__(256) void mg_smooth_block_kernel(typename Op::Level A, long N, int k,
+                                                              const double *__restrict__ xin, long ldi,
+                                                              const double *__restrict__ b, long ldb,
+                                                              double *__restrict__ xout, long ldo,
+                                                              const int *__restrict__ frozen) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const int c0 = blockIdx.y * KC;
+  const unsigned live = mg_live<KC>(c0, k, frozen);
+  if (i >= N || !live) return;
+  const Op op(A);
+  int i0, i1, i2;
+  op.split(i, i0, i1, i2);
+  const auto row = op.template load_row<FROMB>(i, i0, i1, i2);
+#pragma unroll
+  for (int c = 0; c < KC; ++c) {
+    if (!((live >> c) & 1u)) continue;
+    const double *__restrict__ bc = b + (size_t)(c0 + c) * ldb;
+    const double *__restrict__ xc = FROMB ? bc : xin + (size_t)(c0 + c) * ldi;
+    auto X = [&](long j, double wj) { return FROMB ? wj * bc[j] : xc[j]; };
+    const double ax = op.ax_row(row, X, i, i0, i1, i2);
+    xout[(size_t)(c0 + c) * ldo + i] = X(i, row.w) + row.w * (bc[i] - ax);
+  }
+}
+
+// b_c = R (b - A x) for KC columns: points outer, columns inner -- a fine point's row is loaded once and applied to every
+// column of the group, whose residual tiles lie side by side in LDS.  KC = 1 with the columns in gridDim.y is the other
+// form (one tile, reused by nobody: every column is a workgroup of its own).
+template <class Op, int KC>
+__global__ __launch_bounds__(kResThreads) void mg_restrict_block_kernel(typename Op::Level A, int t0, int t1, int t2,
+                                                                        int g0n, int g1n, int k,
+                                                                        const double *__restrict__ x, long ldx,
+                                                                        const double *__restrict__ b, long ldb,
+                                                                        double *__restrict__ bc, long ldc,
+                                                                        const int *__restrict__ frozen) {
+  __shared__ double r[KC][kResLds];
+  const int c0 = blockIdx.y * KC;
+  const unsigned live = mg_live<KC>(c0, k, frozen);
+  if (!live) return;  // uniform: before any barrier
+  const Op op(A);
+  const MgLevelArg &L = op.geo();
+  const unsigned bq = blockIdx.x / (unsigned)g0n;
+  const int J0 = (int)(blockIdx.x % (unsigned)g0n) * t0, J1 = (int)(bq % (unsigned)g1n) * t1, J2 = (int)(bq / (unsigned)g1n) * t2;
+  const int f0 = L.co[0] ? 2 * J0 : J0, F0 = L.co[0] ? 2 * t0 + 1 : t0;
+  const int f1 = L.co[1] ? 2 * J1 : J1, F1 = L.co[1] ? 2 * t1 + 1 : t1;
+  const int f2 = L.co[2] ? 2 * J2 : J2, F2 = L.co[2] ? 2 * t2 + 1 : t2;
+  const int total = F0 * F1 * F2;  // <= kResLds (mg_tile)
+  for (int t = threadIdx.x; t < total; t += kResThreads) {
+    const int l0 = t % F0, q = t / F0, l1 = q % F1, l2 = q / F1;
+    const int g0 = f0 + l0, g1 = f1 + l1, g2 = f2 + l2;
+    if (g0 < L.n[0] && g1 < L.n[1] && g2 < L.n[2]) {
+      const long i = g0 + (long)L.n[0] * (g1 + (long)L.n[1] * g2);
+      const auto row = op.template load_row<false>(i, g0, g1, g2);
+#pragma unroll
+      for (int c = 0; c < KC; ++c) {
+        if (!((live >> c) & 1u)) continue;
+        const double *__restrict__ xc = x + (size_t)(c0 + c) * ldx;
+        auto X = [&](long j, double) { return xc[j]; };
+        r[c][t] = b[(size_t)(c0 + c) * ldb + i] - op.ax_row(row, X, i, g0, g1, g2);
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < KC; ++c) r[c][t] = 0.0;
+    }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < t0 * t1 * t2) {
+    const int j0 = t % t0, q = t / t0, j1 = q % t1, j2 = q / t1;
+    if (J0 + j0 < L.nc[0] && J1 + j1 < L.nc[1] && J2 + j2 < L.nc[2]) {
+      const long jc = (J0 + j0) + (long)L.nc[0] * ((J1 + j1) + (long)L.nc[1] * (J2 + j2));
+#pragma unroll
+      for (int c = 0; c < KC; ++c) {
+        if (!((live >> c) & 1u)) continue;
+        const double *rc = r[c];
+        auto at = [&](int a0, int a1, int a2) { return rc[a0 + F0 * (a1 + F1 * a2)]; };
+        bc[(size_t)(c0 + c) * ldc + jc] = mg_restrict_point(L, at, j0, j1, j2);
+      }
+    }
+  }
+}
+
+// x += P e: one index split per point, then the columns
+template <int KC>
+__global__ __launch_bounds__(256) void mg_prolong_block_kernel(MgLevelArg L, long N, int k, const double *__restrict__ e,
+                                                               long lde, double *__restrict__ x, long ldx,
+                                                               const int *__restrict__ frozen) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const int c0 = blockIdx.y * KC;
+  const unsigned live = mg_live<KC>(c0, k, frozen);
+  if (i >= N || !live) return;
+  int i0, i1, i2;
+  mg_split(L, i, i0, i1, i2);
+#pragma unroll
+  for (int c = 0; c < KC; ++c) {
+    if (!((live >> c) & 1u)) continue;
+    const double *__restrict__ ec = e + (size_t)(c0 + c) * lde;
+    double *__restrict__ xc = x + (size_t)(c0 + c) * ldx;
+    auto E = [&](long j) { return ec[j]; };
+    xc[i] = xc[i] + mg_prolong_point(L, E, i0, i1, i2);
+  }
+}
+
 // ------------------------------------------------------------------ the tail: one workgroup, vectors in LDS
 
 // one sweep of a level in LDS: every thread forms its points' new values, then all are written
@@ -302,10 +454,9 @@ __device__ __forceinline__ void tail_sweep(const Op &op, int N, double *xs, cons
 // Op: MfOp<3> (each level's MgLevelArg copied into registers) or GTailOp (the level's GLevel stays in global memory, and
 // so do its coefficient arrays: 14 kTailT doubles for the top tail level alone do not fit LDS)
 template <class Op>
-__global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const TailArg<typename Op::Level> *__restrict__ T,
-                                                               const double *__restrict__ minv,
-                                                               const double *__restrict__ bin,
-                                                               double *__restrict__ xout) {
+__device__ __forceinline__ void mg_tail_body(const TailArg<typename Op::Level> *__restrict__ T,
+                                             const double *__restrict__ minv, const double *__restrict__ bin,
+                                             double *__restrict__ xout) {
   __shared__ double sh[kTailLds];
   double *const scr = sh + 4 * kTailT;
   double *const mi = sh + 5 * kTailT;
@@ -380,6 +531,26 @@ __global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const TailArg<typ
     const double *xs = sh + T->off[0];
     for (int i = tid; i < N; i += kTailThreads) xout[i] = xs[i];
   }
+}
+
+template <class Op>
+__global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const TailArg<typename Op::Level> *__restrict__ T,
+                                                               const double *__restrict__ minv,
+                                                               const double *__restrict__ bin,
+                                                               double *__restrict__ xout) {
+  mg_tail_body<Op>(T, minv, bin, xout);
+}
+
+// the block form: workgroup c runs the tail on column c's pointers; a frozen column's workgroup returns at once
+template <class Op>
+__global__ __launch_bounds__(kTailThreads) void mg_tail_block_kernel(const TailArg<typename Op::Level> *__restrict__ T,
+                                                                     const double *__restrict__ minv,
+                                                                     const double *__restrict__ bin, long ldb,
+                                                                     double *__restrict__ xout, long ldx,
+                                                                     const int *__restrict__ frozen) {
+  const int c = blockIdx.x;
+  if (frozen && frozen[c]) return;
+  mg_tail_body<Op>(T, minv, bin + (size_t)c * ldb, xout + (size_t)c * ldx);
 }
 
 // ------------------------------------------------------------------ the exact check at creation
@@ -477,6 +648,14 @@ struct psp_mg {
   bool galerkin = false;
   std::vector<GLevel> glev;
   std::vector<double *> coef;
+  // the level vectors of the block cycle (section 9e): per level what `lev` holds, for blk_cols columns of leading
+  // dimension N, and a spare for the finest level; allocated by the first block call, grown on demand
+  struct BlockLevel {
+    double *x = nullptr, *b = nullptr, *t = nullptr;
+  };
+  std::vector<BlockLevel> blk;
+  int blk_cols = 0;
+  size_t blk_bytes = 0;
 };
 
 namespace {
@@ -963,6 +1142,14 @@ void launch_restrict(const typename Op::Level &A, const double *x, const double 
 // in one pass over b), a further sweep, b_c = R (b - A x), the tail -- the cycle kernels with the mode's policy
 struct LevelOps {
   psp_mg *K;
+  using Vec = double *;
+  Vec lx(int l) const { return K->lev[l].x; }
+  Vec lb(int l) const { return K->lev[l].b; }
+  Vec lt(int l) const { return K->lev[l].t; }
+  void prolong(int l, const double *e, double *x) const {
+    const psp_mg::Level &L = K->lev[l];
+    hipLaunchKernelGGL(mg_prolong_kernel, dim3((unsigned)((L.N + 255) / 256)), dim3(256), 0, stream(), L.a, L.N, e, x);
+  }
   template <bool FROMB>
   int smooth(int l, const double *xin, const double *b, double *xout) const {
     const long N = K->lev[l].N;
@@ -1007,6 +1194,143 @@ struct LevelOps {
   }
 };
 
+// a block of vectors: column c at p + c * ld
+struct BVec {
+  double *p = nullptr;
+  long ld = 0;
+  const double *cp() const { return p; }
+  bool operator==(const BVec &o) const { return p == o.p; }
+  bool operator!=(const BVec &o) const { return p != o.p; }
+};
+
+// Columns per thread of the block kernels, by measurement (DESIGN.md section 9e has the register table and the figures).
+// The sweep, scale and prolongation kernels take groups of four columns with stored level operators, whose row of up to 27
+// coefficients is then loaded once for four columns, and of two in the matrix-free mode, which has nothing to share
+// but the index split (two where k <= 2 in both).  The restriction takes ONE column per workgroup (kBlockKCR = 1, the
+// columns in gridDim.y): holding 2 or 4 residual tiles in LDS to share the rows was 5 to 22 % and 40 to 70 % slower.
+constexpr int kBlockKCGalerkin = 4;
+constexpr int kBlockKCMatrixFree = 2;
+constexpr int kBlockKCR = 1;
+// op_apply_block and psp_pcg_batch run the block cycle in these modes (section 9e's routing decision)
+constexpr bool kRouteBlockMatrixFree = true;
+constexpr bool kRouteBlockGalerkin = true;
+
+int block_tuning(const char *name, int dflt, std::initializer_list<int> allowed) {
+  const char *e = tuning_env(name);
+  if (!e) return dflt;
+  const int v = atoi(e);
+  for (int a : allowed)
+    if (a == v) return v;
+  return dflt;
+}
+
+// the block cycle's launches: LevelOps with the column count, the leading dimensions and the frozen flags
+struct BlockOps {
+  psp_mg *K;
+  int k;
+  const int *frozen;
+  int kc, kcr;
+  using Vec = BVec;
+  BlockOps(psp_mg *K_, int k_, const int *frozen_) : K(K_), k(k_), frozen(frozen_) {
+    kc = k <= 2 ? 2 : block_tuning("PSP_MG_BLOCK_KC", K->galerkin ? kBlockKCGalerkin : kBlockKCMatrixFree, {2, 4});
+    kcr = k == 1 ? 1 : block_tuning("PSP_MG_BLOCK_KCR", kBlockKCR, {1, 2, 4});
+  }
+  Vec lx(int l) const { return BVec{K->blk[l].x, K->lev[l].N}; }
+  Vec lb(int l) const { return BVec{K->blk[l].b, K->lev[l].N}; }
+  Vec lt(int l) const { return BVec{K->blk[l].t, K->lev[l].N}; }
+  dim3 grid(long N) const { return dim3((unsigned)((N + 255) / 256), (unsigned)((k + kc - 1) / kc)); }
+
+  template <class Op, bool FROMB>
+  void launch_smooth(const typename Op::Level &A, long N, BVec xin, BVec b, BVec xout) const {
+    if (kc == 4)
+      hipLaunchKernelGGL((mg_smooth_block_kernel<Op, FROMB, 4>), grid(N), dim3(256), 0, stream(), A, N, k, xin.cp(), xin.ld,
+                         b.cp(), b.ld, xout.p, xout.ld, frozen);
+    else
+      hipLaunchKernelGGL((mg_smooth_block_kernel<Op, FROMB, 2>), grid(N), dim3(256), 0, stream(), A, N, k, xin.cp(), xin.ld,
+                         b.cp(), b.ld, xout.p, xout.ld, frozen);
+  }
+  template <bool FROMB>
+  int smooth(int l, BVec xin, BVec b, BVec xout) const {
+    const long N = K->lev[l].N;
+    if (K->galerkin) {
+      const GLevel &G = K->glev[l];
+      return g_dispatch(G, [&](auto sh) { launch_smooth<GOp<sh.nd, sh.noff>, FROMB>(G, N, xin, b, xout); });
+    }
+    const MgLevelArg &a = K->lev[l].a;
+    switch (level_nd(a)) {
+      case 1: launch_smooth<MfOp<1>, FROMB>(a, N, xin, b, xout); break;
+      case 2: launch_smooth<MfOp<2>, FROMB>(a, N, xin, b, xout); break;
+      default: launch_smooth<MfOp<3>, FROMB>(a, N, xin, b, xout); break;
+    }
+    return PSP_OK;
+  }
+  template <class W>
+  void launch_scale(long N, W w, BVec b, BVec dst) const {
+    if (kc == 4)
+      hipLaunchKernelGGL((mg_scale_block_kernel<W, 4>), grid(N), dim3(256), 0, stream(), N, w, k, b.cp(), b.ld, dst.p, dst.ld,
+                         frozen);
+    else
+      hipLaunchKernelGGL((mg_scale_block_kernel<W, 2>), grid(N), dim3(256), 0, stream(), N, w, k, b.cp(), b.ld, dst.p, dst.ld,
+                         frozen);
+  }
+  int first(int l, BVec b, BVec dst) const {
+    if (K->steps > 1) return smooth<true>(l, BVec(), b, dst);
+    const long N = K->lev[l].N;
+    if (K->galerkin)
+      launch_scale(N, GW{K->glev[l].w}, b, dst);
+    else
+      launch_scale(N, MfW{K->lev[l].a.w}, b, dst);
+    return PSP_OK;
+  }
+  int sweep(int l, BVec xin, BVec b, BVec xout) const { return smooth<false>(l, xin, b, xout); }
+
+  template <class Op, int KCR>
+  void launch_restrict_kc(const typename Op::Level &A, BVec x, BVec b, BVec bc) const {
+    const MgLevelArg &a = level_geo(A);
+    int tile[3];
+    mg_tile(a, tile);
+    const long g0n = (a.nc[0] + tile[0] - 1) / tile[0], g1n = (a.nc[1] + tile[1] - 1) / tile[1],
+               g2n = (a.nc[2] + tile[2] - 1) / tile[2];
+    hipLaunchKernelGGL((mg_restrict_block_kernel<Op, KCR>), dim3((unsigned)(g0n * g1n * g2n), (unsigned)((k + KCR - 1) / KCR)),
+                       dim3(kResThreads), 0, stream(), A, tile[0], tile[1], tile[2], (int)g0n, (int)g1n, k, x.cp(), x.ld,
+                       b.cp(), b.ld, bc.p, bc.ld, frozen);
+  }
+  template <class Op>
+  void launch_restrict(const typename Op::Level &A, BVec x, BVec b, BVec bc) const {
+    if (kcr == 4)
+      launch_restrict_kc<Op, 4>(A, x, b, bc);
+    else if (kcr == 2)
+      launch_restrict_kc<Op, 2>(A, x, b, bc);
+    else
+      launch_restrict_kc<Op, 1>(A, x, b, bc);
+  }
+  int restrict_to(int l, BVec x, BVec b, BVec bc) const {
+    if (K->galerkin) {
+      const GLevel &G = K->glev[l];
+      return g_dispatch(G, [&](auto sh) { launch_restrict<GOp<sh.nd, sh.noff>>(G, x, b, bc); });
+    }
+    launch_restrict<MfOp<3>>(K->lev[l].a, x, b, bc);
+    return PSP_OK;
+  }
+  void tail(BVec b, BVec x) const {
+    if (K->galerkin)
+      hipLaunchKernelGGL(mg_tail_block_kernel<GTailOp>, dim3(k), dim3(kTailThreads), 0, stream(),
+                         (const TailArg<GLevel> *)K->tail, (const double *)K->minv, b.cp(), b.ld, x.p, x.ld, frozen);
+    else
+      hipLaunchKernelGGL(mg_tail_block_kernel<MfOp<3>>, dim3(k), dim3(kTailThreads), 0, stream(),
+                         (const TailArg<MgLevelArg> *)K->tail, (const double *)K->minv, b.cp(), b.ld, x.p, x.ld, frozen);
+  }
+  void prolong(int l, BVec e, BVec x) const {
+    const psp_mg::Level &L = K->lev[l];
+    if (kc == 4)
+      hipLaunchKernelGGL(mg_prolong_block_kernel<4>, grid(L.N), dim3(256), 0, stream(), L.a, L.N, k, e.cp(), e.ld, x.p, x.ld,
+                         frozen);
+    else
+      hipLaunchKernelGGL(mg_prolong_block_kernel<2>, grid(L.N), dim3(256), 0, stream(), L.a, L.N, k, e.cp(), e.ld, x.p, x.ld,
+                         frozen);
+  }
+};
+
 // the sss entry points: an sss_mat is read through its full device mirror
 int mg_create_sss(psp_sss_t *A, const char *fn, int (*create)(psp_csr *, int, const int *, double, int, psp_mg **), int ndim,
                   const int *grid, double omega, int steps, psp_mg **out) {
@@ -1018,48 +1342,47 @@ int mg_create_sss(psp_sss_t *A, const char *fn, int (*create)(psp_csr *, int, co
   return create(A->full, ndim, grid, omega, steps, out);
 }
 
-// one V-cycle: the schedule of launches and buffers, the same in both modes
+// one V-cycle: the schedule of launches and buffers, the same in both modes and for one vector (Ops::Vec = double *) or a
+// block of them (BVec): K->launches launches whatever the column count is.  b_dev is only read.
 template <class Ops>
-int mg_schedule(psp_mg *K, const double *b_dev, double *y_dev, const Ops &ops) {
+int mg_schedule(psp_mg *K, typename Ops::Vec b_dev, typename Ops::Vec y_dev, const Ops &ops) {
+  using V = typename Ops::Vec;
   const int steps = K->steps, tf = K->tail_first;
   // where each large level's iterate is after its pre-smoothing; every sweep writes the buffer the previous one did not
-  double *cur[kMaxLevels] = {};
+  V cur[kMaxLevels] = {};
   // down
   for (int l = 0; l < tf; ++l) {
-    const psp_mg::Level &L = K->lev[l];
-    const double *b = l == 0 ? b_dev : L.b;
-    double *const own = l == 0 ? y_dev : L.x;
+    const V b = l == 0 ? b_dev : ops.lb(l);
+    const V own = l == 0 ? y_dev : ops.lx(l);
     // the finest level's last sweep must land in y: its writes are the pre-smoothing launches and `steps` more
     const int writes = (steps >= 2 ? steps - 1 : 1) + steps;
-    double *dst = (l == 0 && (writes & 1) == 0) ? L.t : own;
+    V dst = (l == 0 && (writes & 1) == 0) ? ops.lt(l) : own;
     PSP_TRY(ops.first(l, b, dst));
     for (int k = 2; k < steps; ++k) {
-      double *nxt = dst == own ? L.t : own;
+      V nxt = dst == own ? ops.lt(l) : own;
       PSP_TRY(ops.sweep(l, dst, b, nxt));
       dst = nxt;
     }
     cur[l] = dst;
-    PSP_TRY(ops.restrict_to(l, dst, b, K->lev[l + 1].b));
+    PSP_TRY(ops.restrict_to(l, dst, b, ops.lb(l + 1)));
     PSP_LAUNCH_CHECK();
   }
   // the tail
   {
-    const double *b = tf == 0 ? b_dev : K->lev[tf].b;
-    double *x = tf == 0 ? y_dev : K->lev[tf].x;
+    const V b = tf == 0 ? b_dev : ops.lb(tf);
+    V x = tf == 0 ? y_dev : ops.lx(tf);
     ops.tail(b, x);
     PSP_LAUNCH_CHECK();
     cur[tf] = x;
   }
   // up
   for (int l = tf - 1; l >= 0; --l) {
-    const psp_mg::Level &L = K->lev[l];
-    const double *b = l == 0 ? b_dev : L.b;
-    double *const own = l == 0 ? y_dev : L.x;
-    double *x = cur[l];
-    hipLaunchKernelGGL(mg_prolong_kernel, dim3((unsigned)((L.N + 255) / 256)), dim3(256), 0, stream(), L.a, L.N,
-                       (const double *)cur[l + 1], x);
+    const V b = l == 0 ? b_dev : ops.lb(l);
+    const V own = l == 0 ? y_dev : ops.lx(l);
+    V x = cur[l];
+    ops.prolong(l, cur[l + 1], x);
     for (int k = 0; k < steps; ++k) {
-      double *nxt = x == own ? L.t : own;
+      V nxt = x == own ? ops.lt(l) : own;
       PSP_TRY(ops.sweep(l, x, b, nxt));
       x = nxt;
     }
@@ -1070,14 +1393,65 @@ int mg_schedule(psp_mg *K, const double *b_dev, double *y_dev, const Ops &ops) {
   return PSP_OK;
 }
 
+void mg_block_free(psp_mg *K) {
+  for (psp_mg::BlockLevel &B : K->blk)
+    for (void *p : {(void *)B.x, (void *)B.b, (void *)B.t}) (void)hipFree(p);
+  K->blk.clear();
+  K->blk_cols = 0;
+  K->blk_bytes = 0;
+}
+
+// the block cycle's level vectors for at least k columns (k = 0: none); what mg_alloc_vectors allocates, k columns wide.
+// hipFree waits for the device, so nothing that still runs loses its buffers.
+int mg_block_reserve(psp_mg *K, int k) {
+  if (k == 0) {
+    mg_block_free(K);
+    return PSP_OK;
+  }
+  if (k <= K->blk_cols) return PSP_OK;
+  mg_block_free(K);
+  K->blk.resize(K->lev.size());
+  for (int l = 0; l <= K->tail_first; ++l) {
+    psp_mg::BlockLevel &B = K->blk[l];
+    const size_t bytes = sizeof(double) * (size_t)K->lev[l].N * (size_t)k;
+    hipError_t e = hipSuccess;
+    size_t got = 0;
+    if (l < K->tail_first) e = hipMalloc((void **)&B.t, bytes), got += e == hipSuccess ? bytes : 0;
+    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&B.x, bytes), got += e == hipSuccess ? bytes : 0;
+    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&B.b, bytes), got += e == hipSuccess ? bytes : 0;
+    K->blk_bytes += got;
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      mg_block_free(K);
+      return fail(PSP_ENOMEM, "multigrid: block level vector allocation failed (%d columns)", k);
+    }
+  }
+  K->blk_cols = k;
+  return PSP_OK;
+}
+
 }  // namespace
 
 namespace psp {
 
 // y = V(0, b) on device vectors; y must not alias b.  The handle is locked by the caller.
 int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
-  return mg_schedule(K, b_dev, y_dev, LevelOps{K});
+  return mg_schedule(K, const_cast<double *>(b_dev), y_dev, LevelOps{K});
 }
+
+// Y[:, c] = V(0, X[:, c]) for every column c < k with frozen[c] == 0 (frozen == nullptr: every column), one block cycle:
+// the bits of mg_apply_dev on the column, K's launches whatever k is.  Y must not overlap X.  The handle is locked by the
+// caller.
+int mg_apply_block_dev(psp_mg *K, int k, const double *X, long ldx, double *Y, long ldy, const int *frozen) {
+  PSP_TRY(mg_block_reserve(K, k));
+  return mg_schedule(K, BVec{const_cast<double *>(X), ldx}, BVec{Y, ldy}, BlockOps(K, k, frozen));
+}
+
+int mg_launches(const psp_mg *K) { return K->launches; }
+
+// Where op_apply_block and the batched PCG loop run the block cycle and where they keep the column-by-column path: by the
+// measurements of DESIGN.md section 9e (profiles/mg_block_timing.json).
+bool mg_block_routed(const psp_mg *K) { return K->galerkin ? kRouteBlockGalerkin : kRouteBlockMatrixFree; }
 
 }  // namespace psp
 
@@ -1135,6 +1509,7 @@ int psp_mg_level_operator(psp_mg_t *K, int level, int *offsets_out, int *noff_in
 
 int psp_mg_destroy(psp_mg_t *K) {
   if (!K) return PSP_OK;
+  mg_block_free(K);
   for (double *p : K->coef) (void)hipFree(p);
   for (psp_mg::Level &L : K->lev)
     for (void *p : {(void *)L.x, (void *)L.b, (void *)L.t}) (void)hipFree(p);
@@ -1193,6 +1568,59 @@ int psp_mg_precon(psp_mg_t *K, const double *x_host, double *y_host) {
   if (rc != PSP_OK) return rc;
   if (e != hipSuccess || e2 != hipSuccess)
     return fail(PSP_ENODEV, "psp_mg_precon: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+  return PSP_OK;
+}
+
+int psp_mg_precon_block_dev(psp_mg_t *K, int k, const double *X_dev, long ldx, double *Y_dev, long ldy) {
+  PSP_API_GUARD_H(K);
+  if (cpu_mode()) return fail(PSP_ENODEV, "psp_mg_precon_block_dev: not available with PSP_DEVICE=cpu");
+  if (!K) return fail(PSP_EINVAL, "psp_mg_precon_block_dev: NULL handle");
+  PSP_TRY(block_args("psp_mg_precon_block_dev", K->n, K->n, k, X_dev, ldx, Y_dev, ldy));
+  PSP_TRY(ensure_device());
+  return mg_apply_block_dev(K, k, X_dev, ldx, Y_dev, ldy, nullptr);
+}
+
+int psp_mg_precon_block(psp_mg_t *K, int k, const double *X_host, long ldx, double *Y_host, long ldy) {
+  PSP_API_GUARD_H(K);
+  if (cpu_mode()) return fail(PSP_ENODEV, "psp_mg_precon_block: not available with PSP_DEVICE=cpu");
+  if (!K) return fail(PSP_EINVAL, "psp_mg_precon_block: NULL handle");
+  PSP_TRY(block_args("psp_mg_precon_block", K->n, K->n, k, X_host, ldx, Y_host, ldy));
+  PSP_TRY(ensure_device());
+  const size_t n = (size_t)K->n, nk = n * (size_t)k, row = sizeof(double) * n;
+  double *x = nullptr, *y = nullptr;
+  PSP_TRY(scratch_get(nk, &x));
+  int rc = scratch_get(nk, &y);
+  if (rc != PSP_OK) {
+    scratch_put(x, nk);
+    return rc;
+  }
+  hipError_t e = hipMemcpy2DAsync(x, row, X_host, sizeof(double) * ldx, row, k, hipMemcpyHostToDevice, stream());
+  if (e == hipSuccess) rc = mg_apply_block_dev(K, k, x, (long)n, y, (long)n, nullptr);
+  if (e == hipSuccess && rc == PSP_OK)
+    e = hipMemcpy2DAsync(Y_host, sizeof(double) * ldy, y, row, row, k, hipMemcpyDeviceToHost, stream());
+  const hipError_t e2 = hipStreamSynchronize(stream());
+  scratch_put(x, nk);
+  scratch_put(y, nk);
+  if (rc != PSP_OK) return rc;
+  if (e != hipSuccess || e2 != hipSuccess)
+    return fail(PSP_ENODEV, "psp_mg_precon_block: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+  return PSP_OK;
+}
+
+int psp_mg_block_reserve(psp_mg_t *K, int k) {
+  PSP_API_GUARD_H(K);
+  if (cpu_mode()) return fail(PSP_ENODEV, "psp_mg_block_reserve: not available with PSP_DEVICE=cpu");
+  if (!K) return fail(PSP_EINVAL, "psp_mg_block_reserve: NULL handle");
+  if (k < 0) return fail(PSP_EINVAL, "psp_mg_block_reserve: k = %d columns", k);
+  PSP_TRY(ensure_device());
+  return mg_block_reserve(K, k);
+}
+
+int psp_mg_block_info(psp_mg_t *K, int *columns, long long *bytes) {
+  PSP_API_GUARD_H(K);
+  if (!K) return fail(PSP_EINVAL, "psp_mg_block_info: NULL handle");
+  if (columns) *columns = K->blk_cols;
+  if (bytes) *bytes = (long long)K->blk_bytes;
   return PSP_OK;
 }
 

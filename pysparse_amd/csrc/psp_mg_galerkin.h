@@ -112,6 +112,18 @@ __device__ __forceinline__ double g_ax_rt(const GLevel &L, const X &x, int i, in
   return acc;
 }
 
+// One row of a stored level in registers, for the block kernels: the diagonal, omega / diagonal, and
+// per stored offset the lower coupling (the array at i) and the upper one (the array at i - o), 0 where the neighbour
+// does not exist (mlo / mup say which do).  WN: also omega / diagonal of every neighbour, which the fused first pass
+// (xin = w .* b formed on the fly) multiplies the neighbours' b by.  Every index is a compile-time constant.
+template <int NOFF, bool WN>
+struct GRow {
+  double d, w;
+  double lo[NOFF], up[NOFF];
+  double wlo[WN ? NOFF : 1], wup[WN ? NOFF : 1];
+  unsigned mlo, mup;
+};
+
 // The level-operator policies of the stored mode.  GOp: the launch-per-step kernels, the level's shape in the type (g_ax).
 template <int ND, int NOFF>
 struct GOp {
@@ -122,6 +134,48 @@ struct GOp {
   template <class X>
   __device__ __forceinline__ double ax(const X &x, long i, int i0, int i1, int i2) const {
     return g_ax<ND, NOFF>(G, x, i, i0, i1, i2);
+  }
+  // "load the row, then apply it to a column": every load of a coefficient happens in load_row, ax_row reads only the
+  // column (x(j, w_j) is the column's value at j; w_j = omega / diagonal at j, 0.0 unless the row was loaded with WN).
+  // The terms and their order are g_ax's.
+  template <bool WN>
+  __device__ __forceinline__ GRow<NOFF, WN> load_row(long i, int i0, int i1, int i2) const {
+    GRow<NOFF, WN> r;
+    r.d = G.diag[i];
+    r.w = G.w[i];
+    r.mlo = r.mup = 0u;
+    const int n0 = G.a.n[0], n1 = G.a.n[1], n2 = G.a.n[2];
+    g_for<0, NOFF>([&](auto kc) {
+      constexpr int k = decltype(kc)::value;
+      constexpr int d0 = g_d(ND, NOFF, k, 0), d1 = g_d(ND, NOFF, k, 1), d2 = g_d(ND, NOFF, k, 2);
+      const long o = d0 + (long)n0 * (d1 + (long)n1 * d2);
+      const bool inl = g_in<d0>(i0, n0) && g_in<d1>(i1, n1) && g_in<d2>(i2, n2);
+      const bool inu = g_in<-d0>(i0, n0) && g_in<-d1>(i1, n1) && g_in<-d2>(i2, n2);
+      r.lo[k] = inl ? G.lo[k][i] : 0.0;
+      r.up[k] = inu ? G.lo[k][i - o] : 0.0;
+      if (inl) r.mlo |= 1u << k;
+      if (inu) r.mup |= 1u << k;
+      if constexpr (WN) {
+        r.wlo[k] = inl ? G.w[i + o] : 0.0;
+        r.wup[k] = inu ? G.w[i - o] : 0.0;
+      }
+    });
+    return r;
+  }
+  template <bool WN, class X>
+  __device__ __forceinline__ double ax_row(const GRow<NOFF, WN> &r, const X &x, long i, int, int, int) const {
+    double acc = r.d * x(i, r.w);
+    const int n0 = G.a.n[0], n1 = G.a.n[1];
+    g_for<0, NOFF>([&](auto kc) {
+      constexpr int k = decltype(kc)::value;
+      constexpr int d0 = g_d(ND, NOFF, k, 0), d1 = g_d(ND, NOFF, k, 1), d2 = g_d(ND, NOFF, k, 2);
+      const long o = d0 + (long)n0 * (d1 + (long)n1 * d2);
+      double wl = 0.0, wu = 0.0;
+      if constexpr (WN) wl = r.wlo[k], wu = r.wup[k];
+      if ((r.mlo >> k) & 1u) acc += r.lo[k] * x(i + o, wl);
+      if ((r.mup >> k) & 1u) acc += r.up[k] * x(i - o, wu);
+    });
+    return acc;
   }
   __device__ __forceinline__ double w(long i) const { return G.w[i]; }
   __device__ __forceinline__ void split(long i, int &i0, int &i1, int &i2) const { mg_split<ND>(G.a, i, i0, i1, i2); }

@@ -237,7 +237,9 @@ int launch_spmm_rows(const psp_csr *A, int k, const double *X, long ldx, double 
   return PSP_OK;
 }
 
-bool ranges_overlap(const double *a, size_t na, const double *b, size_t nb) {
+}  // namespace
+
+static bool ranges_overlap(const double *a, size_t na, const double *b, size_t nb) {
   const uintptr_t a0 = (uintptr_t)a, a1 = a0 + sizeof(double) * na, b0 = (uintptr_t)b, b1 = b0 + sizeof(double) * nb;
   return a0 < b1 && b0 < a1;
 }
@@ -252,8 +254,6 @@ int block_args(const char *what, int nrows, int ncols, int k, const double *X, l
     return fail(PSP_EINVAL, "%s: X and Y overlap", what);
   return PSP_OK;
 }
-
-}  // namespace
 
 int csr_spmm_check(const char *what, const psp_csr *A) {
   if (!A) return fail(PSP_EINVAL, "%s: NULL handle", what);
@@ -308,7 +308,7 @@ int jacobi_block_dev(const psp_jacobi *K, int k, const double *X, long ldx, doub
   return PSP_OK;
 }
 
-int op_apply_block(const psp_op *op, int k, const double *X, long ldx, double *Y, long ldy) {
+int op_apply_block(const psp_op *op, int k, const double *X, long ldx, double *Y, long ldy, const int *frozen) {
   if (op->kind == PSP_OP_CSR || op->kind == PSP_OP_SSS) {
     const psp_csr *A = op_native_csr(op);
     PSP_TRY(csr_spmm_check("op_apply_block", A));
@@ -316,6 +316,7 @@ int op_apply_block(const psp_op *op, int k, const double *X, long ldx, double *Y
   }
   if (op->kind == PSP_OP_JACOBI && op->jac && op->jac->steps == 1 && !op->jac->multi && !op->jac->host)
     return jacobi_block_dev(op->jac, k, X, ldx, Y, ldy);
+  if (op->kind == PSP_OP_MG && op->mg && mg_block_routed(op->mg)) return mg_apply_block_dev(op->mg, k, X, ldx, Y, ldy, frozen);
   for (int c = 0; c < k; ++c) PSP_TRY(op_apply(op, X + (size_t)c * ldx, Y + (size_t)c * ldy));
   return PSP_OK;
 }

@@ -633,6 +633,24 @@ class DeviceMultigrid:
     def precon_dev(self, x_ptr, y_ptr):
         check(lib().psp_mg_precon_dev(self._h, x_ptr, y_ptr))
 
+    def precon_block(self, X, Y):
+        """Y[:, c] = K X[:, c] for every column in one block cycle (psp_mg_precon_block): X, Y (n, k),
+        2-D float64 with any strides.  Column c has the bits of precon on X[:, c]; the launches do not grow with k."""
+        _matmat(lib().psp_mg_precon_block, self._h, self.shape, X, Y)
+
+    def precon_block_dev(self, k, x_ptr, ldx, y_ptr, ldy):
+        _check_einval(lib().psp_mg_precon_block_dev(self._h, int(k), x_ptr, int(ldx), y_ptr, int(ldy)))
+
+    def block_reserve(self, k):
+        """allocate the block cycle's level vectors for at least k columns ahead of the first call; k = 0 frees them"""
+        _check_einval(lib().psp_mg_block_reserve(self._h, int(k)))
+
+    def block_info(self):
+        """{"columns", "bytes"}: what the block cycle's level vectors hold now (0, 0 before the first block call)"""
+        cols, nbytes = C.c_int(), C.c_longlong()
+        check(lib().psp_mg_block_info(self._h, C.byref(cols), C.byref(nbytes)))
+        return {"columns": cols.value, "bytes": nbytes.value}
+
     def close(self):
         if getattr(self, "_h", None):
             lib().psp_mg_destroy(self._h)

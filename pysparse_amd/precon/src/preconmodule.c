@@ -382,6 +382,51 @@ static PyObject *MG_precon(MGObject *self, PyObject *args) {
   Py_RETURN_NONE;
 }
 
+/* self.precon_block(X, Y): Y[:, c] := K X[:, c] for every column in one block cycle (psp_mg_precon_block).  X and Y are
+ * (n, k) double arrays with any strides, staged as column-major blocks like a.matmat(X, Y); Y is written back in place. */
+static PyObject *MG_precon_block(MGObject *self, PyObject *args) {
+  PyArrayObject *xp, *yp, *xf = NULL, *yf = NULL;
+  PyObject *result = NULL;
+  npy_intp dims[2];
+  int rc, k;
+  if (!PyArg_ParseTuple(args, "O!O!", &PyArray_Type, &xp, &PyArray_Type, &yp)) return NULL;
+  if (PyArray_NDIM(xp) != 2 || PyArray_TYPE(xp) != NPY_DOUBLE || PyArray_DIM(xp, 0) != self->n || PyArray_DIM(xp, 1) < 1 ||
+      PyArray_DIM(xp, 1) > 0x7fffffff) {
+    PyErr_SetString(PyExc_ValueError, "arg 1 must be a 2-dimensional double array of appropriate size.");
+    return NULL;
+  }
+  if (PyArray_NDIM(yp) != 2 || PyArray_TYPE(yp) != NPY_DOUBLE || PyArray_DIM(yp, 0) != self->n ||
+      PyArray_DIM(yp, 1) != PyArray_DIM(xp, 1)) {
+    PyErr_SetString(PyExc_ValueError, "arg 2 must be a 2-dimensional double array of appropriate size.");
+    return NULL;
+  }
+  if (!PyArray_ISWRITEABLE(yp)) {
+    PyErr_SetString(PyExc_ValueError, "arg 2 must be writeable.");
+    return NULL;
+  }
+  k = (int)PyArray_DIM(xp, 1);
+  xf = (PyArrayObject *)PyArray_FromArray(xp, NULL, NPY_ARRAY_F_CONTIGUOUS | NPY_ARRAY_ALIGNED);
+  dims[0] = self->n;
+  dims[1] = k;
+  yf = (PyArrayObject *)PyArray_EMPTY(2, dims, NPY_DOUBLE, 1); /* never X's memory: the cycle is out of place */
+  if (!xf || !yf) goto done;
+  Py_BEGIN_ALLOW_THREADS
+  rc = psp_mg_precon_block(self->dev, k, (const double *)PyArray_DATA(xf), (long)self->n, (double *)PyArray_DATA(yf),
+                           (long)self->n);
+  Py_END_ALLOW_THREADS
+  if (rc != PSP_OK) {
+    raise_psp(rc);
+    goto done;
+  }
+  if (PyArray_CopyInto(yp, yf) < 0) goto done;
+  result = Py_None;
+  Py_INCREF(result);
+done:
+  Py_XDECREF(xf);
+  Py_XDECREF(yf);
+  return result;
+}
+
 static void MG_dealloc(MGObject *self) {
   if (self->op) psp_op_destroy(self->op);
   if (self->dev) psp_mg_destroy(self->dev);
@@ -434,6 +479,9 @@ static PyObject *MG_get_galerkin(MGObject *self, void *c) {
 static PyMethodDef MG_methods[] = {
     {"precon", (PyCFunction)MG_precon, METH_VARARGS,
      "self.precon(x, y)\n\napply preconditioner self on x, store result in y. x is unchanged."},
+    {"precon_block", (PyCFunction)MG_precon_block, METH_VARARGS,
+     "self.precon_block(X, Y)\n\nY[:, c] := K X[:, c] for every column of the (n, k) arrays in one block cycle; column c has "
+     "the bits of precon on X[:, c]. X is unchanged."},
     {NULL, NULL, 0, NULL}};
 
 static PyGetSetDef MG_getset[] = {{"shape", (getter)MG_get_shape, NULL, "(n, n)", NULL},
