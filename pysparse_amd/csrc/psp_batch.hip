@@ -18,7 +18,8 @@
 // Bit equality with psp_pcg, column by column: the element a thread owns (2t, 2t+1 of a 512-row span), the order in which
 // it adds, the wave tree, the four waves left to right and reduce_block over the spans are those of dot_kernel,
 // residual_kernel, x_update_kernel, r_update_kernel (psp_vec.hip) and of csr_spmv_w4's fused dot; the scalar steps are
-// pcg_scalar_pq / pcg_scalar_xr of psp_solvers.hip applied to one column's state.  One exception is followed on purpose:
+// pcg_head / pcg_alpha / pcg_tail of psp_recur.h -- the ones every loop of psp_pcg takes -- applied to one column's
+// state.  One exception is followed on purpose:
 // a small system that psp_pcg hands to the one-kernel loop of psp_coop.hip is reduced in that loop's own order (a row per
 // thread, wave sums, the 16 waves of a workgroup of 1024 rows, then the workgroups, each left to right), because that is
 // what the single solve of such a system computes; p.q is then a batched dot of its own behind the block product (six
@@ -47,11 +48,8 @@ typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
 constexpr int kBlock = 256;
 constexpr int kMaxN = 1 << 25;  // 65 536 spans: what ONE finishing workgroup adds in the canonical order (psp_internal.h)
 
-// one column's recurrence on the device (PcgDev of psp_solvers.hip without the lazy loop's fields)
-struct BatchCol {
-  double rho, rho1, alpha, beta, normr, tolb, n2b, relres;
-  int info, iter, stag, it, maxit, pad;
-};
+// one column's recurrence on the device: PcgCol of psp_recur.h
+using BatchCol = PcgCol;
 
 // per thread: partial sums (3 values x k columns x spans), the columns' states and their frozen flags, with a pinned
 // mirror of both; for the stream the thread used last (as psp_bvec.hip's set).  psp_trim releases it (batch_trim).
@@ -291,29 +289,6 @@ __global__ __launch_bounds__(kBlock) void bxr_kernel(long n, int k, const double
 
 // ---------------------------------------------------------------- scalar steps, one column each
 
-__device__ __forceinline__ void col_finish(BatchCol *s, int *frozen, int code, int iter) {
-  *frozen = 1;
-  s->info = code;
-  s->iter = iter;
-  s->relres = s->normr / s->n2b;  // pcg.c:166
-}
-
-// pcg.c:99-112 at the head of iteration s->it with the new rho
-__device__ __forceinline__ void col_head(BatchCol *s, int *frozen, double rho) {
-  const double rho1 = s->rho;
-  s->rho1 = rho1;
-  s->rho = rho;
-  if (rho == 0.0) {
-    col_finish(s, frozen, -2, s->it);
-  } else if (s->it > 1) {
-    const double beta = rho / rho1;
-    if (beta == 0.0)
-      col_finish(s, frozen, -6, s->it);
-    else
-      s->beta = beta;
-  }
-}
-
 enum { kStepHead = 0, kStepPq = 1, kStepXr = 2 };
 
 // one workgroup per column: the column's values in reduce_block's order, then the step that waits for them.
@@ -355,34 +330,17 @@ __global__ __launch_bounds__(kReduceBlock) void bfinish_kernel(const double *__r
     reduce_block(parts + (size_t)c * pstride, nparts, NV, (int)((long)k * pstride), true, out, sh);
   }
   if (threadIdx.x != 0) return;
-  BatchCol *s = st + c;
+  // the column's step (psp_recur.h); an exit freezes the column
+  BatchCol &s = st[c];
+  bool over;
   if constexpr (STEP == kStepHead) {
-    col_head(s, frozen + c, out[0]);
-  } else if constexpr (STEP == kStepPq) {  // pcg.c:117-125
-    const double pq = out[0];
-    if (pq == 0.0) {
-      col_finish(s, frozen + c, -6, s->it);
-      return;
-    }
-    const double alpha = s->rho / pq;
-    s->alpha = alpha;
-    if (alpha == 0.0) s->stag = 1;
-  } else {  // pcg.c:127-162
-    const int it = s->it;
-    if (s->stag == 0) s->stag = (out[2] == 0.0) ? 1 : 0;
-    const double normr = sqrt(out[0]);
-    s->normr = normr;
-    if (normr <= s->tolb) {
-      col_finish(s, frozen + c, 0, it);
-    } else if (s->stag == 1) {
-      col_finish(s, frozen + c, -5, it);
-    } else if (it == s->maxit) {
-      col_finish(s, frozen + c, -1, it + 1);  // pcg.c:165: the loop ran out
-    } else {
-      s->it = it + 1;
-      if (fused) col_head(s, frozen + c, out[1]);
-    }
+    over = pcg_head(s, out[0]);
+  } else if constexpr (STEP == kStepPq) {
+    over = pcg_alpha(s, out[0]);
+  } else {
+    over = pcg_tail(s, sqrt(out[0]), out[2] == 0.0) || (fused && pcg_head(s, out[1]));
   }
+  if (over) frozen[c] = 1;
 }
 
 // out[v*k + c] = value v of column c, nothing else (the set-up's norms)

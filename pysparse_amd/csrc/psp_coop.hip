@@ -12,6 +12,9 @@
 // reduction, and a thread forms the entries of p (resp. v) it multiplies with itself from the gathered values -- the
 // owner's own rounded operations on the same operands, hence the same bits.  Every workgroup evaluates the scalar
 // recurrences itself from the same reduced values, so all of them take the same branch and leave the loop together.
+// The recurrences are INLINE COPIES of psp_recur.h's pcg_head / pcg_alpha / pcg_tail and minres_alpha / minres_rotate:
+// calling the shared functions on a local struct changes the registers and the scratch of both kernels
+// (profiles/recur_resources.txt).  A change to an exit rule there is a change here.
 //
 // Arithmetic: per element the reference's operations, multiply and add rounded separately (-ffp-contract=off); a row's
 // products are added left to right (csr_mat.c:49-54); a reduction is: a thread adds its rows in ascending order, the
@@ -203,6 +206,7 @@ __global__ __launch_bounds__(kCoopBlock) void pcg_coop_kernel(int n, int nwg, co
   double rho = rho0, rho1 = 1.0, normr = normr0, alpha, beta = 0.0;
   int flag = -1, it;
   for (it = 1; it <= maxit; ++it) {
+    // (pcg_head's expressions, psp_recur.h; inline copy -- as pcg_alpha's and pcg_tail's below)
     if (rho == 0.0) {  // pcg.c:101-104
       flag = -2;
       break;
@@ -362,7 +366,7 @@ __global__ __launch_bounds__(kCoopBlock) void minres_coop_kernel(int n, int nwg,
       break;
     }
     beta = sqrt(beta);
-    const double c_oold = c_old, s_oold = s_old;  // :151-164
+    const double c_oold = c_old, s_oold = s_old;  // :151-164 (minres_rotate's expressions, psp_recur.h; inline copy)
     c_old = c;
     s_old = s;
     const double r1_hat = c_old * alpha - c_oold * s_old * beta_old;

@@ -368,36 +368,22 @@ int pcg(const psp_op *A, const psp_op *K, int n, double *x, const double *b, dou
     *iter = 0;
     return PSP_OK;
   }
-  double rho = 1.0, rho1, alpha, beta, pq;
-  int stag = 0, it;
-  for (it = 1; it <= maxit; ++it) {
+  PcgCol c = pcg_begin(n2b, tolb, normr, maxit);  // the recurrence and its exits: psp_recur.h
+  if (maxit < 1) pcg_exit(c, -1, 1);              // :91: no iteration runs
+  while (c.it <= maxit) {
     if (K) PSP_TRY(apply(K, r, z));
     else memcpy(z, r, sizeof(double) * (size_t)n);
-    rho1 = rho;
-    rho = ddot(n, r, z);
-    if (rho == 0.0) {  // :101-104
-      *info = -2;
-      break;
-    }
-    if (it == 1) {
+    if (pcg_head(c, ddot(n, r, z))) break;
+    if (c.it == 1) {
       memcpy(p, z, sizeof(double) * (size_t)n);
     } else {
-      beta = rho / rho1;
-      if (beta == 0.0) {  // :109-112
-        *info = -6;
-        break;
-      }
-      for (int i = 0; i < n; ++i) p[i] = z[i] + beta * p[i];
+      for (int i = 0; i < n; ++i) p[i] = z[i] + c.beta * p[i];
     }
     PSP_TRY(apply(A, p, q));
-    pq = ddot(n, p, q);
-    if (pq == 0.0) {  // :118-120
-      *info = -6;
-      break;
-    }
-    alpha = rho / pq;
-    if (alpha == 0.0) stag = 1;
-    if (stag == 0) {  // :127-139
+    if (pcg_alpha(c, ddot(n, p, q))) break;
+    const double alpha = c.alpha;
+    bool scan_stagnated = false;
+    if (c.stag == 0) {  // :127-139
       double dmax = 0.0;
       for (int i = 0; i < n; ++i)
         if (x[i] != 0.0) {
@@ -406,23 +392,18 @@ int pcg(const psp_op *A, const psp_op *K, int n, double *x, const double *b, dou
         } else if (p[i] != 0.0) {
           dmax = 1.0;
         }
-      stag = (1.0 + dmax == 1.0);
+      scan_stagnated = (1.0 + dmax == 1.0);
     }
     daxpy(n, alpha, p, x);
     daxpy(n, -alpha, q, r);
-    normr = dnrm2(n, r);  // the recurred residual (EXPENSIVE_CRIT undefined, :146-153)
-    if (hist) hist[it] = normr;
-    if (normr <= tolb) {
-      *info = 0;
-      break;
-    }
-    if (stag == 1) {
-      *info = -5;
-      break;
-    }
+    const int it = c.it;
+    const bool over = pcg_tail(c, dnrm2(n, r), scan_stagnated);  // the recurred residual (EXPENSIVE_CRIT undefined, :146-153)
+    if (hist) hist[it] = c.normr;
+    if (over) break;
   }
-  *iter = it;  // maxit + 1 when the loop ran out (:165)
-  *relres = normr / n2b;
+  *info = c.info;
+  *iter = c.iter;  // maxit + 1 when the loop ran out (:165)
+  *relres = c.relres;
   return PSP_OK;
 }
 
@@ -444,53 +425,36 @@ int minres(const psp_op *A, const psp_op *K, int n, double *x, const double *b, 
     return PSP_OK;
   }
   beta = std::sqrt(beta);
-  double beta_old = 1.0, c = 1.0, c_old = 1.0, s = 0.0, s_old = 0.0, eta = beta, norm_rmr = norm_r0;
-  if (hist) hist[0] = norm_rmr;
-  for (;;) {
-    if (*iter >= it_max || norm_rmr < errtol * norm_r0) break;  // :114
+  MinresRot R = minres_begin(beta, norm_r0);  // the recurrence and its exits: psp_recur.h
+  if (hist) hist[0] = R.norm_rmr;
+  int end = minres_loop_test(*iter, it_max, R.norm_rmr, errtol, norm_r0);
+  while (end == 1) {
     *iter += 1;
-    for (int i = 0; i < n; ++i) v[i] = y[i] / beta;
+    for (int i = 0; i < n; ++i) v[i] = y[i] / R.beta;
     memcpy(y, v_hat, sizeof(double) * (size_t)n);
     PSP_TRY(apply(A, v, av));
-    const double alpha = ddot(n, v, av);
-    const double c1 = alpha / beta, c2 = beta / beta_old;
+    minres_alpha(R, ddot(n, v, av));
+    const double c1 = R.c1, c2 = R.c2;
     for (int i = 0; i < n; ++i) v_hat[i] = av[i] - c1 * v_hat[i] - c2 * v_hat_old[i];
     memcpy(v_hat_old, y, sizeof(double) * (size_t)n);
     if (K) PSP_TRY(apply(K, v_hat, y));
     else memcpy(y, v_hat, sizeof(double) * (size_t)n);
-    beta_old = beta;
-    beta = ddot(n, v_hat, y);
-    if (beta < 0.0) {  // :144-146
-      *info = -3;
+    end = minres_rotate(R, ddot(n, v_hat, y), *iter, it_max, errtol, norm_r0);
+    if (end == -3 || end == -6) {  // :144-146, :160-162
+      *info = end;
       return PSP_OK;
     }
-    beta = std::sqrt(beta);
-    const double c_oold = c_old, s_oold = s_old;
-    c_old = c;
-    s_old = s;
-    const double r1_hat = c_old * alpha - c_oold * s_old * beta_old;
-    const double r1 = std::sqrt(r1_hat * r1_hat + beta * beta);
-    const double r2 = s_old * alpha + c_oold * c_old * beta_old;
-    const double r3 = s_oold * beta_old;
-    if (r1 == 0.0) {  // :160-162
-      *info = -6;
-      return PSP_OK;
-    }
-    c = r1_hat / r1;
-    s = beta / r1;
+    const double r1 = R.r1, r2 = R.r2, r3 = R.r3, ce = R.c_eta;
     for (int i = 0; i < n; ++i) {
       const double tmp = w[i];
       w[i] = (v[i] - r3 * w_old[i] - r2 * tmp) / r1;
       w_old[i] = tmp;
     }
-    const double ce = c * eta;
     for (int i = 0; i < n; ++i) x[i] += ce * w[i];
-    eta = -s * eta;
-    norm_rmr *= std::fabs(s);  // the estimate in the preconditioned norm (:192)
-    if (hist) hist[*iter] = norm_rmr;
+    if (hist) hist[*iter] = R.norm_rmr;  // the estimate in the preconditioned norm (:192)
   }
-  *relres = norm_rmr / norm_r0;
-  *info = norm_rmr < errtol * norm_r0 ? 0 : -1;
+  *relres = R.norm_rmr / norm_r0;
+  *info = end;
   return PSP_OK;
 }
 

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "pysparse_hip.h"
+#include "psp_recur.h"
 
 namespace psp {
 
@@ -506,12 +507,8 @@ namespace psp {
 // Device-resident scalar state of the asynchronous PCG loop (psp_solvers.hip): the kernels
 // of one iteration read alpha / beta / status from here instead of from host arguments, so
 // the host can enqueue many iterations without synchronising.
-struct PcgDev {
-  double rho, rho1, alpha, beta, normr, tolb, n2b, relres;
+struct PcgDev : PcgCol {  // psp_recur.h: the recurrence itself
   int status;  // 0 running, 1 finished (every later kernel is a no-op)
-  int info, iter, stag;
-  int it;      // iteration the enqueued kernels are working on (1-based), advanced on the device
-  int maxit;
   // lazy x-update loop (pcg_async_loop_lazy): x += alpha_x * p of the last finished iteration is
   // applied by the NEXT iteration's p-update pass (or by the final pass after the loop)
   int xpend;       // an x update (and its stagnation scan) is pending
@@ -522,28 +519,20 @@ struct PcgDev {
   double alpha_x;
 };
 // Device-resident scalar state of the asynchronous MINRES loop (psp_solvers.hip; minres.c:96-193): the
-// Lanczos / Givens recurrences are evaluated by the thread that finishes each reduction; the vector
-// kernels read their coefficients from here.
-struct MinresDev {
-  double beta, beta_old, alpha, c, c_old, s, s_old, eta, norm_rmr, norm_r0, errtol, relres;
-  double c1, c2;             // Lanczos coefficients of the running iteration: alpha/beta, beta/beta_old
-  double r1, r2, r3, c_eta;  // its w / x update (minres.c:172-180)
+// Lanczos / Givens recurrences (MinresRot, psp_recur.h) are evaluated by the thread that finishes each reduction; the
+// vector kernels read their coefficients from here.
+struct MinresDev : MinresRot {
+  double norm_r0, errtol, relres;
   int status;  // 1: ended by -3 / -6 (minres.c:144-146, :160-162) or after the last w/x update: all kernels no-ops
   int stop;    // the loop test at the head of the NEXT iteration failed (minres.c:114): only the w/x update
                // of the running iteration is still to be done
   int skip;    // status | stop -- what the SpMV / scale / Lanczos kernels look at
   int info, iter, it_max;
 };
-// Device-resident scalars of the cgs / bicgstab / qmrs loops (round 5; psp_solvers.hip): the recurrences of
-// cgs.c / bicgstab.c / qmrs.c are evaluated by the thread that finishes each reduction, the fused vector kernels read their
-// coefficients from here, the host enqueues a batch of iterations and reads the state once -- no host round trip per
-// reduction (they cost 12 us each at 1024^2: profiles/r4_extra_solvers_1024sq.txt).
-struct KryDev {
-  double r[32];
-  int status;  // 1: the loop is over -- every later kernel is a no-op
-  int code;    // which way it ended (per solver)
-  int iter, maxit;
-};
+// Device-resident scalars of the cgs / bicgstab / qmrs loops (round 5; psp_solvers.hip): KryDev of psp_recur.h.  The
+// recurrences of cgs.c / bicgstab.c / qmrs.c are evaluated by the thread that finishes each reduction, the fused vector
+// kernels read their coefficients from there, the host enqueues a batch of iterations and reads the state once -- no host
+// round trip per reduction (they cost 12 us each at 1024^2: profiles/r4_extra_solvers_1024sq.txt).
 // scalar operands of a fused vector kernel: S == nullptr: the by-value arguments; else S->r[i0 / i1 / i2] (and the
 // kernel does nothing once S->status is set)
 struct KryArg {

@@ -339,6 +339,7 @@ __global__ __launch_bounds__(BLK) void pcg_mid_kernel(MidArgs a) {
   if (a.stamps && wg == (int)(a.stamps[0]) && t == 0 && it <= 16) a.stamps[8 + (it - 1) * 8 + (K)] = wall_clock64()
   for (it = 1; it <= a.maxit; ++it) {
     PSP_MID_STAMP(0);
+    // (pcg_head's expressions, psp_recur.h; inline copy -- as pcg_alpha's and pcg_tail's below)
     if (rho == 0.0) {  // pcg.c:101-104
       flag = -2;
       break;
@@ -543,7 +544,11 @@ __global__ __launch_bounds__(BLK) void pcg_mid_kernel(MidArgs a) {
 // entries it gathers by beta itself (the owner's own correctly rounded division), so v = y / beta is never exchanged.  The
 // window holds nothing between iterations here, so the partial sums are staged in its own part and the neighbours' y is
 // copied straight into its halo zones.  Expressions: csr_spmv_w4's scaled product, lanczos_kernel, minres_wx_kernel
-// (psp_vec.hip), minres_scalar_alpha / minres_scalar_beta (psp_solvers.hip) -- the launch-per-phase loop's bits.
+// (psp_vec.hip), minres_alpha / minres_rotate (psp_recur.h) -- the launch-per-phase loop's bits.
+// The scalar steps of the four kernels of this file are INLINE COPIES of psp_recur.h's pcg_head / pcg_alpha / pcg_tail and
+// minres_alpha / minres_rotate: calling the shared functions on a local struct changes the registers and the scratch of
+// these kernels (profiles/recur_resources.txt), and they are tuned to their budget.  A change to an exit rule there is
+// a change here.
 struct MidMinresArgs {
   int n, nwg, H;
   int offs[12];
@@ -726,7 +731,7 @@ __global__ __launch_bounds__(BLK) void minres_mid_kernel(MidMinresArgs a) {
     if (!mid_barrier(a.ctl, nwg, gen)) return;
     mid_halo_dma<BLK>(a.yv, base, B, H, n, win, H + B);  // the next iteration's halo rides with the partial sums
     mid_reduce<1, BLK>(s1, a.part + kMidMaxSpans, a.nspans, -1, a.nspans, stage, grp);
-    // ---- minres_scalar_beta: :143-164, :180, :192
+    // ---- minres_rotate's expressions (psp_recur.h; inline copy): :143-164, :180, :192
     const double beta_start = beta;  // beta at the start of this iteration
     beta_old = beta;
     double b2 = s1[0];
@@ -966,6 +971,7 @@ __global__ __launch_bounds__(kBrickBlock) void pcg_brick_kernel(BrickArgs a) {
   double rho = a.rho0, rho1 = 1.0, normr = a.normr0, alpha = 0.0, beta = 0.0;
   int flag = -1, it;
   for (it = 1; it <= a.maxit; ++it) {
+    // (pcg_head's expressions, psp_recur.h; inline copy -- as pcg_alpha's and pcg_tail's below)
     if (rho == 0.0) {  // pcg.c:101-104
       flag = -2;
       break;
@@ -1329,7 +1335,7 @@ __global__ __launch_bounds__(kBrickBlock) void minres_brick_kernel(BrickMinresAr
 #pragma unroll
     for (int j = 0; j < kBrickHPT; ++j) yh[j] = hidx[j] >= 0 ? mcoh_load(a.yv + hrow[j]) : 0.0;  // the next iteration's halo
     brick_reduce<1>(s1, a.part + kMidMaxWg, nwg, red + NW);
-    // ---- minres_scalar_beta: :143-164, :180, :192
+    // ---- minres_rotate's expressions (psp_recur.h; inline copy): :143-164, :180, :192
     const double beta_start = beta;
     beta_old = beta;
     const double b2 = s1[0];

@@ -393,56 +393,26 @@ struct LoopState {
 // reduction.  The host enqueues kBatch iterations, then reads the 96-byte state once: two host
 // round trips per ITERATION become one per BATCH (matters when an iteration is shorter than ~1 ms).
 
+// an exit of the recurrence (psp_recur.h) ends the loop: every later launch is a no-op
 __device__ __forceinline__ void pcg_finish(PcgDev *st, int code, int iter) {
   st->status = 1;
-  st->info = code;
-  st->iter = iter;
-  st->relres = st->normr / st->n2b;  // pcg.c:166
+  pcg_exit(*st, code, iter);
 }
 
-// after q = A p and the p.q reduction: pcg.c:117-125
+// after q = A p and the p.q reduction
 __device__ __forceinline__ void pcg_scalar_pq(PcgDev *st, const double *__restrict__ scal) {
   if (st->status) return;
-  const double pq = scal[0];
-  if (pq == 0.0) {
-    pcg_finish(st, -6, st->it);
-    return;
-  }
-  const double alpha = st->rho / pq;
-  st->alpha = alpha;
-  if (alpha == 0.0) st->stag = 1;
+  if (pcg_alpha(*st, scal[0])) st->status = 1;
 }
 
-// after the x/r update and its reductions: pcg.c:127-162 for iteration `it`, then the head
-// of iteration it+1 (pcg.c:99-112)
+// after the x/r update and its reductions {r.r, r.z, rows the scan saw move}: the tail of iteration `it`, then the head
+// of iteration it+1 (z = dinv .* r or r: r.z is its rho)
 __device__ __forceinline__ void pcg_scalar_xr(PcgDev *st, const double *__restrict__ scal, double *__restrict__ hist) {
   if (st->status) return;
   const int it = st->it;
-  if (st->stag == 0) st->stag = (scal[2] == 0.0) ? 1 : 0;
-  const double normr = sqrt(scal[0]);
-  st->normr = normr;
-  if (hist) hist[it] = normr;
-  if (normr <= st->tolb) {
-    pcg_finish(st, 0, it);
-  } else if (st->stag == 1) {
-    pcg_finish(st, -5, it);
-  } else if (it == st->maxit) {
-    pcg_finish(st, -1, it + 1);  // pcg.c:165: the loop ran out
-  } else {
-    const double rho1 = st->rho, rho = scal[1];
-    st->rho1 = rho1;
-    st->rho = rho;
-    st->it = it + 1;
-    if (rho == 0.0) {
-      pcg_finish(st, -2, it + 1);
-    } else {
-      const double beta = rho / rho1;
-      if (beta == 0.0)
-        pcg_finish(st, -6, it + 1);
-      else
-        st->beta = beta;
-    }
-  }
+  const bool over = pcg_tail(*st, sqrt(scal[0]), scal[2] == 0.0) || pcg_head(*st, scal[1]);
+  if (hist) hist[it] = st->normr;
+  if (over) st->status = 1;
 }
 
 struct PcgPq : StepOf<PcgDev> {
@@ -673,7 +643,7 @@ static int pcg_async_loop_lazy(psp_csr *Acsr, const double *dinv, int n, double 
 }
 
 // Acsr_forced != nullptr: the caller has moved the system into the numbering of a renumbered copy of A
-// (pcg_device below): multiply with that handle, take z = dinv_forced .* r (or z = r), never touch A / K
+// (PermutedSystem below): multiply with that handle, take z = dinv_forced .* r (or z = r), never touch A / K
 // ||v||_2 where the sum of squares `sq` has left [1e-280, 1e280] (or is not a number): sqrt(sum v_i^2) cannot be
 // trusted there, the reference's dnrm2 (scaled form: pcg.c:57,75; minres.c:71) still can.  The norm is then
 // formed at a power-of-two scale (exact): 2^e * sqrt(sum (v_i * 2^-e)^2), e = exponent of max |v_i|.  Only the
@@ -859,12 +829,11 @@ static int pcg_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_force
   }
   note_solve("pcg_host_scalars", -1, -1, dstream);
 
-  double rho = 1.0, rho1, beta = 0.0, alpha, pq;
-  int stag = 0;
-  int it;
-  for (it = 1; it <= maxit; ++it) {  // pcg.c:91
-    const double *zsrc = r;           // vector the p-update reads z from
-    const double *zdinv = dinv;       // fused: z = dinv.*r formed on the fly
+  PcgCol c = pcg_begin(n2b, tolb, normr, maxit);  // the recurrence and its exits: psp_recur.h
+  if (maxit < 1) pcg_exit(c, -1, 1);              // pcg.c:91: no iteration runs
+  while (c.it <= maxit) {
+    const double *zsrc = r;      // vector the p-update reads z from
+    const double *zdinv = dinv;  // fused: z = dinv.*r formed on the fly
     if (!fused) {
       zdinv = nullptr;
       if (K) {  // pcg.c:93-94
@@ -876,20 +845,8 @@ static int pcg_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_force
       PSP_TRY(reduce_fetch(w, np, 1, s));
       rho_next = s[0];
     }
-    rho1 = rho;
-    rho = rho_next;
-    if (rho == 0.0) {  // pcg.c:101-104
-      *info = -2;
-      break;
-    }
-    if (it > 1) {
-      beta = rho / rho1;
-      if (beta == 0.0) {  // pcg.c:109-112
-        *info = -6;
-        break;
-      }
-    }
-    PSP_TRY(k_pupdate(n, zsrc, zdinv, it == 1 ? 0.0 : beta, it == 1, p));  // pcg.c:106, :113-114
+    if (pcg_head(c, rho_next)) break;
+    PSP_TRY(k_pupdate(n, zsrc, zdinv, c.it == 1 ? 0.0 : c.beta, c.it == 1, p));  // pcg.c:106, :113-114
 
     // q = A p, pq = p.q (pcg.c:116-117)
     if (Acsr) {
@@ -899,33 +856,20 @@ static int pcg_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_force
       PSP_TRY(k_dot(n, p, q, w->partials, &np));
     }
     PSP_TRY(reduce_fetch(w, np, 1, s));
-    pq = s[0];
-    if (pq == 0.0) {  // pcg.c:118-120
-      *info = -6;
-      break;
-    }
-    alpha = rho / pq;
-    if (alpha == 0.0) stag = 1;  // pcg.c:124-125
+    if (pcg_alpha(c, s[0])) break;
 
     // stagnation scan, x += alpha p, r -= alpha q, normr (pcg.c:127-152)
-    PSP_TRY(k_xr_update(n, alpha, p, q, fused ? dinv : nullptr, x, r, w->partials, &np));
+    PSP_TRY(k_xr_update(n, c.alpha, p, q, fused ? dinv : nullptr, x, r, w->partials, &np));
     PSP_TRY(reduce_fetch(w, np, 3, s));
-    if (stag == 0) stag = (s[2] == 0.0);
-    normr = sqrt(s[0]);
     rho_next = s[1];
-    if (hist) hist[it] = normr;
-
-    if (normr <= tolb) {  // pcg.c:154-157
-      *info = 0;
-      break;
-    }
-    if (stag == 1) {  // pcg.c:159-162
-      *info = -5;
-      break;
-    }
+    const int it = c.it;
+    const bool over = pcg_tail(c, sqrt(s[0]), s[2] == 0.0);
+    if (hist) hist[it] = c.normr;
+    if (over) break;
   }
-  *iter = it;  // pcg.c:165: maxit + 1 when the loop ran out
-  *relres = normr / n2b;
+  *info = c.info;
+  *iter = c.iter;
+  *relres = c.relres;
   PSP_HIP(hipStreamSynchronize(stream()));
   return PSP_OK;
 }
@@ -975,8 +919,8 @@ struct PermutedSystem {
   int leave(int n, double *x) { return reorder_gather(n, inv, xp, x, nullptr); }  // x[j] = xp[inv[j]]
 };
 
-static int pcg_permuted(const psp_op *A, const psp_op *K, int n, double *x, const double *b, double tol, int maxit,
-                        int *info, int *iter, double *relres, double *hist) {
+static int pcg_device(const psp_op *A, const psp_op *K, int n, double *x, const double *b, double tol, int maxit,
+                      int *info, int *iter, double *relres, double *hist) {
   DevVecs mem;
   PermutedSystem ps;
   int active = 0;
@@ -988,11 +932,6 @@ static int pcg_permuted(const psp_op *A, const psp_op *K, int n, double *x, cons
   PSP_TRY(ps.leave(n, x));
   PSP_HIP(hipStreamSynchronize(stream()));
   return PSP_OK;
-}
-
-static int pcg_device(const psp_op *A, const psp_op *K, int n, double *x, const double *b, double tol, int maxit,
-                      int *info, int *iter, double *relres, double *hist) {
-  return pcg_permuted(A, K, n, x, b, tol, maxit, info, iter, relres, hist);
 }
 
 // ====================================================================== MINRES
@@ -1017,65 +956,28 @@ __device__ __forceinline__ void minres_scalar_alpha(MinresDev *st, const double 
     st->status = 1;
     return;
   }
-  const double alpha = scal[0];  // minres.c:129
-  st->alpha = alpha;
-  st->c1 = alpha / st->beta;  // minres.c:131
-  st->c2 = st->beta / st->beta_old;
+  minres_alpha(*st, scal[0]);
 }
 
+// minres_rotate (psp_recur.h) on v_hat . y, and what its answer means to the kernels behind it
 __device__ __forceinline__ void minres_scalar_beta(MinresDev *st, const double *__restrict__ scal,
                                                    double *__restrict__ hist) {
   if (st->status) return;
-  const double alpha = st->alpha;
-  const double beta_old = st->beta;
-  st->beta_old = beta_old;
-  double beta = scal[0];  // minres.c:143
-  if (beta < 0.0) {       // minres.c:144-146
+  const int end = minres_rotate(*st, scal[0], st->iter, st->it_max, st->errtol, st->norm_r0);
+  if (end == -3 || end == -6) {  // before the w / x update
     st->status = 1;
     st->skip = 1;
-    st->info = -3;
+    st->info = end;
     return;
   }
-  beta = sqrt(beta);
-  st->beta = beta;
-  // QR factorisation + Givens rotation (minres.c:151-164)
-  const double c_oold = st->c_old;
-  const double c_old = st->c;
-  const double s_oold = st->s_old;
-  const double s_old = st->s;
-  st->c_old = c_old;
-  st->s_old = s_old;
-  const double r1_hat = c_old * alpha - c_oold * s_old * beta_old;
-  const double r1 = sqrt(r1_hat * r1_hat + beta * beta);
-  const double r2 = s_old * alpha + c_oold * c_old * beta_old;
-  const double r3 = s_oold * beta_old;
-  if (r1 == 0.0) {  // minres.c:160-162
-    st->status = 1;
-    st->skip = 1;
-    st->info = -6;
-    return;
-  }
-  const double c = r1_hat / r1;
-  const double s_ = beta / r1;
-  st->c = c;
-  st->s = s_;
-  st->r1 = r1;
-  st->r2 = r2;
-  st->r3 = r3;
-  st->c_eta = c * st->eta;  // minres.c:180
-  st->eta = -s_ * st->eta;
-  const double norm_rmr = st->norm_rmr * fabs(s_);  // minres.c:192
-  st->norm_rmr = norm_rmr;
-  if (hist) hist[st->iter] = norm_rmr;
-  // head of the next iteration (minres.c:114, strict <)
-  const bool conv = norm_rmr < st->errtol * st->norm_r0;
-  if (st->iter >= st->it_max || conv) {
+  if (hist) hist[st->iter] = st->norm_rmr;
+  if (end == 1) {
+    st->iter += 1;
+  } else {  // the loop test failed: the w / x update still runs
     st->stop = 1;
     st->skip = 1;
-    st->relres = norm_rmr / st->norm_r0;  // minres.c:195
-    st->info = conv ? 0 : -1;
-  } else {
-    st->iter += 1;
+    st->relres = st->norm_rmr / st->norm_r0;  // minres.c:195
+    st->info = end;
   }
 }
 
@@ -1108,14 +1010,7 @@ static int minres_async_loop(psp_csr *Acsr, const double *dinv, bool hasK, int n
   LoopState<MinresDev> S;
   PSP_TRY(S.init(hist ? (size_t)it_max + 1 : 0));
   MinresDev *st = S.dev, *hst = S.host;
-  hst->beta = beta0;
-  hst->beta_old = 1.0;
-  hst->c = 1.0;
-  hst->c_old = 1.0;
-  hst->s = 0.0;
-  hst->s_old = 0.0;
-  hst->eta = beta0;
-  hst->norm_rmr = norm_r0;
+  static_cast<MinresRot &>(*hst) = minres_begin(beta0, norm_r0);
   hst->norm_r0 = norm_r0;
   hst->errtol = errtol;
   hst->iter = 1;
@@ -1237,18 +1132,16 @@ static int minres_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_fo
     return PSP_OK;
   }
   beta = sqrt(beta);
-  double beta_old = 1.0;
-  double c = 1.0, c_old = 1.0, s_ = 0.0, s_old = 0.0, c_oold, s_oold;
   PSP_HIP(hipMemsetAsync(wv, 0, bytes, stream()));  // minres.c:86-90
   PSP_HIP(hipMemsetAsync(w_old, 0, bytes, stream()));
-  double eta = beta;
-  double norm_rmr = norm_r0;
-  if (hist) hist[0] = norm_rmr;
+  if (hist) hist[0] = norm_r0;
+  // minres.c:114 before iteration 1: only a solve that iterates is handed to a device-resident loop
+  const bool iterates = minres_loop_test(0, it_max, norm_r0, errtol, norm_r0) == 1;
 
   const bool sk = single_kernel_loops_enabled();  // psp_set_single_kernel_loops(0): launch-per-phase loops only
   double dcst;
   const int dstream = (hasK && dinv && !dinv_constant(dinv, n, &dcst)) ? 1 : 0;
-  if (sk && Acsr && kfused && it_max >= 1 && !(norm_rmr < errtol * norm_r0))
+  if (sk && Acsr && kfused && iterates)
     for (const MinresSkLoop &L : minres_sk_loops()) {  // the whole loop as one kernel: mid, brick, coop
       if ((L.needs_dinv && hasK && !dinv) || !L.applicable(Acsr, n)) continue;
       const int rc = L.run(Acsr, hasK ? dinv : nullptr, n, x, v_hat, y, wv, v, av, norm_r0, beta, errtol, it_max, info, iter,
@@ -1259,7 +1152,7 @@ static int minres_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_fo
       }
       note_fallback();  // refused / gave up: x, v_hat, y are untouched, the loops below take over
     }
-  if (Acsr && kfused && minres_async_enabled() && it_max >= 1 && !(norm_rmr < errtol * norm_r0)) {
+  if (Acsr && kfused && minres_async_enabled() && iterates) {
     // scaled product (reads y, writes Av) + lanczos (Av, v_hat, v_hat_old read; v_hat, y written: 40, + 8 when K streams
     // dinv) + w / x update (y, w, w_old, x read; w, x written: 48): 88 bytes per row beside the product
     note_solve("minres_async", 5 + (n > (1 << 21) ? 2 : 0), 88 + 8 * dstream, dstream);
@@ -1269,18 +1162,19 @@ static int minres_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_fo
   }
   note_solve("minres_host_scalars", -1, -1, dstream);
 
-  while (true) {
-    if (*iter >= it_max || norm_rmr < errtol * norm_r0) break;  // minres.c:114 (strict <)
+  MinresRot R = minres_begin(beta, norm_r0);  // the recurrence and its exits: psp_recur.h
+  int end = minres_loop_test(*iter, it_max, R.norm_rmr, errtol, norm_r0);
+  while (end == 1) {
     *iter += 1;
 
     // v = y / beta (minres.c:123-124); y = v_hat is implied: the update below keeps the
     // old v_hat in v_hat_old directly (minres.c:125,135)
     const double *vsrc = hasK ? y : v_hat;  // unnormalised Lanczos vector of this iteration
-    const double vdiv = beta;
+    const double vdiv = R.beta;
     int scaled = 0;
     if (Acsr && kfused && (!hasK || y2))
       PSP_TRY(csr_spmv_scaled_launch(Acsr, vsrc, vdiv, av, w->partials, &np, &scaled));
-    if (!scaled) PSP_TRY(k_scale_div(n, vsrc, beta, v));
+    if (!scaled) PSP_TRY(k_scale_div(n, vsrc, vdiv, v));
     // Av = A v, alpha = v.Av (minres.c:127-129)
     if (scaled) {
     } else if (Acsr) {
@@ -1290,66 +1184,44 @@ static int minres_device_core(const psp_op *A, const psp_op *K, psp_csr *Acsr_fo
       PSP_TRY(k_dot(n, v, av, w->partials, &np));
     }
     PSP_TRY(reduce_fetch(w, np, 1, s));
-    const double alpha = s[0];
-    const double dconst1 = alpha / beta, dconst2 = beta / beta_old;  // minres.c:131
+    minres_alpha(R, s[0]);
     // v_hat = Av - c1 v_hat - c2 v_hat_old; v_hat_old = old v_hat; y = K v_hat; beta^2
     // (the kernels write the new v_hat over v_hat_old; swapping the names is "v_hat_old = old v_hat")
     if (kfused) {
       // scaled mode: the new y goes to the other buffer (vsrc = old y is still needed by the w update)
       double *ynew = (scaled && hasK) ? y2 : y;
-      PSP_TRY(k_lanczos(n, av, dconst1, dconst2, v_hat, v_hat_old, dinv, ynew, w->partials, &np));
+      PSP_TRY(k_lanczos(n, av, R.c1, R.c2, v_hat, v_hat_old, dinv, ynew, w->partials, &np));
       std::swap(v_hat, v_hat_old);
       if (scaled && hasK) std::swap(y, y2);
     } else {
-      PSP_TRY(k_lanczos_plain(n, av, dconst1, dconst2, v_hat, v_hat_old));
+      PSP_TRY(k_lanczos_plain(n, av, R.c1, R.c2, v_hat, v_hat_old));
       std::swap(v_hat, v_hat_old);
       PSP_TRY(op_apply(K, v_hat, y));  // minres.c:137-140
       PSP_TRY(k_dot(n, v_hat, y, w->partials, &np));
     }
     PSP_TRY(reduce_fetch(w, np, 1, s));
-    beta_old = beta;
-    beta = s[0];  // minres.c:143
-    if (beta < 0.0) {
-      *info = -3;
+    end = minres_rotate(R, s[0], *iter, it_max, errtol, norm_r0);
+    if (end == -3 || end == -6) {  // minres.c:144-146, :160-162: relres stays untouched
+      *info = end;
       PSP_HIP(hipStreamSynchronize(stream()));
       return PSP_OK;
     }
-    beta = sqrt(beta);
-
-    // QR factorisation + Givens rotation (minres.c:151-164)
-    c_oold = c_old;
-    c_old = c;
-    s_oold = s_old;
-    s_old = s_;
-    const double r1_hat = c_old * alpha - c_oold * s_old * beta_old;
-    const double r1 = sqrt(r1_hat * r1_hat + beta * beta);
-    const double r2 = s_old * alpha + c_oold * c_old * beta_old;
-    const double r3 = s_oold * beta_old;
-    if (r1 == 0.0) {
-      *info = -6;
-      PSP_HIP(hipStreamSynchronize(stream()));
-      return PSP_OK;
-    }
-    c = r1_hat / r1;
-    s_ = beta / r1;
 
     // w, x update (minres.c:172-180)
     // new w lands in w_old's buffer; scaled: v = vsrc / vdiv on the fly (vsrc is v_hat_old resp. y2 now)
-    PSP_TRY(k_minres_wx(n, scaled ? vsrc : v, r1, r2, r3, c * eta, wv, w_old, x, scaled != 0, vdiv));
+    PSP_TRY(k_minres_wx(n, scaled ? vsrc : v, R.r1, R.r2, R.r3, R.c_eta, wv, w_old, x, scaled != 0, vdiv));
     std::swap(wv, w_old);
-    eta = -s_ * eta;
-    norm_rmr *= fabs(s_);  // minres.c:192
-    if (hist) hist[*iter] = norm_rmr;
+    if (hist) hist[*iter] = R.norm_rmr;
   }
 
-  *relres = norm_rmr / norm_r0;  // minres.c:195
-  *info = (norm_rmr < errtol * norm_r0) ? 0 : -1;
+  *relres = R.norm_rmr / norm_r0;  // minres.c:195
+  *info = end;
   PSP_HIP(hipStreamSynchronize(stream()));
   return PSP_OK;
 }
 
-static int minres_permuted(const psp_op *A, const psp_op *K, int n, double *x, const double *b, double errtol,
-                           int it_max, int *info, int *iter, double *relres, double *hist) {
+static int minres_device(const psp_op *A, const psp_op *K, int n, double *x, const double *b, double errtol,
+                         int it_max, int *info, int *iter, double *relres, double *hist) {
   DevVecs mem;
   PermutedSystem ps;
   int active = 0;
@@ -1362,11 +1234,6 @@ static int minres_permuted(const psp_op *A, const psp_op *K, int n, double *x, c
   PSP_TRY(ps.leave(n, x));
   PSP_HIP(hipStreamSynchronize(stream()));
   return PSP_OK;
-}
-
-static int minres_device(const psp_op *A, const psp_op *K, int n, double *x, const double *b, double errtol,
-                         int it_max, int *info, int *iter, double *relres, double *hist) {
-  return minres_permuted(A, K, n, x, b, errtol, it_max, info, iter, relres, hist);
 }
 
 // largest |v_i|: per-workgroup maxima on the device, the few thousand of them on the host (a path taken once
@@ -1476,132 +1343,6 @@ namespace {
 
 constexpr int kKryBatch = 8;
 
-enum KryOp {
-  kCgsD, kCgsR,
-  kBicgD1, kBicgTt, kBicgXr,
-  kQmrsDelta0, kQmrsEps, kQmrsRho, kQmrsDelta,
-};
-// cgs registers
-enum { CG_RHO = 0, CG_ALPHA, CG_BETA, CG_D, CG_RES, CG_RHONEW, CG_THR };
-// bicgstab registers
-enum { BI_RHO1 = 0, BI_RHO2, BI_ALPHA, BI_OMEGA, BI_BETA, BI_D1, BI_D2, BI_RR, BI_RHONEXT, BI_RES0, BI_TOL, BI_RES };
-// qmrs registers
-enum { QM_RHO0 = 0, QM_RHO1, QM_TAU, QM_C0, QM_C1, QM_EPS0, QM_XI1, QM_THETA0, QM_THETA, QM_ETA0, QM_DELTA, QM_CC, QM_BETA,
-       QM_CC2, QM_RHO1INV, QM_ERR, QM_RESINIT, QM_TOL, QM_OUT };
-
-__device__ __forceinline__ void kry_end(KryDev *S, int code) {
-  S->status = 1;
-  S->code = code;
-}
-
-// bicgstab.c: head of an iteration (the do-loop's first statements), after the previous one decided to go on
-__device__ __forceinline__ void bicg_head(KryDev *S) {
-  S->iter += 1;
-  if (S->r[BI_RHO1] == 0.0) {
-    kry_end(S, 3);  // "return" with info as initialised (-6)
-    return;
-  }
-  S->r[BI_BETA] = (S->r[BI_RHO1] / S->r[BI_RHO2]) * (S->r[BI_ALPHA] / S->r[BI_OMEGA]);
-}
-
-// qmrs.c: head of an iteration (while test, ++iter, eps0 / delta tests, cc)
-__device__ __forceinline__ void qmrs_head(KryDev *S) {
-  if (!(S->r[QM_ERR] > S->r[QM_TOL] && S->iter < S->maxit)) {
-    kry_end(S, 1);  // the loop test failed: normal end
-    return;
-  }
-  S->iter += 1;
-  if (S->r[QM_EPS0] == 0.0) {
-    kry_end(S, 6);
-    return;
-  }
-  if (S->r[QM_DELTA] == 0.0) {
-    kry_end(S, 2);
-    return;
-  }
-  S->r[QM_CC] = S->r[QM_XI1] * (S->r[QM_DELTA] / S->r[QM_EPS0]);
-}
-
-// the recurrences that follow the reduction(s) of OP, on the registers the reduction wrote
-template <int OP>
-__device__ __forceinline__ void kry_step(KryDev *S) {
-  double *r = S->r;
-  if constexpr (OP == kCgsD) {  // cgs.c: alpha = rho / (v . r0)
-    r[CG_ALPHA] = r[CG_RHO] / r[CG_D];
-  }
-  if constexpr (OP == kCgsR) {  // cgs.c: convergence test on r.r, beta, the for-loop's increment and test
-    if (r[CG_RES] < r[CG_THR]) {
-      kry_end(S, 1);
-    } else {
-      r[CG_BETA] = r[CG_RHONEW] / r[CG_RHO];
-      r[CG_RHO] = r[CG_RHONEW];
-      S->iter += 1;
-      if (!(S->iter < S->maxit)) kry_end(S, 2);
-    }
-  }
-  if constexpr (OP == kBicgD1) r[BI_ALPHA] = r[BI_RHO1] / r[BI_D1];  // alpha = rho / (rhat . v)
-  if constexpr (OP == kBicgTt) r[BI_OMEGA] = r[BI_D1] / r[BI_D2];    // omega = (t . s) / (t . t)
-  if constexpr (OP == kBicgXr) {  // res, the omega == 0 return, the loop test, then the next iteration's head
-    const double res = sqrt(r[BI_RR]);
-    r[BI_RES] = res;
-    if (r[BI_OMEGA] == 0.0) {
-      kry_end(S, 4);
-    } else {
-      r[BI_RHO2] = r[BI_RHO1];
-      r[BI_RHO1] = r[BI_RHONEXT];
-      if (!((res / r[BI_RES0] > r[BI_TOL]) && (S->iter < S->maxit))) kry_end(S, 1);
-      else bicg_head(S);
-    }
-  }
-  if constexpr (OP == kQmrsDelta0) {  // first iteration: delta = K v1 . v1, then the head
-    r[QM_DELTA] = r[QM_OUT];
-    qmrs_head(S);
-  }
-  if constexpr (OP == kQmrsEps) {  // eps0 = g . t; beta = eps0 / delta
-    r[QM_EPS0] = r[QM_OUT];
-    r[QM_BETA] = r[QM_EPS0] / r[QM_DELTA];
-  }
-  if constexpr (OP == kQmrsRho) {  // qmrs.c: rho1 = ||v1||, theta, c1, eta0, tau, the coefficients of the d / x update
-    const double rho1 = sqrt(r[QM_OUT]);
-    const double beta = r[QM_BETA], c0 = r[QM_C0];
-    r[QM_RHO1] = rho1;
-    r[QM_XI1] = rho1;
-    if (c0 * fabs(beta) == 0.0) {
-      kry_end(S, 6);
-      return;
-    }
-    const double theta = rho1 / (c0 * fabs(beta));
-    const double c1 = 1.0 / sqrt(theta * theta + 1.0);
-    r[QM_THETA] = theta;
-    r[QM_C1] = c1;
-    if (beta * (c0 * c0) == 0.0) {
-      kry_end(S, 6);
-      return;
-    }
-    r[QM_ETA0] = -r[QM_ETA0] * r[QM_RHO0] * (c1 * c1) / (beta * (c0 * c0));
-    r[QM_TAU] = r[QM_TAU] * theta * c1;
-    if (rho1 == 0.0) {
-      kry_end(S, 6);
-      return;
-    }
-    const double d1 = r[QM_THETA0] * c1;
-    r[QM_CC2] = d1 * d1;
-    r[QM_RHO1INV] = 1.0 / rho1;
-  }
-  if constexpr (OP == kQmrsDelta) {  // delta of the next iteration; the tail of this one; the next one's head
-    r[QM_DELTA] = r[QM_OUT];
-    if (r[QM_XI1] == 0.0) {
-      kry_end(S, 6);
-      return;
-    }
-    r[QM_RHO0] = r[QM_RHO1];
-    r[QM_ERR] = r[QM_TAU] / r[QM_RESINIT];
-    r[QM_C0] = r[QM_C1];
-    r[QM_THETA0] = r[QM_THETA];
-    qmrs_head(S);
-  }
-}
-
 // kBicgTt: t . s (the product's epilogue) and t . t (a pass of its own) in ONE finishing launch, then omega
 template <int OP>
 struct KryStep : StepOf<KryDev, 0, OP == kBicgTt, true> {
@@ -1611,6 +1352,86 @@ struct KryStep : StepOf<KryDev, 0, OP == kBicgTt, true> {
 bool kry_devscal_enabled() {  // read per solve (A/B inside one process)
   const char *e = psp::tuning_env("PSP_KRY_DEVSCAL");
   return e ? atoi(e) != 0 : true;
+}
+
+// Where the scalars of a fused loop live.  A loop body is written once against these two forms:
+//   step<OP>(np, nvals, reg)   adds the workspace's partial sums into registers reg .. and takes kry_step<OP> (psp_recur.h);
+//                              step2: two single sums, the second from the second array of partial sums
+//   val(i), arg(i0, ...)       a vector kernel's scalar operands: by value, and as KryArg -- the kernels accept both
+//   skip()                     what the products look at to become no-ops
+//   ended()                    the loop is known to be over; the device form learns that only from poll(), once per batch,
+//                              and its launches behind the end are no-ops
+struct KryOnDevice {
+  static constexpr int kBatch = kKryBatch;
+  Workspace *w;
+  LoopState<KryDev> st;
+  KryDev *S = nullptr;
+  int begin(const KryDev &init) {
+    PSP_TRY(st.init());
+    *st.host = init;
+    PSP_TRY(st.upload());
+    S = st.dev;
+    return PSP_OK;
+  }
+  const int *skip() const { return &S->status; }
+  double val(int) const { return 0.0; }
+  KryArg arg(int i0, int i1 = 0, int i2 = 0) const { return KryArg{S, i0, i1, i2}; }
+  template <int OP>
+  int step(int np, int nvals, int reg) {
+    return reduce_then<KryStep<OP>>(w->partials, np, nvals, S->r + reg, S);
+  }
+  template <int OP>
+  int step2(int np0, int reg0, int np1, int reg1) {
+    return reduce2_then<KryStep<OP>>(w->partials, np0, S->r + reg0, w->partials + kMaxParts, np1, S->r + reg1, S, 0, 1);
+  }
+  bool ended() const { return false; }
+  int poll() { return st.fetch(); }
+  const KryDev &state() const { return *st.host; }
+};
+struct KryOnHost {
+  static constexpr int kBatch = 1;  // looks at status after every step
+  Workspace *w;
+  KryDev H;
+  int begin(const KryDev &init) {
+    H = init;
+    return PSP_OK;
+  }
+  const int *skip() const { return nullptr; }
+  double val(int i) const { return H.r[i]; }
+  KryArg arg(int, int = 0, int = 0) const { return KryArg(); }
+  template <int OP>
+  int step(int np, int nvals, int reg) {
+    PSP_TRY(reduce_fetch(w, np, nvals, H.r + reg));
+    kry_step<OP>(&H);
+    return PSP_OK;
+  }
+  template <int OP>
+  int step2(int np0, int reg0, int np1, int reg1) {
+    PSP_TRY(reduce_fetch(w, np0, 1, H.r + reg0));
+    PSP_TRY(finish_partials_fetch(w->partials + kMaxParts, np1, 1, w->scal_dev, H.r + reg1));
+    kry_step<OP>(&H);
+    return PSP_OK;
+  }
+  bool ended() const { return H.status != 0; }
+  int poll() { return PSP_OK; }
+  const KryDev &state() const { return H; }
+};
+
+// runs loop(scalars) from the state *H with the scalars on the device or on the host; *H: the state it ended in
+template <class Loop>
+int kry_run(bool on_device, Workspace *w, KryDev *H, Loop &&loop) {
+  if (on_device) {
+    KryOnDevice sc{w};
+    PSP_TRY(sc.begin(*H));
+    PSP_TRY(loop(sc));
+    *H = sc.state();
+    return PSP_OK;
+  }
+  KryOnHost sc{w};
+  PSP_TRY(sc.begin(*H));
+  PSP_TRY(loop(sc));
+  *H = sc.state();
+  return PSP_OK;
 }
 
 }  // namespace
@@ -1625,7 +1446,7 @@ static int cgs_device(const psp_op *A, const psp_op *K, int n, double *x, const 
   double *r0, *r, *p, *q, *u, *v, *tmp, *tmp2;
   for (double **pp : {&r0, &r, &p, &q, &u, &v, &tmp, &tmp2}) PSP_TRY(mem.alloc(n, pp));
   const double tol_sq = tol * tol;
-  double alpha, beta, rho, rho_new, bnrm_sq, d;
+  double rho, bnrm_sq;
   *iter = 0;
   PSP_TRY(op_apply(A, x, tmp));
   PSP_TRY(B.copy(b, r0));
@@ -1640,6 +1461,11 @@ static int cgs_device(const psp_op *A, const psp_op *K, int n, double *x, const 
     *info = 0;
     return PSP_OK;
   }
+  KryDev H = {};  // the recurrences: kry_step<kCgsD / kCgsR> (psp_recur.h)
+  H.r[CG_RHO] = rho;
+  H.r[CG_THR] = bnrm_sq * tol_sq;
+  H.r[CG_RES] = *res;  // maxit < 1: cgs.c takes the root of what the caller left there
+  H.maxit = maxit;
   // Native matrix + None / jacobi(1): three fused passes (psp_vec.hip: cgs_q / cgs_r / cgs_p -- per element the copy +
   // daxpy pairs of the reference, quick returns included), v.r0 on the first product: ~17 instead of ~44 vector
   // streams per iteration.  PSP_CGS_FUSED=0 keeps the unfused sequence below (A/B).
@@ -1649,98 +1475,65 @@ static int cgs_device(const psp_op *A, const psp_op *K, int n, double *x, const 
   }();
   psp_csr *Acsr = op_native_csr(A);
   const double *dinv = fused_dinv(K);
-  if (fuse_on && Acsr && !Acsr->nparts && (K == nullptr || dinv != nullptr)) {
+  if (maxit < 1) {  // cgs.c's for-loop does not run
+  } else if (fuse_on && Acsr && !Acsr->nparts && (K == nullptr || dinv != nullptr)) {
     double *kp = p;  // no preconditioner: K p is p
     if (K) {
       PSP_TRY(mem.alloc(n, &kp));
       PSP_TRY(op_apply(K, p, kp));
     }
-    double sc[2];
-    int np;
-    if (kry_devscal_enabled() && maxit >= 1 && csr_spmv_has_skip(Acsr)) {
-      LoopState<KryDev> st;
-      PSP_TRY(st.init());
-      st.host->r[CG_RHO] = rho;
-      st.host->r[CG_THR] = bnrm_sq * tol_sq;
-      st.host->maxit = maxit;
-      PSP_TRY(st.upload());
-      KryDev *S = st.dev;
+    PSP_TRY(kry_run(kry_devscal_enabled() && csr_spmv_has_skip(Acsr), w, &H, [&](auto &sc) -> int {
+      int np;
       do {
-        for (int k = 0; k < kKryBatch; ++k) {
-          PSP_TRY(csr_spmv_launch(Acsr, kp, v, r0, w->partials, &np, &S->status));
-          PSP_TRY(reduce_then<KryStep<kCgsD>>(w->partials, np, 1, S->r + CG_D, S));
-          PSP_TRY(k_cgs_q(n, u, v, x, q, tmp2, dinv, 0.0, KryArg{S, CG_ALPHA}));
-          PSP_TRY(csr_spmv_launch(Acsr, tmp2, tmp, nullptr, nullptr, nullptr, &S->status));
-          PSP_TRY(k_cgs_r(n, r, tmp, r0, 0.0, w->partials, &np, KryArg{S, CG_ALPHA}));
-          PSP_TRY(reduce_then<KryStep<kCgsR>>(w->partials, np, 2, S->r + CG_RES, S));
-          PSP_TRY(k_cgs_p(n, r, q, p, u, kp, dinv, 0.0, KryArg{S, CG_BETA}));
+        for (int k = 0; k < sc.kBatch; ++k) {
+          PSP_TRY(csr_spmv_launch(Acsr, kp, v, r0, w->partials, &np, sc.skip()));
+          PSP_TRY(sc.template step<kCgsD>(np, 1, CG_D));
+          PSP_TRY(k_cgs_q(n, u, v, x, q, tmp2, dinv, sc.val(CG_ALPHA), sc.arg(CG_ALPHA)));
+          PSP_TRY(csr_spmv_launch(Acsr, tmp2, tmp, nullptr, nullptr, nullptr, sc.skip()));
+          PSP_TRY(k_cgs_r(n, r, tmp, r0, sc.val(CG_ALPHA), w->partials, &np, sc.arg(CG_ALPHA)));
+          PSP_TRY(sc.template step<kCgsR>(np, 2, CG_RES));
+          if (sc.ended()) break;
+          PSP_TRY(k_cgs_p(n, r, q, p, u, kp, dinv, sc.val(CG_BETA), sc.arg(CG_BETA)));
         }
-        PSP_TRY(st.fetch());
-      } while (!st.host->status);
-      *iter = st.host->iter;
-      *res = sqrt(st.host->r[CG_RES] / bnrm_sq);
-      *info = st.host->code == 1 ? 0 : -1;
+        PSP_TRY(sc.poll());
+      } while (!sc.state().status);
       return PSP_OK;
-    }
-    for (; *iter < maxit; (*iter)++) {
-      PSP_TRY(csr_spmv_launch(Acsr, kp, v, r0, w->partials, &np, nullptr));
-      PSP_TRY(reduce_fetch(w, np, 1, &d));
-      alpha = rho / d;
-      PSP_TRY(k_cgs_q(n, u, v, x, q, tmp2, dinv, alpha));
-      PSP_TRY(csr_spmv_launch(Acsr, tmp2, tmp, nullptr, nullptr, nullptr, nullptr));
-      PSP_TRY(k_cgs_r(n, r, tmp, r0, alpha, w->partials, &np));
-      PSP_TRY(reduce_fetch(w, np, 2, sc));
-      *res = sc[0];
-      if (*res < bnrm_sq * tol_sq) {
-        *res = sqrt(*res / bnrm_sq);
-        *info = 0;
-        return PSP_OK;
+    }));
+  } else {
+    while (!H.status) {
+      if (K) {
+        PSP_TRY(op_apply(K, p, tmp));
+        PSP_TRY(op_apply(A, tmp, v));
+      } else {
+        PSP_TRY(op_apply(A, p, v));
       }
-      rho_new = sc[1];
-      beta = rho_new / rho;
-      rho = rho_new;
-      PSP_TRY(k_cgs_p(n, r, q, p, u, kp, dinv, beta));
+      PSP_TRY(B.dot(v, r0, &H.r[CG_D]));
+      kry_step<kCgsD>(&H);
+      const double alpha = H.r[CG_ALPHA], ddummy = -alpha;
+      PSP_TRY(B.copy(u, q));
+      PSP_TRY(B.axpy(ddummy, v, q));
+      PSP_TRY(B.copy(u, tmp));
+      PSP_TRY(B.axpy(1.0, q, tmp));
+      PSP_TRY(apply_or_copy(K, n, tmp, tmp2));
+      PSP_TRY(B.axpy(alpha, tmp2, x));
+      PSP_TRY(op_apply(A, tmp2, tmp));
+      PSP_TRY(B.axpy(ddummy, tmp, r));
+      PSP_TRY(B.dot(r, r, &H.r[CG_RES]));
+      if (cgs_converged(&H)) break;
+      PSP_TRY(B.dot(r, r0, &H.r[CG_RHONEW]));
+      cgs_next(&H);
+      const double beta = H.r[CG_BETA];
+      PSP_TRY(B.copy(r, u));
+      PSP_TRY(B.axpy(beta, q, u));
+      PSP_TRY(B.copy(q, tmp));
+      PSP_TRY(B.axpy(beta, p, tmp));
+      PSP_TRY(B.copy(u, p));
+      PSP_TRY(B.axpy(beta, tmp, p));
     }
-    *res = sqrt(*res / bnrm_sq);
-    *info = -1;
-    return PSP_OK;
   }
-  for (; *iter < maxit; (*iter)++) {
-    if (K) {
-      PSP_TRY(op_apply(K, p, tmp));
-      PSP_TRY(op_apply(A, tmp, v));
-    } else {
-      PSP_TRY(op_apply(A, p, v));
-    }
-    PSP_TRY(B.dot(v, r0, &d));
-    alpha = rho / d;
-    const double ddummy = -alpha;
-    PSP_TRY(B.copy(u, q));
-    PSP_TRY(B.axpy(ddummy, v, q));
-    PSP_TRY(B.copy(u, tmp));
-    PSP_TRY(B.axpy(1.0, q, tmp));
-    PSP_TRY(apply_or_copy(K, n, tmp, tmp2));
-    PSP_TRY(B.axpy(alpha, tmp2, x));
-    PSP_TRY(op_apply(A, tmp2, tmp));
-    PSP_TRY(B.axpy(ddummy, tmp, r));
-    PSP_TRY(B.dot(r, r, res));
-    if (*res < bnrm_sq * tol_sq) {
-      *res = sqrt(*res / bnrm_sq);
-      *info = 0;
-      return PSP_OK;
-    }
-    PSP_TRY(B.dot(r, r0, &rho_new));
-    beta = rho_new / rho;
-    rho = rho_new;
-    PSP_TRY(B.copy(r, u));
-    PSP_TRY(B.axpy(beta, q, u));
-    PSP_TRY(B.copy(q, tmp));
-    PSP_TRY(B.axpy(beta, p, tmp));
-    PSP_TRY(B.copy(u, p));
-    PSP_TRY(B.axpy(beta, tmp, p));
-  }
-  *res = sqrt(*res / bnrm_sq);
-  *info = -1;
+  *iter = H.iter;
+  *res = sqrt(H.r[CG_RES] / bnrm_sq);
+  *info = H.code == 1 ? 0 : -1;  // 1: converged; else the for-loop ran out
   return PSP_OK;
 }
 
@@ -1753,7 +1546,7 @@ static int bicgstab_device(const psp_op *A, const psp_op *K, int n, double *x, c
   DevVecs mem;
   double *r, *rhat, *p, *phat, *v, *s, *shat, *t;
   for (double **pp : {&r, &rhat, &p, &phat, &v, &s, &shat, &t}) PSP_TRY(mem.alloc(n, pp));
-  double alpha = 0.0, omega = 0.0, rho_im1, rho_im2 = 0.0, beta, res, res0, n2b, d1, d2;
+  double rho, res0, n2b;
   *info = -6;
   PSP_TRY(B.nrm2(b, &n2b));
   if (n2b == 0.0) {
@@ -1767,7 +1560,18 @@ static int bicgstab_device(const psp_op *A, const psp_op *K, int n, double *x, c
   PSP_TRY(k_lin2(n, 1.0, b, -1.0, r, r));  // r = b + -r
   PSP_TRY(B.nrm2(r, &res0));
   PSP_TRY(B.copy(r, rhat));
-  *iter = 0;
+  // the first iteration's head, on the host.  Every later rho = rhat . r is formed where the iteration before has
+  // updated r (bicgstab.c forms it at the top of the loop: the same dot of the same vectors), so that one recurrence,
+  // kry_step<kBicgD1 / kBicgTt / kBicgXr> (psp_recur.h), serves all three loops
+  *iter = 1;
+  PSP_TRY(B.dot(rhat, r, &rho));
+  if (rho == 0.0) return PSP_OK;  // info stays -6 (the module ignores the kernel's -1)
+  KryDev H = {};
+  H.r[BI_RHO1] = rho;
+  H.r[BI_RES0] = res0;
+  H.r[BI_TOL] = tol;
+  H.iter = 1;
+  H.maxit = maxit;
   // Native matrix + None / jacobi(1): the vector passes of one iteration are three fused kernels (psp_vec.hip:
   // bicg_p / bicg_s / bicg_xr -- the same rounded operations per element), d1 = rhat.v and t.s ride on the two
   // products, the next rho on the last pass: ~21 instead of 32 vector streams per iteration.
@@ -1780,101 +1584,65 @@ static int bicgstab_device(const psp_op *A, const psp_op *K, int n, double *x, c
   const double *dinv = fused_dinv(K);
   if (fuse_on && Acsr && !Acsr->nparts && (K == nullptr || dinv != nullptr)) {
     double *ph = K ? phat : p, *sh = K ? shat : s;  // no preconditioner: phat is p, shat is s
-    double sc[2];
-    int np;
-    PSP_TRY(B.dot(rhat, r, &rho_im1));
-    if (kry_devscal_enabled() && maxit >= 1 && csr_spmv_has_skip(Acsr)) {
-      *iter = 1;
-      if (rho_im1 == 0.0) return PSP_OK;  // the first iteration's head, on the host
-      LoopState<KryDev> st;
-      PSP_TRY(st.init());
-      st.host->r[BI_RHO1] = rho_im1;
-      st.host->r[BI_RES0] = res0;
-      st.host->r[BI_TOL] = tol;
-      st.host->iter = 1;
-      st.host->maxit = maxit;
-      PSP_TRY(st.upload());
-      KryDev *S = st.dev;
-      int np2;
+    const bool devscal = kry_devscal_enabled() && maxit >= 1 && csr_spmv_has_skip(Acsr);
+    PSP_TRY(kry_run(devscal, w, &H, [&](auto &sc) -> int {
+      int np, np2;
       do {
-        for (int k = 0; k < kKryBatch; ++k) {
-          PSP_TRY(k_bicg_p(n, r, v, p, ph, dinv, 0.0, 0.0, false, KryArg{S, BI_BETA, BI_OMEGA}));  // first: S->iter == 1
-          PSP_TRY(csr_spmv_launch(Acsr, ph, v, rhat, w->partials, &np, &S->status));
-          PSP_TRY(reduce_then<KryStep<kBicgD1>>(w->partials, np, 1, S->r + BI_D1, S));
-          PSP_TRY(k_bicg_s(n, r, v, s, sh, dinv, 0.0, KryArg{S, BI_ALPHA}));
-          PSP_TRY(csr_spmv_launch(Acsr, sh, t, s, w->partials, &np, &S->status));
-          // t . t into the second array of partial sums (runs once more after the loop has ended: its result is ignored);
-          // ONE finishing launch for t . s, t . t and omega
+        for (int k = 0; k < sc.kBatch; ++k) {
+          // (first iteration: by value for the host form; the device form's kernel looks at S->iter itself)
+          PSP_TRY(k_bicg_p(n, r, v, p, ph, dinv, sc.val(BI_BETA), sc.val(BI_OMEGA), sc.state().iter == 1,
+                           sc.arg(BI_BETA, BI_OMEGA)));
+          PSP_TRY(csr_spmv_launch(Acsr, ph, v, rhat, w->partials, &np, sc.skip()));
+          PSP_TRY(sc.template step<kBicgD1>(np, 1, BI_D1));
+          PSP_TRY(k_bicg_s(n, r, v, s, sh, dinv, sc.val(BI_ALPHA), sc.arg(BI_ALPHA)));
+          PSP_TRY(csr_spmv_launch(Acsr, sh, t, s, w->partials, &np, sc.skip()));
+          // t . t into the second array of partial sums (device form: runs once more after the loop has ended, its result
+          // is ignored; ONE finishing launch for t . s, t . t and omega)
           PSP_TRY(k_dot(n, t, t, w->partials + kMaxParts, &np2));
-          PSP_TRY(reduce2_then<KryStep<kBicgTt>>(w->partials, np, S->r + BI_D1, w->partials + kMaxParts, np2,
-                                                 S->r + BI_D2, S, 0, 1));
-          PSP_TRY(k_bicg_xr(n, x, ph, sh, s, t, r, rhat, 0.0, 0.0, w->partials, &np, KryArg{S, BI_ALPHA, BI_OMEGA}));
-          PSP_TRY(reduce_then<KryStep<kBicgXr>>(w->partials, np, 2, S->r + BI_RR, S));
+          PSP_TRY(sc.template step2<kBicgTt>(np, BI_D1, np2, BI_D2));
+          PSP_TRY(k_bicg_xr(n, x, ph, sh, s, t, r, rhat, sc.val(BI_ALPHA), sc.val(BI_OMEGA), w->partials, &np,
+                            sc.arg(BI_ALPHA, BI_OMEGA)));
+          PSP_TRY(sc.template step<kBicgXr>(np, 2, BI_RR));  // {r . r, rhat . r}
+          if (sc.ended()) break;
         }
-        PSP_TRY(st.fetch());
-      } while (!st.host->status);
-      *iter = st.host->iter;
-      if (st.host->code == 1) {
-        *relres = st.host->r[BI_RES] / res0;
-        *info = (*relres >= tol) ? -1 : 0;
-      }
-      return PSP_OK;  // codes 3 / 4: rho == 0 / omega == 0 -- info stays -6, relres untouched, like the returns below
-    }
+        PSP_TRY(sc.poll());
+      } while (!sc.state().status);
+      return PSP_OK;
+    }));
+  } else {
     do {
-      (*iter)++;
-      if (rho_im1 == 0.0) return PSP_OK;
-      beta = *iter == 1 ? 0.0 : (rho_im1 / rho_im2) * (alpha / omega);
-      PSP_TRY(k_bicg_p(n, r, v, p, ph, dinv, beta, omega, *iter == 1));
-      PSP_TRY(csr_spmv_launch(Acsr, ph, v, rhat, w->partials, &np, nullptr));
-      PSP_TRY(reduce_fetch(w, np, 1, &d1));
-      alpha = rho_im1 / d1;
-      PSP_TRY(k_bicg_s(n, r, v, s, sh, dinv, alpha));
-      PSP_TRY(csr_spmv_launch(Acsr, sh, t, s, w->partials, &np, nullptr));
-      PSP_TRY(reduce_fetch(w, np, 1, &d1));
-      PSP_TRY(B.dot(t, t, &d2));
-      omega = d1 / d2;
-      PSP_TRY(k_bicg_xr(n, x, ph, sh, s, t, r, rhat, alpha, omega, w->partials, &np));
-      PSP_TRY(reduce_fetch(w, np, 2, sc));
-      res = sqrt(sc[0]);
-      if (omega == 0.0) return PSP_OK;
-      rho_im2 = rho_im1;
-      rho_im1 = sc[1];  // rhat . r of the next iteration (bicgstab.c computes it at the top of the loop)
-    } while ((res / res0 > tol) && (*iter < maxit));
-    *relres = res / res0;
-    *info = (*relres >= tol) ? -1 : 0;
-    return PSP_OK;
+      if (H.iter == 1) {
+        PSP_TRY(B.copy(r, p));
+      } else {
+        PSP_TRY(k_lin2(n, 1.0, p, -H.r[BI_OMEGA], v, t));  // t is free here: p - omega*v
+        PSP_TRY(k_lin2(n, 1.0, r, H.r[BI_BETA], t, p));    // p = r + beta*(p - omega*v)
+      }
+      PSP_TRY(apply_or_copy(K, n, p, phat));
+      PSP_TRY(op_apply(A, phat, v));
+      PSP_TRY(B.dot(rhat, v, &H.r[BI_D1]));
+      kry_step<kBicgD1>(&H);
+      const double alpha = H.r[BI_ALPHA];
+      PSP_TRY(k_lin2(n, 1.0, r, -alpha, v, s));  // v_plus_cw(n, r, v, -alpha, s)
+      PSP_TRY(apply_or_copy(K, n, s, shat));
+      PSP_TRY(op_apply(A, shat, t));
+      PSP_TRY(B.dot(t, s, &H.r[BI_D1]));
+      PSP_TRY(B.dot(t, t, &H.r[BI_D2]));
+      kry_step<kBicgTt>(&H);
+      const double omega = H.r[BI_OMEGA];
+      PSP_TRY(k_lin2(n, 1.0, x, alpha, phat, x));  // x = x + alpha*phat ...
+      PSP_TRY(k_lin2(n, 1.0, x, omega, shat, x));  // ... + omega*shat
+      PSP_TRY(k_lin2(n, 1.0, s, -omega, t, r));    // r = s - omega*t
+      PSP_TRY(B.dot(r, r, &H.r[BI_RR]));
+      PSP_TRY(B.dot(rhat, r, &H.r[BI_RHONEXT]));
+      kry_step<kBicgXr>(&H);
+    } while (!H.status);
   }
-  do {
-    (*iter)++;
-    PSP_TRY(B.dot(rhat, r, &rho_im1));
-    if (rho_im1 == 0.0) return PSP_OK;  // info stays -6 (the module ignores the kernel's -1)
-    if (*iter == 1) {
-      PSP_TRY(B.copy(r, p));
-    } else {
-      beta = (rho_im1 / rho_im2) * (alpha / omega);
-      PSP_TRY(k_lin2(n, 1.0, p, -omega, v, t));  // t is free here: p - omega*v
-      PSP_TRY(k_lin2(n, 1.0, r, beta, t, p));    // p = r + beta*(p - omega*v)
-    }
-    PSP_TRY(apply_or_copy(K, n, p, phat));
-    PSP_TRY(op_apply(A, phat, v));
-    PSP_TRY(B.dot(rhat, v, &d1));
-    alpha = rho_im1 / d1;
-    PSP_TRY(k_lin2(n, 1.0, r, -alpha, v, s));  // v_plus_cw(n, r, v, -alpha, s)
-    PSP_TRY(apply_or_copy(K, n, s, shat));
-    PSP_TRY(op_apply(A, shat, t));
-    PSP_TRY(B.dot(t, s, &d1));
-    PSP_TRY(B.dot(t, t, &d2));
-    omega = d1 / d2;
-    PSP_TRY(k_lin2(n, 1.0, x, alpha, phat, x));  // x = x + alpha*phat ...
-    PSP_TRY(k_lin2(n, 1.0, x, omega, shat, x));  // ... + omega*shat
-    PSP_TRY(k_lin2(n, 1.0, s, -omega, t, r));    // r = s - omega*t
-    PSP_TRY(B.nrm2(r, &res));
-    if (omega == 0.0) return PSP_OK;
-    rho_im2 = rho_im1;
-  } while ((res / res0 > tol) && (*iter < maxit));
-  *relres = res / res0;
-  *info = (*relres >= tol) ? -1 : 0;
-  return PSP_OK;
+  *iter = H.iter;
+  if (H.code == 1) {  // the loop test failed: normal end
+    *relres = H.r[BI_RES] / res0;
+    *info = (*relres >= tol) ? -1 : 0;
+  }
+  return PSP_OK;  // codes 3 / 4: rho == 0 / omega == 0 -- info stays -6, relres untouched, like the reference's returns
 }
 
 // pysparse/itsolvers/src/qmrs.c:29-154
@@ -1886,24 +1654,26 @@ static int qmrs_device(const psp_op *A, const psp_op *K, int n, double *x, const
   DevVecs mem;
   double *wrk1, *p, *d, *v1, *t, *g;
   for (double **pp : {&wrk1, &p, &d, &v1, &t, &g}) PSP_TRY(mem.alloc(n, pp));
-  double beta, res_init, delta, theta, c0, c1, theta0, cc, xi1, rho1inv, tau, eta0, eps0, rho0, rho1, d1;
+  double rho0;
   PSP_TRY(B.copy(b, v1));
   PSP_TRY(B.nrm2(v1, &rho0));
-  tau = rho0;
   PSP_TRY(k_scale_div(n, v1, rho0, v1));
   PSP_TRY(B.zero(p));
   PSP_TRY(B.zero(g));
   PSP_TRY(B.zero(d));
   PSP_TRY(B.zero(x));
-  c0 = 1.0;
-  eps0 = 1.0;
-  xi1 = 1.0;
-  theta0 = 0.0;
-  eta0 = -1.0;
-  res_init = rho0;
-  *err = 1.0;
-  *iter = 0;
-#define QMRS_RET(code) do { *info = (code); PSP_HIP(hipStreamSynchronize(stream())); return PSP_OK; } while (0)
+  KryDev H = {};  // the recurrences: qmrs_head / kry_step<kQmrs...> / qmrs_tail (psp_recur.h)
+  H.r[QM_RHO0] = rho0;
+  H.r[QM_TAU] = rho0;
+  H.r[QM_C0] = 1.0;
+  H.r[QM_EPS0] = 1.0;
+  H.r[QM_XI1] = 1.0;
+  H.r[QM_THETA0] = 0.0;
+  H.r[QM_ETA0] = -1.0;
+  H.r[QM_ERR] = 1.0;
+  H.r[QM_RESINIT] = rho0;
+  H.r[QM_TOL] = tol;
+  H.maxit = maxit;
   // Native matrix + None / jacobi(1): four fused passes (psp_vec.hip: qmrs_kv / qmrs_pg / qmrs_v / qmrs_dx -- the same
   // rounded operations per element), g.t on the product, K v1 and its dot for the next iteration on the last pass:
   // 17 instead of 25 vector streams per iteration.  PSP_QMRS_FUSED=0 keeps the unfused sequence below (A/B).
@@ -1915,128 +1685,61 @@ static int qmrs_device(const psp_op *A, const psp_op *K, int n, double *x, const
   const double *dinv = fused_dinv(K);
   if (fuse_on && Acsr && !Acsr->nparts && (K == nullptr || dinv != nullptr)) {
     double *kv = K ? wrk1 : v1;  // no preconditioner: K v1 is v1
-    int np;
-    bool have_delta = false;
-    if (kry_devscal_enabled() && csr_spmv_has_skip(Acsr)) {
-      LoopState<KryDev> st;
-      PSP_TRY(st.init());
-      double *R = st.host->r;
-      R[QM_RHO0] = rho0;
-      R[QM_TAU] = tau;
-      R[QM_C0] = c0;
-      R[QM_EPS0] = eps0;
-      R[QM_XI1] = xi1;
-      R[QM_THETA0] = theta0;
-      R[QM_ETA0] = eta0;
-      R[QM_ERR] = *err;
-      R[QM_RESINIT] = res_init;
-      R[QM_TOL] = tol;
-      st.host->maxit = maxit;
-      PSP_TRY(st.upload());
-      KryDev *S = st.dev;
+    PSP_TRY(kry_run(kry_devscal_enabled() && csr_spmv_has_skip(Acsr), w, &H, [&](auto &sc) -> int {
+      int np;
       // K v1 . v1 of the first iteration, then its head (the later ones get theirs from the d / x pass)
       PSP_TRY(k_qmrs_kv(n, v1, kv, dinv, w->partials, &np));
-      PSP_TRY(reduce_then<KryStep<kQmrsDelta0>>(w->partials, np, 1, S->r + QM_OUT, S));
+      PSP_TRY(sc.template step<kQmrsDelta0>(np, 1, QM_OUT));
+      if (sc.ended()) return PSP_OK;
       do {
-        for (int k = 0; k < kKryBatch; ++k) {
-          PSP_TRY(k_qmrs_pg(n, v1, kv, p, g, 0.0, KryArg{S, QM_CC}));
-          PSP_TRY(csr_spmv_launch(Acsr, g, t, g, w->partials, &np, &S->status));
-          PSP_TRY(reduce_then<KryStep<kQmrsEps>>(w->partials, np, 1, S->r + QM_OUT, S));
-          PSP_TRY(k_qmrs_v(n, t, v1, 0.0, w->partials, &np, KryArg{S, QM_BETA}));
-          PSP_TRY(reduce_then<KryStep<kQmrsRho>>(w->partials, np, 1, S->r + QM_OUT, S));
-          PSP_TRY(k_qmrs_dx(n, p, d, x, v1, kv, dinv, 0.0, 0.0, 0.0, w->partials, &np, KryArg{S, QM_ETA0, QM_CC2, QM_RHO1INV}));
-          PSP_TRY(reduce_then<KryStep<kQmrsDelta>>(w->partials, np, 1, S->r + QM_OUT, S));
+        for (int k = 0; k < sc.kBatch; ++k) {
+          PSP_TRY(k_qmrs_pg(n, v1, kv, p, g, sc.val(QM_CC), sc.arg(QM_CC)));
+          PSP_TRY(csr_spmv_launch(Acsr, g, t, g, w->partials, &np, sc.skip()));
+          PSP_TRY(sc.template step<kQmrsEps>(np, 1, QM_OUT));
+          PSP_TRY(k_qmrs_v(n, t, v1, sc.val(QM_BETA), w->partials, &np, sc.arg(QM_BETA)));
+          PSP_TRY(sc.template step<kQmrsRho>(np, 1, QM_OUT));
+          if (sc.ended()) break;
+          PSP_TRY(k_qmrs_dx(n, p, d, x, v1, kv, dinv, sc.val(QM_ETA0), sc.val(QM_CC2), sc.val(QM_RHO1INV), w->partials, &np,
+                            sc.arg(QM_ETA0, QM_CC2, QM_RHO1INV)));
+          PSP_TRY(sc.template step<kQmrsDelta>(np, 1, QM_OUT));  // K v1 . v1 of the next iteration
+          if (sc.ended()) break;
         }
-        PSP_TRY(st.fetch());
-      } while (!st.host->status);
-      *iter = st.host->iter;
-      *err = st.host->r[QM_ERR];
-      if (st.host->code != 1) QMRS_RET(-st.host->code);  // 6 -> -6, 2 -> -2: left by a breakdown test
-      if (K) {
-        PSP_TRY(op_apply(K, x, wrk1));
-        PSP_TRY(B.copy(wrk1, x));
-      }
-      *info = (*err < tol) ? 0 : -1;
+        PSP_TRY(sc.poll());
+      } while (!sc.state().status);
       return PSP_OK;
+    }));
+  } else {
+    for (;;) {
+      qmrs_head(&H);
+      if (H.status) break;
+      PSP_TRY(apply_or_copy(K, n, v1, wrk1));
+      PSP_TRY(B.dot(wrk1, v1, &H.r[QM_DELTA]));
+      qmrs_head_delta(&H);
+      if (H.status) break;
+      const double cc = H.r[QM_CC];
+      PSP_TRY(k_lin2(n, 1.0, v1, -cc, p, p));    // p = v1 - p*cc
+      PSP_TRY(k_lin2(n, 1.0, wrk1, -cc, g, g));  // g = wrk1 - g*cc
+      PSP_TRY(op_apply(A, g, t));
+      PSP_TRY(B.dot(g, t, &H.r[QM_OUT]));
+      kry_step<kQmrsEps>(&H);
+      PSP_TRY(k_lin2(n, 1.0, t, -H.r[QM_BETA], v1, v1));  // v1 = t - v1*beta
+      PSP_TRY(B.dot(v1, v1, &H.r[QM_OUT]));
+      kry_step<kQmrsRho>(&H);
+      if (H.status) break;
+      PSP_TRY(k_lin2(n, H.r[QM_ETA0], p, H.r[QM_CC2], d, d));  // d = p*eta0 + d*cc
+      PSP_TRY(k_lin2(n, 1.0, x, 1.0, d, x));                   // x += d
+      PSP_TRY(k_scal(n, H.r[QM_RHO1INV], v1));                 // v1 *= rho1inv
+      qmrs_tail(&H);
+      if (H.status) break;
     }
-    while (*err > tol && *iter < maxit) {
-      ++(*iter);
-      if (eps0 == 0.0) QMRS_RET(-6);
-      if (!have_delta) {
-        PSP_TRY(k_qmrs_kv(n, v1, kv, dinv, w->partials, &np));
-        PSP_TRY(reduce_fetch(w, np, 1, &delta));
-      }
-      if (delta == 0.0) QMRS_RET(-2);
-      cc = xi1 * (delta / eps0);
-      PSP_TRY(k_qmrs_pg(n, v1, kv, p, g, cc));
-      PSP_TRY(csr_spmv_launch(Acsr, g, t, g, w->partials, &np, nullptr));
-      PSP_TRY(reduce_fetch(w, np, 1, &eps0));
-      beta = eps0 / delta;
-      PSP_TRY(k_qmrs_v(n, t, v1, beta, w->partials, &np));
-      PSP_TRY(reduce_fetch(w, np, 1, &rho1));
-      rho1 = sqrt(rho1);
-      xi1 = rho1;
-      if (c0 * fabs(beta) == 0.0) QMRS_RET(-6);
-      theta = rho1 / (c0 * fabs(beta));
-      c1 = 1.0 / sqrt(theta * theta + 1.0);
-      if (beta * (c0 * c0) == 0.0) QMRS_RET(-6);
-      eta0 = -eta0 * rho0 * (c1 * c1) / (beta * (c0 * c0));
-      tau = tau * theta * c1;
-      if (rho1 == 0.0) QMRS_RET(-6);
-      d1 = theta0 * c1;
-      cc = d1 * d1;
-      rho1inv = 1.0 / rho1;
-      PSP_TRY(k_qmrs_dx(n, p, d, x, v1, kv, dinv, eta0, cc, rho1inv, w->partials, &np));
-      PSP_TRY(reduce_fetch(w, np, 1, &delta));  // K v1 . v1 of the next iteration
-      have_delta = true;
-      if (xi1 == 0.0) QMRS_RET(-6);
-      rho0 = rho1;
-      *err = tau / res_init;
-      c0 = c1;
-      theta0 = theta;
-    }
-    if (K) {
-      PSP_TRY(op_apply(K, x, wrk1));
-      PSP_TRY(B.copy(wrk1, x));
-    }
-    *info = (*err < tol) ? 0 : -1;
+  }
+  *iter = H.iter;
+  *err = H.r[QM_ERR];
+  if (H.code != 1) {  // 6 -> -6, 2 -> -2: left by a breakdown test
+    *info = -H.code;
+    PSP_HIP(hipStreamSynchronize(stream()));
     return PSP_OK;
   }
-  while (*err > tol && *iter < maxit) {
-    ++(*iter);
-    if (eps0 == 0.0) QMRS_RET(-6);
-    PSP_TRY(apply_or_copy(K, n, v1, wrk1));
-    PSP_TRY(B.dot(wrk1, v1, &delta));
-    if (delta == 0.0) QMRS_RET(-2);
-    cc = xi1 * (delta / eps0);
-    PSP_TRY(k_lin2(n, 1.0, v1, -cc, p, p));    // p = v1 - p*cc
-    PSP_TRY(k_lin2(n, 1.0, wrk1, -cc, g, g));  // g = wrk1 - g*cc
-    PSP_TRY(op_apply(A, g, t));
-    PSP_TRY(B.dot(g, t, &eps0));
-    beta = eps0 / delta;
-    PSP_TRY(k_lin2(n, 1.0, t, -beta, v1, v1));  // v1 = t - v1*beta
-    PSP_TRY(B.nrm2(v1, &rho1));
-    xi1 = rho1;
-    if (c0 * fabs(beta) == 0.0) QMRS_RET(-6);
-    theta = rho1 / (c0 * fabs(beta));
-    c1 = 1.0 / sqrt(theta * theta + 1.0);
-    if (beta * (c0 * c0) == 0.0) QMRS_RET(-6);
-    eta0 = -eta0 * rho0 * (c1 * c1) / (beta * (c0 * c0));
-    tau = tau * theta * c1;
-    if (rho1 == 0.0) QMRS_RET(-6);
-    d1 = theta0 * c1;
-    cc = d1 * d1;
-    rho1inv = 1.0 / rho1;
-    PSP_TRY(k_lin2(n, eta0, p, cc, d, d));  // d = p*eta0 + d*cc
-    PSP_TRY(k_lin2(n, 1.0, x, 1.0, d, x));  // x += d
-    PSP_TRY(k_scal(n, rho1inv, v1));        // v1 *= rho1inv
-    if (xi1 == 0.0) QMRS_RET(-6);
-    rho0 = rho1;
-    *err = tau / res_init;
-    c0 = c1;
-    theta0 = theta;
-  }
-#undef QMRS_RET
   if (K) {
     PSP_TRY(op_apply(K, x, wrk1));
     PSP_TRY(B.copy(wrk1, x));
