@@ -494,6 +494,42 @@ int psp_bv_tdot(int n, int m, const double *V_dev, int64_t ld, const double *x_d
 int psp_bv_gemv(int n, int m, const double *V_dev, int64_t ld, const double *h_dev, double alpha, double beta,
                 double *y_dev);
 int psp_bv_rotate(int n, int j, double *V_dev, int64_t ld, const double *U_host, int ldu, int u0, int jn, int dst0);
+/* The block kernels of psp_lobpcg, same layout rules.
+ *   gram  : G[a + b ldg] = sum_i A[i,a] B[i,b] (ma x mb entries, nothing else of G is written), a thread keeping an
+ *           8 x 4 tile of sums, so A is streamed ceil(mb / 4) times and B ceil(ma / 8) times.  Column b of G has the bits
+ *           of psp_bv_tdot(n, ma, A, lda, B + b ldb, h) whenever both take the same access form: the 16-byte form iff n,
+ *           lda and ldb are even and both bases are 16-byte aligned (tdot alternates from column to column when ldb is
+ *           odd and n even: those columns agree to rounding only).  With A == B, G is exactly symmetric.
+ *   resid : for c < k (k <= 32): r = AX[:,c] - theta[c] MX[:,c] (the product rounded, then the difference), written to
+ *           R[:, slot[c]] where slot[c] >= 0 (slot_host: k ints on the host, distinct where >= 0 and < k) and nowhere
+ *           otherwise; nrm2[c] = r . r for every c with the bits of psp_bv_tdot(n, 1, R_c, ldr, R_c, h) on the stored
+ *           column.  MX_dev may be the X block itself; R must not overlap AX or MX. */
+int psp_bv_gram(int n, int ma, const double *A_dev, int64_t lda, int mb, const double *B_dev, int64_t ldb, double *G_dev,
+                int64_t ldg);
+int psp_bv_resid(int n, int k, const double *AX_dev, int64_t ldax, const double *MX_dev, int64_t ldmx,
+                 const double *theta_dev, const int *slot_host, double *R_dev, int64_t ldr, double *nrm2_dev);
+
+/* ------------------------------------------------------------------ psp_lobpcg: block eigensolver (psp_lobpcg.hip)
+ * The k smallest eigenpairs of A x = lambda M x by LOBPCG: A symmetric, M symmetric positive definite or NULL (identity),
+ * K a symmetric positive definite preconditioner for A or NULL; 1 <= k <= 32, 3 k <= n.  Every n-vector stays on the
+ * device; per iteration K is applied ONCE to the block of active residuals (psp_op_apply_block_dev: one block V-cycle for a
+ * multigrid handle) and A (and M) multiply ONE block.  X0_host: x0_cols (0 .. k) start columns, column-major with leading
+ * dimension ldx0; the other columns come from the device generator of psp_jdsym.  A column with ||A x - theta M x||_2 <=
+ * tol (x M-normalised; absolute, like jdtol) is soft-locked.  When every column passes, A X and M X are recomputed by
+ * explicit products and the test is repeated on them before the call returns.
+ * On return: lambda_host[k] ascending, X_host (n x k, column-major, leading dimension ldx) M-orthonormal, res_host[k] the
+ * explicit residual norms, *kconv the columns with res <= tol, *it the iterations done (itmax reached is not an error).
+ * psp_last_solve_info names the loop "lobpcg"; its info[2] is the number of restarts (Rayleigh-Ritz steps repeated without
+ * P because S' M S did not factor), info[0] and info[1] are -1.
+ * PSP_EINVAL: k or n out of range, tol <= 0, itmax < 0, operators of different order, multi-device or split operands --
+ * all before any device call; PSP_ENODEV with PSP_DEVICE=cpu. */
+int psp_lobpcg(const psp_op_t *A, const psp_op_t *M, const psp_op_t *K, int n, int k, double tol, int itmax,
+               const double *X0_host, int x0_cols, long ldx0, double *lambda_host, double *X_host, long ldx,
+               double *res_host, int *kconv, int *it);
+/* Test hook of its projected problem (no device needed): GA c = lambda GM c of order m <= 128, both matrices column-major
+ * with leading dimension ld and symmetrised on entry; lambda_host ascending, C_host (m x m, leading dimension ld) with
+ * C' GM C = I and C' GA C = diag(lambda).  PSP_ESINGULAR when GM is not positive definite. */
+int psp_debug_gen_ritz(int m, const double *GA_host, const double *GM_host, int ld, double *lambda_host, double *C_host);
 
 /* ------------------------------------------------------------------ products and PCG on blocks of vectors
  * Y[:, c] = A X[:, c] for c < k with the matrix streamed once per group of up to eight columns (psp_spmm.hip).  Blocks

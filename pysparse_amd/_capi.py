@@ -44,6 +44,7 @@ psp_minresstate_create psp_minresstate_destroy psp_minresstate_init psp_minresst
 psp_kd_minres_scale psp_kd_minres_matvec psp_kd_minres_lanczos psp_kd_minres_scalar psp_kd_minres_wx
 psp_bv_tdot psp_bv_gemv psp_bv_rotate psp_jdsym psp_op_apply_host psp_debug_ritz psp_debug_lu_factor psp_debug_lu_solve
 psp_csr_matmat psp_csr_matmat_dev psp_sss_matmat psp_sss_matmat_dev psp_op_apply_block_dev psp_pcg_batch psp_pcg_batch_dev
+psp_bv_gram psp_bv_resid psp_lobpcg psp_debug_gen_ritz
 """.split()
 
 
@@ -206,6 +207,10 @@ def _declare(L):
         "psp_op_apply_block_dev": [vp, i, vp, C.c_long, vp, C.c_long],
         "psp_pcg_batch": [vp, vp, i, i, vp, C.c_long, vp, C.c_long, d, i, pi, pi, pd],
         "psp_pcg_batch_dev": [vp, vp, i, i, vp, C.c_long, vp, C.c_long, d, i, pi, pi, pd],
+        "psp_bv_gram": [i, i, vp, i64, i, vp, i64, vp, i64],
+        "psp_bv_resid": [i, i, vp, i64, vp, i64, vp, vp, vp, i64, vp],
+        "psp_lobpcg": [vp, vp, vp, i, i, d, i, vp, i, C.c_long, vp, vp, C.c_long, vp, pi, pi],
+        "psp_debug_gen_ritz": [i, vp, vp, i, vp, vp],
     }
     for name, argtypes in sig.items():
         f = getattr(L, name)

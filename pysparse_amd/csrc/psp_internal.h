@@ -569,7 +569,20 @@ int correq_apply(const psp_op *op, const double *x_dev, double *y_dev);
 int bv_tdot(long n, int m, const double *V, long ld, const double *x, double *h_dev);
 int bv_gemv(long n, int m, const double *V, long ld, const double *h_dev, double alpha, double beta, double *y);
 int bv_rotate(long n, int j, double *V, long ld, const double *U_host, int ldu, int u0, int jn, int dst0);
+// bv_rotate again with the coefficients the calling thread's last bv_rotate uploaded (the images of a rotated block)
+int bv_rotate_again(long n, int j, double *V, long ld, int jn, int dst0);
+// G[a + b*ldg] = A[:, a] . B[:, b]: column b has the bits of bv_tdot(n, ma, A, lda, B + b*ldb) when both take the same
+// access form (16-byte: n, lda, ldb even and both bases aligned)
+int bv_gram(long n, int ma, const double *A, long lda, int mb, const double *B, long ldb, double *G_dev, long ldg);
+// R[:, slot[c]] = AX[:, c] - theta[c] MX[:, c] where slot[c] >= 0 (k <= 32), nrm2[c] = r . r with bv_tdot's bits
+int bv_resid(long n, int k, const double *AX, long ldax, const double *MX, long ldmx, const double *theta_dev,
+             const int *slot_host, double *R, long ldr, double *nrm2_dev);
 void bv_trim();  // psp_trim: the calling thread's partial-sum and U buffers
+// psp_jdsym.hip, shared with psp_lobpcg.hip: eigenpairs of the symmetric j x j matrix in the upper triangle of Mu by cyclic
+// Jacobi rotations (s in no particular order, U the vectors as columns; j <= 128 callers), and count uniform (0, 1)
+// values from the splitmix64 hash of (fixed seed, first + index) on the device
+void sym_jacobi_eig(int j, const double *Mu, int ldm, double *s, double *U, int ldu);
+int random_fill_dev(long count, unsigned long long first, double *out);
 // psp_solvers.hip: the six Krylov loops at their device-pointer level, no locking, no argument checks (psp_jdsym.hip calls
 // them on the correction equation with the handles already locked); which = PSP_LIN_*
 int krylov_dev(int which, const psp_op *A, const psp_op *K, int n, double *x_dev, const double *b_dev, double tol, int maxit,

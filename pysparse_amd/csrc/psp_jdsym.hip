@@ -310,6 +310,10 @@ int correq_right(const psp_correq *ce, double *r) {
 
 namespace psp {
 
+// for psp_lobpcg.hip: the cyclic-Jacobi routine and the device generator of the start vectors, as jdsym uses them
+void sym_jacobi_eig(int j, const double *Mu, int ldm, double *s, double *U, int ldu) { jacobi_eig(j, Mu, ldm, s, U, ldu); }
+int random_fill_dev(long count, unsigned long long first, double *out) { return random_fill(count, first, out); }
+
 int correq_apply(const psp_op *op, const double *x, double *y) {
   const psp_correq *ce = op->ce;
   if (!ce) return fail(PSP_EINVAL, "correction-equation operator without a system");
