@@ -426,6 +426,29 @@ int psp_mg_is_galerkin(const psp_mg_t *K, int *galerkin);
  * matrix-free handle. */
 int psp_mg_level_operator(psp_mg_t *K, int level, int *offsets_out, int *noff_inout, double *values_host);
 
+/* The general creation call: flags = 0 is psp_mg_create_csr / _sss, PSP_MG_GALERKIN the _galerkin pair (the four are
+ * calls of these), PSP_MG_SINGLE the single-precision cycle of either mode (precision='single'); any
+ * other bit is PSP_EINVAL.  The single-precision cycle is the mode's cycle evaluated in IEEE float32 on rounded data: the
+ * level operators (c_a, d, omega / d; the Galerkin chain and omega / diagonal) and the coarsest inverse are formed in
+ * double exactly as without the flag, then every stored number is rounded once to float; b is rounded as it is read,
+ * every sweep, restriction, prolongation and the tail run in float in the same summation orders, and the result is
+ * widened into y.  x and y stay double vectors: the handle is used like any other (psp_mg_precon*, psp_op_from_mg, the
+ * solvers), with the same level grids and launches, the same bits from call to call, from host and device entry
+ * points, from csr and sss handles and from column c of a block.  PSP_EINVAL naming the single-precision range when a
+ * level diagonal or omega / diagonal is not finite, not > 0 or below FLT_MIN after rounding; the same matrix is
+ * accepted without the flag.  A Galerkin handle releases each level's double arrays as soon as the next level is built:
+ * at rest it holds float arrays only. */
+#define PSP_MG_GALERKIN 1u
+#define PSP_MG_SINGLE 2u
+int psp_mg_create_csr_ex(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, unsigned flags, psp_mg_t **out);
+int psp_mg_create_sss_ex(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, unsigned flags, psp_mg_t **out);
+/* 64, or 32 for a handle created with PSP_MG_SINGLE */
+int psp_mg_precision(const psp_mg_t *K, int *bits);
+/* What the handle holds on the device at rest, the block cycle's vectors (psp_mg_block_info) excluded: the level
+ * operators with the coarsest inverse and the tail's table, and the level vectors.  Either pointer may be NULL.
+ * psp_mg_level_operator on a single-precision handle returns the stored floats widened to double. */
+int psp_mg_bytes(const psp_mg_t *K, long long *operator_bytes, long long *vector_bytes);
+
 /* --------------------------------------------------------- operator protocol */
 
 /* Host callback operator: the C image of SpMatrix_Matvec / SpMatrix_Precon

@@ -34,6 +34,7 @@ psp_ssor_create psp_ssor_destroy psp_ssor_info psp_ssor_run_info psp_ssor_brick_
 psp_mg_create_csr psp_mg_create_sss psp_mg_destroy psp_mg_precon psp_mg_precon_dev psp_mg_info psp_op_from_mg
 psp_mg_create_csr_galerkin psp_mg_create_sss_galerkin psp_mg_is_galerkin psp_mg_level_operator
 psp_mg_precon_block psp_mg_precon_block_dev psp_mg_block_reserve psp_mg_block_info
+psp_mg_create_csr_ex psp_mg_create_sss_ex psp_mg_precision psp_mg_bytes
 psp_op_from_csr psp_op_from_sss psp_op_from_jacobi psp_op_from_ssor psp_op_from_callback psp_op_destroy
 psp_pcg psp_pcg_dev psp_minres psp_minres_dev psp_cgs psp_bicgstab psp_qmrs psp_gmres
 psp_k_dot psp_k_residual psp_k_pupdate psp_k_csr_matvec_dot psp_k_xr_update psp_k_gather
@@ -163,6 +164,8 @@ def _declare(L):
         "psp_mg_precon": [vp, vp, vp], "psp_mg_precon_dev": [vp, vp, vp], "psp_mg_info": [vp, pi, pi, pi, pi],
         "psp_mg_precon_block": [vp, i, vp, C.c_long, vp, C.c_long], "psp_mg_precon_block_dev": [vp, i, vp, C.c_long, vp, C.c_long],
         "psp_mg_block_reserve": [vp, i], "psp_mg_block_info": [vp, pi, C.POINTER(C.c_longlong)],
+        "psp_mg_create_csr_ex": [vp, i, pi, d, i, C.c_uint, pvp], "psp_mg_create_sss_ex": [vp, i, pi, d, i, C.c_uint, pvp],
+        "psp_mg_precision": [vp, pi], "psp_mg_bytes": [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
         "psp_op_from_mg": [vp, pvp],
         "psp_op_from_csr": [vp, pvp], "psp_op_from_sss": [vp, pvp], "psp_op_from_jacobi": [vp, pvp],
         "psp_op_from_callback": [i, HOST_APPLY_FN, vp, pvp], "psp_op_destroy": [vp],

@@ -46,22 +46,26 @@ constexpr int kTailT = kTailThreads * kTailPts;    // largest level the tail tak
 constexpr int kTailMaxLev = 12;                    // 2048 -> 1024 -> ... -> 4 -> 2 in 1-D is 11 levels
 constexpr int kCoarsestMax = 27;                   // no axis >= 4: at most 3^3 points
 constexpr int kMaxLevels = 32;                     // n < 2^31 and every level at least halves
-// LDS of the tail (doubles): x and b of every level (level sizes at least halve: their sum stays below 2 kTailT), one
+// LDS of the tail (elements of the cycle's scalar type): x and b of every level (level sizes at least halve: their sum stays below 2 kTailT), one
 // level-sized scratch for the residual, the dense inverse
 constexpr int kTailLds = 5 * kTailT + kCoarsestMax * kCoarsestMax;
 // mg_restrict: 256 coarse points per workgroup; the fine residuals of the tile plus halo (2 t + 1 per coarsened axis)
 constexpr int kResThreads = 256;
 constexpr int kResLds = 33 * 9 * 9;  // the 3-D tile 16 x 4 x 4; 2-D 32 x 8 -> 65 x 17, 1-D 256 -> 513 are smaller
 
-struct MgLevelArg {
-  int n[3];     // dimensions (1 on the axes the grid does not have)
-  int co[3];    // 1: the axis is coarsened towards the next level
-  int nc[3];    // dimensions of the next level
-  double c[3];  // 0 on axes of length 1
-  double d;     // 2 sum c + s
-  double w;     // omega / d
-  double rs;    // 1 / 2^(coarsened axes)
+// S: the scalar type the cycle runs in -- double, or float for precision='single' (the level's
+// numbers are formed in double and rounded once)
+template <class S>
+struct MgLevelArgT {
+  int n[3];   // dimensions (1 on the axes the grid does not have)
+  int co[3];  // 1: the axis is coarsened towards the next level
+  int nc[3];  // dimensions of the next level
+  S c[3];     // 0 on axes of length 1
+  S d;        // 2 sum c + s
+  S w;        // omega / d
+  S rs;       // 1 / 2^(coarsened axes)
 };
+using MgLevelArg = MgLevelArgT<double>;
 
 template <class LevelT>  // what the mode keeps of a level: MgLevelArg, or psp_mg_galerkin.h's GLevel
 struct TailArg {
@@ -72,9 +76,9 @@ struct TailArg {
 };
 
 // (A_l x)[i]: the diagonal first, then axis by axis the lower and the upper neighbour -- one fixed order everywhere
-template <class X>
-__device__ __forceinline__ double mg_ax(const MgLevelArg &L, const X &x, long i, int i0, int i1, int i2) {
-  double acc = L.d * x(i);
+template <class S, class X>
+__device__ __forceinline__ S mg_ax(const MgLevelArgT<S> &L, const X &x, long i, int i0, int i1, int i2) {
+  S acc = L.d * x(i);
   if (L.n[0] > 1) {
     if (i0 > 0) acc -= L.c[0] * x(i - 1);
     if (i0 < L.n[0] - 1) acc -= L.c[0] * x(i + 1);
@@ -93,8 +97,8 @@ __device__ __forceinline__ double mg_ax(const MgLevelArg &L, const X &x, long i,
 }
 
 // ND: axes the level's index is split into
-template <int ND = 3>
-__device__ __forceinline__ void mg_split(const MgLevelArg &L, long i, int &i0, int &i1, int &i2) {
+template <int ND = 3, class S>
+__device__ __forceinline__ void mg_split(const MgLevelArgT<S> &L, long i, int &i0, int &i1, int &i2) {
   i0 = (int)i, i1 = 0, i2 = 0;
   if constexpr (ND == 2) {
     i0 = (int)(i % L.n[0]);
@@ -110,57 +114,64 @@ __device__ __forceinline__ void mg_split(const MgLevelArg &L, long i, int &i0, i
 // The level-operator policy of the matrix-free mode: the level is its MgLevelArg, held by value (a kernel argument, or
 // the tail's copy of its table entry in registers).  With ND < 3 the dead axes are set to length 1 so that their terms
 // of mg_ax compile away; MfOp<3> takes any level as it is (the restriction and the tail, whose shapes are run-time).
-template <int ND>
+template <int ND, class S>
 struct MfOp {
-  using Level = MgLevelArg;
-  MgLevelArg L;
-  __device__ __forceinline__ explicit MfOp(const MgLevelArg &a) : L(a) {
+  using Scalar = S;
+  static constexpr bool kFinest = true;  // the shape can be the finest level's (mg_with_io)
+  using Level = MgLevelArgT<S>;
+  Level L;
+  __device__ __forceinline__ explicit MfOp(const Level &a) : L(a) {
     if constexpr (ND < 3) L.n[2] = 1;
     if constexpr (ND < 2) L.n[1] = 1;
   }
-  __device__ __forceinline__ const MgLevelArg &geo() const { return L; }
+  __device__ __forceinline__ const Level &geo() const { return L; }
   template <class X>
-  __device__ __forceinline__ double ax(const X &x, long i, int i0, int i1, int i2) const {
+  __device__ __forceinline__ S ax(const X &x, long i, int i0, int i1, int i2) const {
     return mg_ax(L, x, i, i0, i1, i2);
   }
-  __device__ __forceinline__ double w(long) const { return L.w; }
+  __device__ __forceinline__ S w(long) const { return L.w; }
   __device__ __forceinline__ void split(long i, int &i0, int &i1, int &i2) const { mg_split<ND>(L, i, i0, i1, i2); }
   // the block kernels' pair (GOp in psp_mg_galerkin.h has the real one): this mode's row is kernel arguments, nothing is
   // loaded; x(j, w_j) is the column's value at j
   struct Row {
-    double w;
+    S w;
   };
   template <bool WN>
   __device__ __forceinline__ Row load_row(long, int, int, int) const {
     return Row{L.w};
   }
   template <class X>
-  __device__ __forceinline__ double ax_row(const Row &r, const X &x, long i, int i0, int i1, int i2) const {
+  __device__ __forceinline__ S ax_row(const Row &r, const X &x, long i, int i0, int i1, int i2) const {
     auto X1 = [&](long j) { return x(j, r.w); };
     return mg_ax(L, X1, i, i0, i1, i2);
   }
 };
 // omega / d as mg_scale_kernel takes it
+template <class S>
 struct MfW {
-  double w;
-  __device__ __forceinline__ double operator()(long) const { return w; }
+  using Scalar = S;
+  S w;
+  __device__ __forceinline__ S operator()(long) const { return w; }
 };
-__host__ __device__ inline const MgLevelArg &level_geo(const MgLevelArg &a) { return a; }
+template <class S>
+__host__ __device__ inline const MgLevelArgT<S> &level_geo(const MgLevelArgT<S> &a) {
+  return a;
+}
 
 // (R r)[j] for the coarse point (j0, j1, j2); r is indexed through `at(l0, l1, l2)` with fine coordinates, which returns 0
 // outside the grid.  Weights 1/2, 1, 1/2 along a coarsened axis at fine 2j, 2j+1, 2j+2; axis 2 outermost, ascending.
-template <class AT>
-__device__ __forceinline__ double mg_restrict_point(const MgLevelArg &L, const AT &at, int j0, int j1, int j2) {
+template <class S, class AT>
+__device__ __forceinline__ S mg_restrict_point(const MgLevelArgT<S> &L, const AT &at, int j0, int j1, int j2) {
   const int b0 = L.co[0] ? 2 * j0 : j0, m0 = L.co[0] ? 3 : 1;
   const int b1 = L.co[1] ? 2 * j1 : j1, m1 = L.co[1] ? 3 : 1;
   const int b2 = L.co[2] ? 2 * j2 : j2, m2 = L.co[2] ? 3 : 1;
-  double sum = 0.0;
+  S sum = 0;
   for (int k2 = 0; k2 < m2; ++k2) {
-    const double w2 = (L.co[2] && k2 != 1) ? 0.5 : 1.0;
+    const S w2 = (L.co[2] && k2 != 1) ? S(0.5) : S(1);
     for (int k1 = 0; k1 < m1; ++k1) {
-      const double w1 = (L.co[1] && k1 != 1) ? 0.5 * w2 : w2;
+      const S w1 = (L.co[1] && k1 != 1) ? S(0.5) * w2 : w2;
       for (int k0 = 0; k0 < m0; ++k0) {
-        const double w0 = (L.co[0] && k0 != 1) ? 0.5 * w1 : w1;
+        const S w0 = (L.co[0] && k0 != 1) ? S(0.5) * w1 : w1;
         sum += w0 * at(b0 + k0, b1 + k1, b2 + k2);
       }
     }
@@ -171,20 +182,22 @@ __device__ __forceinline__ double mg_restrict_point(const MgLevelArg &L, const A
 // (P e)[i] for the fine point (i0, i1, i2); e is the next level's vector.  Along a coarsened axis an odd index takes
 // coarse (i - 1) / 2 whole, an even one half of coarse i / 2 - 1 and half of i / 2 where they exist; lower before upper,
 // axis 2 outermost.
+template <class S>
 struct MgAxisSrc {
   int ja, jb, cnt;  // the coarse indices a fine index takes from (jb only when cnt == 2)
-  double wt;
+  S wt;
 };
-__device__ __forceinline__ MgAxisSrc mg_axis_src(int co, int g, int nc) {
-  MgAxisSrc s;
+template <class S>
+__device__ __forceinline__ MgAxisSrc<S> mg_axis_src(int co, int g, int nc) {
+  MgAxisSrc<S> s;
   s.jb = 0;
   if (!co) {
-    s.ja = g, s.cnt = 1, s.wt = 1.0;
+    s.ja = g, s.cnt = 1, s.wt = S(1);
   } else if (g & 1) {
-    s.ja = (g - 1) >> 1, s.cnt = 1, s.wt = 1.0;
+    s.ja = (g - 1) >> 1, s.cnt = 1, s.wt = S(1);
   } else {
     const int lo = (g >> 1) - 1, hi = g >> 1;  // at least one exists: nc >= 2 on a coarsened axis
-    s.wt = 0.5;
+    s.wt = S(0.5);
     if (lo >= 0 && hi < nc) {
       s.ja = lo, s.jb = hi, s.cnt = 2;
     } else {
@@ -193,12 +206,12 @@ __device__ __forceinline__ MgAxisSrc mg_axis_src(int co, int g, int nc) {
   }
   return s;
 }
-template <class E>
-__device__ __forceinline__ double mg_prolong_point(const MgLevelArg &L, const E &e, int i0, int i1, int i2) {
-  const MgAxisSrc a0 = mg_axis_src(L.co[0], i0, L.nc[0]), a1 = mg_axis_src(L.co[1], i1, L.nc[1]),
-                  a2 = mg_axis_src(L.co[2], i2, L.nc[2]);
-  const double w = a0.wt * a1.wt * a2.wt;  // powers of two: exact
-  double sum = 0.0;
+template <class S, class E>
+__device__ __forceinline__ S mg_prolong_point(const MgLevelArgT<S> &L, const E &e, int i0, int i1, int i2) {
+  const MgAxisSrc<S> a0 = mg_axis_src<S>(L.co[0], i0, L.nc[0]), a1 = mg_axis_src<S>(L.co[1], i1, L.nc[1]),
+                     a2 = mg_axis_src<S>(L.co[2], i2, L.nc[2]);
+  const S w = a0.wt * a1.wt * a2.wt;  // powers of two: exact
+  S sum = 0;
   for (int k2 = 0; k2 < a2.cnt; ++k2) {
     const long j2 = k2 ? a2.jb : a2.ja;
     for (int k1 = 0; k1 < a1.cnt; ++k1) {
@@ -214,40 +227,50 @@ __device__ __forceinline__ double mg_prolong_point(const MgLevelArg &L, const E 
 
 // ------------------------------------------------------------------ the launch-per-step kernels of the large levels
 
+// Element types.  S = the policy's Scalar is what every level vector holds and every operation is done in.  The finest
+// level alone also touches the caller's vectors, which are double whatever S is: TB (of b) and TO (of the vector a sweep
+// writes) are deduced from the pointers; an element is converted to S as it is loaded, a result to TO as it is stored.
+// With S = double all three are double and the conversions are none.
+
 // the first sweep from x = 0: x = 0 + (omega / d)(b - 0) = (omega / d) b; W: MfW (a scalar) or GW (an array)
-template <class W>
-__global__ __launch_bounds__(256) void mg_scale_kernel(long N, W w, const double *__restrict__ b, double *__restrict__ x) {
+template <class W, class TB>
+__global__ __launch_bounds__(256) void mg_scale_kernel(long N, W w, const TB *__restrict__ b,
+                                                       typename W::Scalar *__restrict__ x) {
+  using S = typename W::Scalar;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < N) x[i] = w(i) * b[i];
+  if (i < N) x[i] = w(i) * (S)b[i];
 }
 
 // one sweep, out of place: xout = xin + (omega / d)(b - A xin); reads xin and b (and, with a stored stencil, w and every
 // coefficient array) once, writes xout once; the neighbours (of xin, and the neighbours' rows of the lower arrays: the
 // upper couplings) come from the caches.  FROMB: xin is the first sweep's (omega / d) b, formed on the fly -- sweeps one
 // and two of a cycle in one pass.
-template <class Op, bool FROMB>
-__global__ __launch_bounds__(256) void mg_smooth_kernel(typename Op::Level A, long N, const double *__restrict__ xin,
-                                                        const double *__restrict__ b, double *__restrict__ xout) {
+template <class Op, bool FROMB, class TB, class TO>
+__global__ __launch_bounds__(256) void mg_smooth_kernel(typename Op::Level A, long N,
+                                                        const typename Op::Scalar *__restrict__ xin,
+                                                        const TB *__restrict__ b, TO *__restrict__ xout) {
+  using S = typename Op::Scalar;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   const Op op(A);
   int i0, i1, i2;
   op.split(i, i0, i1, i2);
-  auto X = [&](long k) { return FROMB ? op.w(k) * b[k] : xin[k]; };
-  const double ax = op.ax(X, i, i0, i1, i2);
-  xout[i] = X(i) + op.w(i) * (b[i] - ax);
+  auto X = [&](long k) -> S { return FROMB ? op.w(k) * (S)b[k] : xin[k]; };
+  const S ax = op.ax(X, i, i0, i1, i2);
+  xout[i] = (TO)(X(i) + op.w(i) * ((S)b[i] - ax));
 }
 
 // b_c = R (b - A x): blockIdx.x = the tile of coarse points (t[0] x t[1] x t[2] = 256 of them), `r` = the fine residuals
 // the tile's restriction reads; a fine point outside the grid counts as 0.  The fine residual never reaches memory.
-template <class Op>
+template <class Op, class TB>
 __global__ __launch_bounds__(kResThreads) void mg_restrict_kernel(typename Op::Level A, int t0, int t1, int t2, int g0n,
-                                                                  int g1n, const double *__restrict__ x,
-                                                                  const double *__restrict__ b,
-                                                                  double *__restrict__ bc) {
-  __shared__ double r[kResLds];
+                                                                  int g1n, const typename Op::Scalar *__restrict__ x,
+                                                                  const TB *__restrict__ b,
+                                                                  typename Op::Scalar *__restrict__ bc) {
+  using S = typename Op::Scalar;
+  __shared__ S r[kResLds];
   const Op op(A);
-  const MgLevelArg &L = op.geo();
+  const MgLevelArgT<S> &L = op.geo();
   // the tile's three indices ride in blockIdx.x (g0n x g1n x g2n tiles, axis 0 fastest): a long second or third axis
   // would not fit gridDim.y / gridDim.z
   const unsigned bq = blockIdx.x / (unsigned)g0n;
@@ -260,10 +283,10 @@ __global__ __launch_bounds__(kResThreads) void mg_restrict_kernel(typename Op::L
   for (int t = threadIdx.x; t < total; t += kResThreads) {
     const int l0 = t % F0, q = t / F0, l1 = q % F1, l2 = q / F1;
     const int g0 = f0 + l0, g1 = f1 + l1, g2 = f2 + l2;
-    double v = 0.0;
+    S v = 0;
     if (g0 < L.n[0] && g1 < L.n[1] && g2 < L.n[2]) {
       const long i = g0 + (long)L.n[0] * (g1 + (long)L.n[1] * g2);
-      v = b[i] - op.ax(X, i, g0, g1, g2);
+      v = (S)b[i] - op.ax(X, i, g0, g1, g2);
     }
     r[t] = v;
   }
@@ -274,15 +297,16 @@ __global__ __launch_bounds__(kResThreads) void mg_restrict_kernel(typename Op::L
     if (J0 + j0 < L.nc[0] && J1 + j1 < L.nc[1] && J2 + j2 < L.nc[2]) {
       // the tile's fine region starts at the fine image of its first coarse point: local fine coordinates
       auto at = [&](int a0, int a1, int a2) { return r[a0 + F0 * (a1 + F1 * a2)]; };
-      const double v = mg_restrict_point(L, at, j0, j1, j2);
+      const S v = mg_restrict_point(L, at, j0, j1, j2);
       bc[(J0 + j0) + (long)L.nc[0] * ((J1 + j1) + (long)L.nc[1] * (J2 + j2))] = v;
     }
   }
 }
 
 // x += P e: reads x and e, writes x
-__global__ __launch_bounds__(256) void mg_prolong_kernel(MgLevelArg L, long N, const double *__restrict__ e,
-                                                         double *__restrict__ x) {
+template <class S>
+__global__ __launch_bounds__(256) void mg_prolong_kernel(MgLevelArgT<S> L, long N, const S *__restrict__ e,
+                                                         S *__restrict__ x) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   int i0, i1, i2;
@@ -308,26 +332,28 @@ __device__ __forceinline__ unsigned mg_live(int c0, int k, const int *__restrict
   return m;
 }
 
-template <class W, int KC>
-__global__ __launch_bounds__(256) void mg_scale_block_kernel(long N, W w, int k, const double *__restrict__ b, long ldb,
-                                                             double *__restrict__ x, long ldx,
+template <class W, int KC, class TB>
+__global__ __launch_bounds__(256) void mg_scale_block_kernel(long N, W w, int k, const TB *__restrict__ b, long ldb,
+                                                             typename W::Scalar *__restrict__ x, long ldx,
                                                              const int *__restrict__ frozen) {
+  using S = typename W::Scalar;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   const int c0 = blockIdx.y * KC;
   const unsigned live = mg_live<KC>(c0, k, frozen);
   if (i >= N || !live) return;
-  const double wi = w(i);
+  const S wi = w(i);
 #pragma unroll
   for (int c = 0; c < KC; ++c)
-    if ((live >> c) & 1u) x[(size_t)(c0 + c) * ldx + i] = wi * b[(size_t)(c0 + c) * ldb + i];
+    if ((live >> c) & 1u) x[(size_t)(c0 + c) * ldx + i] = wi * (S)b[(size_t)(c0 + c) * ldb + i];
 }
 
-template <class Op, bool FROMB, int KC>
+template <class Op, bool FROMB, int KC, class TB, class TO>
 __global__ __launch_bounds__(256) void mg_smooth_block_kernel(typename Op::Level A, long N, int k,
-                                                              const double *__restrict__ xin, long ldi,
-                                                              const double *__restrict__ b, long ldb,
-                                                              double *__restrict__ xout, long ldo,
+                                                              const typename Op::Scalar *__restrict__ xin, long ldi,
+                                                              const TB *__restrict__ b, long ldb,
+                                                              TO *__restrict__ xout, long ldo,
                                                               const int *__restrict__ frozen) {
+  using S = typename Op::Scalar;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   const int c0 = blockIdx.y * KC;
   const unsigned live = mg_live<KC>(c0, k, frozen);
@@ -339,30 +365,36 @@ __global__ __launch_bounds__(256) void mg_smooth_block_kernel(typename Op::Level
 #pragma unroll
   for (int c = 0; c < KC; ++c) {
     if (!((live >> c) & 1u)) continue;
-    const double *__restrict__ bc = b + (size_t)(c0 + c) * ldb;
-    const double *__restrict__ xc = FROMB ? bc : xin + (size_t)(c0 + c) * ldi;
-    auto X = [&](long j, double wj) { return FROMB ? wj * bc[j] : xc[j]; };
-    const double ax = op.ax_row(row, X, i, i0, i1, i2);
-    xout[(size_t)(c0 + c) * ldo + i] = X(i, row.w) + row.w * (bc[i] - ax);
+    const TB *__restrict__ bc = b + (size_t)(c0 + c) * ldb;
+    const S *__restrict__ xc = FROMB ? nullptr : xin + (size_t)(c0 + c) * ldi;
+    auto X = [&](long j, S wj) -> S {
+      if constexpr (FROMB)
+        return wj * (S)bc[j];
+      else
+        return xc[j];
+    };
+    const S ax = op.ax_row(row, X, i, i0, i1, i2);
+    xout[(size_t)(c0 + c) * ldo + i] = (TO)(X(i, row.w) + row.w * ((S)bc[i] - ax));
   }
 }
 
 // b_c = R (b - A x) for KC columns: points outer, columns inner -- a fine point's row is loaded once and applied to every
 // column of the group, whose residual tiles lie side by side in LDS.  KC = 1 with the columns in gridDim.y is the other
 // form (one tile, reused by nobody: every column is a workgroup of its own).
-template <class Op, int KC>
+template <class Op, int KC, class TB>
 __global__ __launch_bounds__(kResThreads) void mg_restrict_block_kernel(typename Op::Level A, int t0, int t1, int t2,
                                                                         int g0n, int g1n, int k,
-                                                                        const double *__restrict__ x, long ldx,
-                                                                        const double *__restrict__ b, long ldb,
-                                                                        double *__restrict__ bc, long ldc,
+                                                                        const typename Op::Scalar *__restrict__ x, long ldx,
+                                                                        const TB *__restrict__ b, long ldb,
+                                                                        typename Op::Scalar *__restrict__ bc, long ldc,
                                                                         const int *__restrict__ frozen) {
-  __shared__ double r[KC][kResLds];
+  using S = typename Op::Scalar;
+  __shared__ S r[KC][kResLds];
   const int c0 = blockIdx.y * KC;
   const unsigned live = mg_live<KC>(c0, k, frozen);
   if (!live) return;  // uniform: before any barrier
   const Op op(A);
-  const MgLevelArg &L = op.geo();
+  const MgLevelArgT<S> &L = op.geo();
   const unsigned bq = blockIdx.x / (unsigned)g0n;
   const int J0 = (int)(blockIdx.x % (unsigned)g0n) * t0, J1 = (int)(bq % (unsigned)g1n) * t1, J2 = (int)(bq / (unsigned)g1n) * t2;
   const int f0 = L.co[0] ? 2 * J0 : J0, F0 = L.co[0] ? 2 * t0 + 1 : t0;
@@ -378,13 +410,13 @@ __global__ __launch_bounds__(kResThreads) void mg_restrict_block_kernel(typename
 #pragma unroll
       for (int c = 0; c < KC; ++c) {
         if (!((live >> c) & 1u)) continue;
-        const double *__restrict__ xc = x + (size_t)(c0 + c) * ldx;
-        auto X = [&](long j, double) { return xc[j]; };
-        r[c][t] = b[(size_t)(c0 + c) * ldb + i] - op.ax_row(row, X, i, g0, g1, g2);
+        const S *__restrict__ xc = x + (size_t)(c0 + c) * ldx;
+        auto X = [&](long j, S) { return xc[j]; };
+        r[c][t] = (S)b[(size_t)(c0 + c) * ldb + i] - op.ax_row(row, X, i, g0, g1, g2);
       }
     } else {
 #pragma unroll
-      for (int c = 0; c < KC; ++c) r[c][t] = 0.0;
+      for (int c = 0; c < KC; ++c) r[c][t] = 0;
     }
   }
   __syncthreads();
@@ -396,7 +428,7 @@ __global__ __launch_bounds__(kResThreads) void mg_restrict_block_kernel(typename
 #pragma unroll
       for (int c = 0; c < KC; ++c) {
         if (!((live >> c) & 1u)) continue;
-        const double *rc = r[c];
+        const S *rc = r[c];
         auto at = [&](int a0, int a1, int a2) { return rc[a0 + F0 * (a1 + F1 * a2)]; };
         bc[(size_t)(c0 + c) * ldc + jc] = mg_restrict_point(L, at, j0, j1, j2);
       }
@@ -405,9 +437,9 @@ __global__ __launch_bounds__(kResThreads) void mg_restrict_block_kernel(typename
 }
 
 // x += P e: one index split per point, then the columns
-template <int KC>
-__global__ __launch_bounds__(256) void mg_prolong_block_kernel(MgLevelArg L, long N, int k, const double *__restrict__ e,
-                                                               long lde, double *__restrict__ x, long ldx,
+template <int KC, class S>
+__global__ __launch_bounds__(256) void mg_prolong_block_kernel(MgLevelArgT<S> L, long N, int k, const S *__restrict__ e,
+                                                               long lde, S *__restrict__ x, long ldx,
                                                                const int *__restrict__ frozen) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   const int c0 = blockIdx.y * KC;
@@ -418,8 +450,8 @@ __global__ __launch_bounds__(256) void mg_prolong_block_kernel(MgLevelArg L, lon
 #pragma unroll
   for (int c = 0; c < KC; ++c) {
     if (!((live >> c) & 1u)) continue;
-    const double *__restrict__ ec = e + (size_t)(c0 + c) * lde;
-    double *__restrict__ xc = x + (size_t)(c0 + c) * ldx;
+    const S *__restrict__ ec = e + (size_t)(c0 + c) * lde;
+    S *__restrict__ xc = x + (size_t)(c0 + c) * ldx;
     auto E = [&](long j) { return ec[j]; };
     xc[i] = xc[i] + mg_prolong_point(L, E, i0, i1, i2);
   }
@@ -429,13 +461,14 @@ __global__ __launch_bounds__(256) void mg_prolong_block_kernel(MgLevelArg L, lon
 
 // one sweep of a level in LDS: every thread forms its points' new values, then all are written
 template <class Op>
-__device__ __forceinline__ void tail_sweep(const Op &op, int N, double *xs, const double *bs) {
+__device__ __forceinline__ void tail_sweep(const Op &op, int N, typename Op::Scalar *xs, const typename Op::Scalar *bs) {
+  using S = typename Op::Scalar;
   auto X = [&](long k) { return xs[k]; };
-  double xn[kTailPts];
+  S xn[kTailPts];
 #pragma unroll
   for (int p = 0; p < kTailPts; ++p) {
     const int i = threadIdx.x + p * kTailThreads;
-    xn[p] = 0.0;
+    xn[p] = 0;
     if (i < N) {
       int i0, i1, i2;
       op.split(i, i0, i1, i2);
@@ -452,21 +485,24 @@ __device__ __forceinline__ void tail_sweep(const Op &op, int N, double *xs, cons
 }
 
 // Op: MfOp<3> (each level's MgLevelArg copied into registers) or GTailOp (the level's GLevel stays in global memory, and
-// so do its coefficient arrays: 14 kTailT doubles for the top tail level alone do not fit LDS)
-template <class Op>
+// so do its coefficient arrays: 14 kTailT doubles for the top tail level alone do not fit LDS).  TB / TX: the elements of
+// the tail's input and output -- the caller's doubles when the whole grid is the tail, else the level's S.
+template <class Op, class TB, class TX>
 __device__ __forceinline__ void mg_tail_body(const TailArg<typename Op::Level> *__restrict__ T,
-                                             const double *__restrict__ minv, const double *__restrict__ bin,
-                                             double *__restrict__ xout) {
-  __shared__ double sh[kTailLds];
-  double *const scr = sh + 4 * kTailT;
-  double *const mi = sh + 5 * kTailT;
+                                             const typename Op::Scalar *__restrict__ minv, const TB *__restrict__ bin,
+                                             TX *__restrict__ xout) {
+  using S = typename Op::Scalar;
+  using Geo = MgLevelArgT<S>;
+  __shared__ S sh[kTailLds];
+  S *const scr = sh + 4 * kTailT;
+  S *const mi = sh + 5 * kTailT;
   const int nl = T->nlev, steps = T->steps, tid = threadIdx.x;
   {
-    const MgLevelArg &L = level_geo(T->lev[0]);
+    const Geo &L = level_geo(T->lev[0]);
     const int N = L.n[0] * L.n[1] * L.n[2];
-    double *bs = sh + 2 * kTailT + T->off[0];
-    for (int i = tid; i < N; i += kTailThreads) bs[i] = bin[i];
-    const MgLevelArg &C = level_geo(T->lev[nl - 1]);
+    S *bs = sh + 2 * kTailT + T->off[0];
+    for (int i = tid; i < N; i += kTailThreads) bs[i] = (S)bin[i];
+    const Geo &C = level_geo(T->lev[nl - 1]);
     const int nc = C.n[0] * C.n[1] * C.n[2];
     for (int i = tid; i < nc * nc; i += kTailThreads) mi[i] = minv[i];
   }
@@ -474,9 +510,9 @@ __device__ __forceinline__ void mg_tail_body(const TailArg<typename Op::Level> *
   // down
   for (int l = 0; l < nl - 1; ++l) {
     const Op op(T->lev[l]);
-    const MgLevelArg &L = op.geo();
+    const Geo &L = op.geo();
     const int N = L.n[0] * L.n[1] * L.n[2], Nc = L.nc[0] * L.nc[1] * L.nc[2];
-    double *xs = sh + T->off[l], *bs = sh + 2 * kTailT + T->off[l], *bn = sh + 2 * kTailT + T->off[l + 1];
+    S *xs = sh + T->off[l], *bs = sh + 2 * kTailT + T->off[l], *bn = sh + 2 * kTailT + T->off[l + 1];
     for (int i = tid; i < N; i += kTailThreads) xs[i] = op.w(i) * bs[i];
     __syncthreads();
     for (int k = 1; k < steps; ++k) tail_sweep(op, N, xs, bs);
@@ -488,7 +524,7 @@ __device__ __forceinline__ void mg_tail_body(const TailArg<typename Op::Level> *
     }
     __syncthreads();
     auto at = [&](int a0, int a1, int a2) {
-      return (a0 < L.n[0] && a1 < L.n[1] && a2 < L.n[2]) ? scr[a0 + L.n[0] * (a1 + L.n[1] * a2)] : 0.0;
+      return (a0 < L.n[0] && a1 < L.n[1] && a2 < L.n[2]) ? scr[a0 + L.n[0] * (a1 + L.n[1] * a2)] : S(0);
     };
     for (int j = tid; j < Nc; j += kTailThreads) {
       const int j0 = j % L.nc[0], q = j / L.nc[0], j1 = q % L.nc[1], j2 = q / L.nc[1];
@@ -498,12 +534,12 @@ __device__ __forceinline__ void mg_tail_body(const TailArg<typename Op::Level> *
   }
   // the coarsest level: x = A^-1 b with the inverse formed at creation
   {
-    const MgLevelArg &C = level_geo(T->lev[nl - 1]);
+    const Geo &C = level_geo(T->lev[nl - 1]);
     const int nc = C.n[0] * C.n[1] * C.n[2];
-    double *xs = sh + T->off[nl - 1];
-    const double *bs = sh + 2 * kTailT + T->off[nl - 1];
+    S *xs = sh + T->off[nl - 1];
+    const S *bs = sh + 2 * kTailT + T->off[nl - 1];
     if (tid < nc) {
-      double s = 0.0;
+      S s = 0;
       for (int j = 0; j < nc; ++j) s += mi[tid * nc + j] * bs[j];
       xs[tid] = s;
     }
@@ -512,10 +548,10 @@ __device__ __forceinline__ void mg_tail_body(const TailArg<typename Op::Level> *
   // up
   for (int l = nl - 2; l >= 0; --l) {
     const Op op(T->lev[l]);
-    const MgLevelArg &L = op.geo();
+    const Geo &L = op.geo();
     const int N = L.n[0] * L.n[1] * L.n[2];
-    double *xs = sh + T->off[l];
-    const double *bs = sh + 2 * kTailT + T->off[l], *en = sh + T->off[l + 1];
+    S *xs = sh + T->off[l];
+    const S *bs = sh + 2 * kTailT + T->off[l], *en = sh + T->off[l + 1];
     auto E = [&](long k) { return en[k]; };
     for (int i = tid; i < N; i += kTailThreads) {
       int i0, i1, i2;
@@ -526,27 +562,26 @@ __device__ __forceinline__ void mg_tail_body(const TailArg<typename Op::Level> *
     for (int k = 0; k < steps; ++k) tail_sweep(op, N, xs, bs);
   }
   {
-    const MgLevelArg &L = level_geo(T->lev[0]);
+    const Geo &L = level_geo(T->lev[0]);
     const int N = L.n[0] * L.n[1] * L.n[2];
-    const double *xs = sh + T->off[0];
-    for (int i = tid; i < N; i += kTailThreads) xout[i] = xs[i];
+    const S *xs = sh + T->off[0];
+    for (int i = tid; i < N; i += kTailThreads) xout[i] = (TX)xs[i];
   }
 }
 
-template <class Op>
+template <class Op, class TB, class TX>
 __global__ __launch_bounds__(kTailThreads) void mg_tail_kernel(const TailArg<typename Op::Level> *__restrict__ T,
-                                                               const double *__restrict__ minv,
-                                                               const double *__restrict__ bin,
-                                                               double *__restrict__ xout) {
+                                                               const typename Op::Scalar *__restrict__ minv,
+                                                               const TB *__restrict__ bin, TX *__restrict__ xout) {
   mg_tail_body<Op>(T, minv, bin, xout);
 }
 
 // the block form: workgroup c runs the tail on column c's pointers; a frozen column's workgroup returns at once
-template <class Op>
+template <class Op, class TB, class TX>
 __global__ __launch_bounds__(kTailThreads) void mg_tail_block_kernel(const TailArg<typename Op::Level> *__restrict__ T,
-                                                                     const double *__restrict__ minv,
-                                                                     const double *__restrict__ bin, long ldb,
-                                                                     double *__restrict__ xout, long ldx,
+                                                                     const typename Op::Scalar *__restrict__ minv,
+                                                                     const TB *__restrict__ bin, long ldb,
+                                                                     TX *__restrict__ xout, long ldx,
                                                                      const int *__restrict__ frozen) {
   const int c = blockIdx.x;
   if (frozen && frozen[c]) return;
@@ -633,25 +668,35 @@ __global__ __launch_bounds__(256) void mg_check_w4_kernel(int n, MgStencil S, Mg
 struct psp_mg {
   int n = 0, ndim = 0, steps = 2;
   double omega = 0.8;
+  // precision='single' (section 9g): every vector and array below holds floats, `af` and `glev32` are what the kernels
+  // take; `a` (and the geometry in `glev`) stays as formed in double
+  bool single = false;
   struct Level {
     MgLevelArg a;
+    MgLevelArgT<float> af;
     long N = 0;
-    double *x = nullptr, *b = nullptr, *t = nullptr;  // the level's vectors (levels in the tail have none)
+    // the level's vectors (levels in the tail have none): doubles, or floats on a single-precision handle, which also
+    // owns the finest level's x (a double handle works in the caller's y there)
+    void *x = nullptr, *b = nullptr, *t = nullptr;
   };
   std::vector<Level> lev;
   int tail_first = 0;  // first level of the tail launch
   int launches = 0;    // kernel launches of one application
-  double *minv = nullptr;
+  void *minv = nullptr;  // the coarsest level's inverse, in the handle's scalar type
   void *tail = nullptr;  // the mode's TailArg on the device
   // galerkin = True (psp_mg_galerkin.h): the stored level operators; `coef` owns each level's arrays in one allocation
-  // (diagonal, omega / diagonal, the lower arrays)
+  // (diagonal, omega / diagonal, the lower arrays).  A single-precision handle keeps the rounded arrays in `coef32`; its
+  // `coef[l]` lives only until level l + 1 is built and level l is rounded.
   bool galerkin = false;
   std::vector<GLevel> glev;
+  std::vector<GLevelT<float>> glev32;
   std::vector<double *> coef;
+  std::vector<float *> coef32;
+  size_t op_bytes = 0, vec_bytes = 0;  // what the handle holds at rest (psp_mg_bytes)
   // the level vectors of the block cycle (section 9e): per level what `lev` holds, for blk_cols columns of leading
   // dimension N, and a spare for the finest level; allocated by the first block call, grown on demand
   struct BlockLevel {
-    double *x = nullptr, *b = nullptr, *t = nullptr;
+    void *x = nullptr, *b = nullptr, *t = nullptr;
   };
   std::vector<BlockLevel> blk;
   int blk_cols = 0;
@@ -660,10 +705,44 @@ struct psp_mg {
 
 namespace {
 
-int level_nd(const MgLevelArg &a) { return a.n[2] > 1 ? 3 : a.n[1] > 1 ? 2 : 1; }
+// what the kernels of scalar type S take of level l
+template <class S>
+const MgLevelArgT<S> &mf_level(const psp_mg *K, int l) {
+  if constexpr (std::is_same_v<S, double>)
+    return K->lev[l].a;
+  else
+    return K->lev[l].af;
+}
+template <class S>
+const GLevelT<S> &g_level(const psp_mg *K, int l) {
+  if constexpr (std::is_same_v<S, double>)
+    return K->glev[l];
+  else
+    return K->glev32[l];
+}
+
+// the level's numbers rounded once to float (section 9g); rs is a power of two
+MgLevelArgT<float> mg_round_level(const MgLevelArg &a) {
+  MgLevelArgT<float> f;
+  for (int x = 0; x < 3; ++x) f.n[x] = a.n[x], f.co[x] = a.co[x], f.nc[x] = a.nc[x], f.c[x] = (float)a.c[x];
+  f.d = (float)a.d;
+  f.w = (float)a.w;
+  f.rs = (float)a.rs;
+  return f;
+}
+
+const char *const kSingleRange =
+    "multigrid(precision='single'): a level diagonal or omega / diagonal is outside the single-precision range (not finite, "
+    "not > 0 or below FLT_MIN after rounding to float32); precision='double' takes this operator";
+
+template <class S>
+int level_nd(const MgLevelArgT<S> &a) {
+  return a.n[2] > 1 ? 3 : a.n[1] > 1 ? 2 : 1;
+}
 
 // coarse points per workgroup of mg_restrict along each axis (256 in all): by the axes the level really has
-void mg_tile(const MgLevelArg &a, int t[3]) {
+template <class S>
+void mg_tile(const MgLevelArgT<S> &a, int t[3]) {
   const int nd = level_nd(a);
   if (nd == 1) {
     t[0] = 256, t[1] = 1, t[2] = 1;
@@ -860,6 +939,7 @@ int mg_level_grids(psp_mg *K, const int n[3], int steps) {
   for (;;) {
     psp_mg::Level L;
     memset(&L.a, 0, sizeof L.a);
+    memset(&L.af, 0, sizeof L.af);
     int coarsened = 0;
     for (int a = 0; a < 3; ++a) {
       L.a.n[a] = cur[a];
@@ -886,19 +966,23 @@ int mg_level_grids(psp_mg *K, const int n[3], int steps) {
 }
 
 // level vectors: the finest level works in the caller's vectors and one spare; a level that heads the tail needs its
-// b and x in memory (the restriction above it writes b, the prolongation reads x); the levels inside the tail have none
+// b and x in memory (the restriction above it writes b, the prolongation reads x); the levels inside the tail have none.
+// A single-precision handle holds floats, and an x of its own for the finest level too when that level is not the tail:
+// the caller's y is double and takes only the last sweep (mg_schedule).
 int mg_alloc_vectors(psp_mg *K) {
   for (int l = 0; l <= K->tail_first; ++l) {
     psp_mg::Level &L = K->lev[l];
-    const size_t bytes = sizeof(double) * (size_t)L.N;
+    const size_t bytes = (K->single ? sizeof(float) : sizeof(double)) * (size_t)L.N;
+    const bool own_x = l > 0 || (K->single && K->tail_first > 0);
     hipError_t e = hipSuccess;
-    if (l < K->tail_first) e = hipMalloc((void **)&L.t, bytes);
-    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&L.x, bytes);
-    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&L.b, bytes);
+    if (l < K->tail_first) e = hipMalloc(&L.t, bytes);
+    if (own_x && e == hipSuccess) e = hipMalloc(&L.x, bytes);
+    if (l > 0 && e == hipSuccess) e = hipMalloc(&L.b, bytes);
     if (e != hipSuccess) {
       (void)hipGetLastError();
       return fail(PSP_ENOMEM, "multigrid: level vector allocation failed");
     }
+    K->vec_bytes += bytes * ((L.t != nullptr) + (L.x != nullptr) + (L.b != nullptr));
   }
   return PSP_OK;
 }
@@ -918,20 +1002,26 @@ int mg_upload_tail(psp_mg *K, const std::vector<double> &inv, LevelOf &&level) {
     off += (int)K->lev[l].N;
   }
   if (off > 2 * kTailT) return fail(PSP_EINVAL, "multigrid: the tail does not fit");
-  if (hipMalloc((void **)&K->minv, sizeof(double) * inv.size()) != hipSuccess ||
-      hipMalloc(&K->tail, sizeof T) != hipSuccess ||
-      hipMemcpy(K->minv, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess ||
+  // the inverse was formed in double; a single-precision handle keeps it rounded to float
+  const std::vector<float> inv32(K->single ? inv.begin() : inv.end(), inv.end());
+  const void *src = K->single ? (const void *)inv32.data() : (const void *)inv.data();
+  const size_t bytes = (K->single ? sizeof(float) : sizeof(double)) * inv.size();
+  if (hipMalloc(&K->minv, bytes) != hipSuccess || hipMalloc(&K->tail, sizeof T) != hipSuccess ||
+      hipMemcpy(K->minv, src, bytes, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(K->tail, &T, sizeof T, hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipGetLastError();
     return fail(PSP_ENOMEM, "multigrid: tail table allocation failed");
   }
+  K->op_bytes += bytes + sizeof T;
   return PSP_OK;
 }
 
 // the handle of either mode: build(K) is everything that can fail once it exists (it is destroyed then)
 template <class Build>
-int mg_make(const psp_csr *A, int ndim, double omega, int steps, bool galerkin, psp_mg **out, Build &&build) {
+int mg_make(const psp_csr *A, int ndim, double omega, int steps, bool galerkin, bool single, psp_mg **out,
+            Build &&build) {
   psp_mg *K = new psp_mg();
+  K->single = single;
   K->n = A->nrows;
   K->ndim = ndim;
   K->omega = omega;
@@ -946,7 +1036,7 @@ int mg_make(const psp_csr *A, int ndim, double omega, int steps, bool galerkin, 
   return PSP_OK;
 }
 
-int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, psp_mg **out) {
+int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, psp_mg **out) {
   int n[3];
   PSP_TRY(mg_check_args(A, ndim, grid, omega, steps, out, n));
   PSP_TRY(ensure_device());
@@ -962,7 +1052,7 @@ int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, ps
     return fail(PSP_EINVAL, "multigrid: the shift s = diagonal - 2 sum c = %g is negative", s);
   if (s < 0.0) s = 0.0;
 
-  return mg_make(A, ndim, omega, steps, false, out, [&](psp_mg *K) {
+  return mg_make(A, ndim, omega, steps, false, single, out, [&](psp_mg *K) {
     // the levels: c_a / 4 on the axes coarsened above, d = 2 sum c + s
     PSP_TRY(mg_level_grids(K, n, steps));
     double c[3] = {S.c[0], S.c[1], S.c[2]};
@@ -976,10 +1066,16 @@ int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, ps
       L.a.w = omega / L.a.d;
       for (int a = 0; a < 3; ++a)
         if (L.a.co[a]) c[a] /= 4.0;
+      if (single) {
+        L.af = mg_round_level(L.a);
+        if (!(L.af.d >= FLT_MIN && L.af.d <= FLT_MAX) || !(L.af.w >= FLT_MIN && L.af.w <= FLT_MAX))
+          return fail(PSP_EINVAL, "%s", kSingleRange);
+      }
     }
     PSP_TRY(mg_alloc_vectors(K));
     std::vector<double> inv;
     PSP_TRY(coarsest_inverse(K->lev.back().a, &inv));
+    if (single) return mg_upload_tail(K, inv, [&](int l) { return K->lev[l].af; });
     return mg_upload_tail(K, inv, [&](int l) { return K->lev[l].a; });
   });
 }
@@ -1002,8 +1098,8 @@ GOut g_out(const GLevel &G) {
   return o;
 }
 
-int g_bad_shape(const GLevel &G) {
-  return fail(PSP_EINVAL, "multigrid: internal error (a level of %d axes with %d lower arrays)", G.nd, G.noff);
+int g_bad_shape(int nd, int noff) {
+  return fail(PSP_EINVAL, "multigrid: internal error (a level of %d axes with %d lower arrays)", nd, noff);
 }
 
 // f(GShape<ND, NOFF>{}) for the level's shape: the one place that turns (nd, noff) into template arguments
@@ -1011,15 +1107,15 @@ template <int ND, int NOFF>
 struct GShape {
   static constexpr int nd = ND, noff = NOFF;
 };
-template <class F>
-int g_dispatch(const GLevel &G, F &&f) {
+template <class S, class F>
+int g_dispatch(const GLevelT<S> &G, F &&f) {
   switch (G.nd * 16 + G.noff) {
     case 1 * 16 + 1: f(GShape<1, 1>{}); break;
     case 2 * 16 + 2: f(GShape<2, 2>{}); break;
     case 2 * 16 + 4: f(GShape<2, 4>{}); break;
     case 3 * 16 + 3: f(GShape<3, 3>{}); break;
     case 3 * 16 + 13: f(GShape<3, 13>{}); break;
-    default: return g_bad_shape(G);
+    default: return g_bad_shape(G.nd, G.noff);
   }
   return PSP_OK;
 }
@@ -1050,36 +1146,81 @@ void g_dense(const GLevel &G, const std::vector<double> &blk, std::vector<double
   }
 }
 
-// mg_create_galerkin's part of mg_make
+// the arrays of level l in one allocation of scalar type S (diagonal, omega / diagonal, the lower arrays), and the
+// level's pointers into it
+template <class S>
+int g_alloc_level(psp_mg *K, int l, S **owner, GLevelT<S> *G) {
+  const size_t N = (size_t)K->lev[l].N;
+  if (hipMalloc((void **)owner, sizeof(S) * (size_t)(2 + G->noff) * N) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PSP_ENOMEM, "multigrid: level operator allocation failed");
+  }
+  G->diag = *owner;
+  G->w = *owner + N;
+  for (int k = 0; k < G->noff; ++k) G->lo[k] = *owner + (size_t)(2 + k) * N;
+  return PSP_OK;
+}
+
+// precision='single': level l's double arrays rounded into float ones (flag: mg_round_kernel's), then released -- the
+// next level has been built from them by now.  hipFree waits for the kernels that still read them.
+int g_round_level(psp_mg *K, int l, int *flag) {
+  const GLevel &G = K->glev[l];
+  GLevelT<float> &F = K->glev32[l];
+  memset(&F, 0, sizeof F);
+  F.a = mg_round_level(G.a);
+  F.nd = G.nd;
+  F.noff = G.noff;
+  memcpy(F.od, G.od, sizeof F.od);
+  PSP_TRY(g_alloc_level(K, l, &K->coef32[l], &F));
+  const long N = K->lev[l].N, total = (long)(2 + G.noff) * N;
+  hipLaunchKernelGGL(mg_round_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream(), total, 2 * N,
+                     (const double *)K->coef[l], K->coef32[l], flag);
+  PSP_LAUNCH_CHECK();
+  K->op_bytes += sizeof(float) * (size_t)total;
+  return PSP_OK;
+}
+void g_release_double(psp_mg *K, int l) {
+  (void)hipFree(K->coef[l]);
+  K->coef[l] = nullptr;
+  GLevel &G = K->glev[l];
+  G.diag = G.w = nullptr;
+  for (int k = 0; k < kGMaxOff; ++k) G.lo[k] = nullptr;
+}
+
+// mg_create_galerkin's part of mg_make; flags: three ints on the device (the extraction's, the Galerkin product's, the
+// rounding's)
 int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
   const double omega = K->omega;
+  const bool single = K->single;
   const int nd = n[2] > 1 ? 3 : n[1] > 1 ? 2 : 1;
   PSP_TRY(mg_level_grids(K, n, K->steps));  // section 9c's
   const int nl = (int)K->lev.size();
-  // the level vectors and the level operators' arrays
+  // the level vectors and the level operators' arrays (a single-precision handle allocates a level's double arrays only
+  // when it builds the level)
   PSP_TRY(mg_alloc_vectors(K));
   K->glev.resize(nl);
   K->coef.assign(nl, nullptr);
+  if (single) {
+    K->glev32.resize(nl);
+    K->coef32.assign(nl, nullptr);
+  }
   for (int l = 0; l < nl; ++l) {
     psp_mg::Level &L = K->lev[l];
     GLevel &G = K->glev[l];
     memset(&G, 0, sizeof G);
     G.a = L.a;
+    if (single) L.af = mg_round_level(L.a);  // the prolongation's geometry
     G.nd = nd;
     G.noff = l == 0 ? nd : g_full_noff(nd);
-    if (hipMalloc((void **)&K->coef[l], sizeof(double) * (size_t)(2 + G.noff) * (size_t)L.N) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(PSP_ENOMEM, "multigrid: level operator allocation failed");
-    }
-    G.diag = K->coef[l];
-    G.w = K->coef[l] + L.N;
-    for (int k = 0; k < G.noff; ++k) {
-      G.lo[k] = K->coef[l] + (size_t)(2 + k) * (size_t)L.N;
+    for (int k = 0; k < G.noff; ++k)
       for (int a = 0; a < 3; ++a) G.od[k][a] = g_d(nd, G.noff, k, a);
+    if (!single || l == 0) {
+      PSP_TRY(g_alloc_level(K, l, &K->coef[l], &G));
+      if (!single) K->op_bytes += sizeof(double) * (size_t)(2 + G.noff) * (size_t)L.N;
     }
   }
   // level 0: the checking pass writes it
-  PSP_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), stream()));
+  PSP_HIP(hipMemsetAsync(flags, 0, 3 * sizeof(int), stream()));
   PSP_HIP(hipMemsetAsync(K->coef[0], 0, sizeof(double) * (size_t)(2 + nd) * (size_t)K->lev[0].N, stream()));
   hipLaunchKernelGGL(mg_extract_csr_kernel, dim3((A->nrows + 255) / 256), dim3(256), 0, stream(), A->nrows, n[0], n[1], n[2],
                      omega, (const int *)A->ind, (const int *)A->col, (const double *)A->val, g_out(K->glev[0]), flags);
@@ -1091,116 +1232,186 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
                 g_why(bad));
   // A_{l+1} = R_l A_l P_l, level by level
   for (int l = 0; l + 1 < nl; ++l) {
+    if (single) PSP_TRY(g_alloc_level(K, l + 1, &K->coef[l + 1], &K->glev[l + 1]));
     PSP_TRY(launch_galerkin(K->glev[l], K->lev[l + 1].N, omega, g_out(K->glev[l + 1]), flags + 1));
     PSP_LAUNCH_CHECK();
+    if (single) {
+      PSP_TRY(g_round_level(K, l, flags + 2));
+      g_release_double(K, l);
+    }
   }
-  PSP_TRY(read_flag(flags + 1, &bad));
-  if (bad) return fail(PSP_ESINGULAR, "multigrid(galerkin=True): a level operator's diagonal is not finite and > 0");
-  // the coarsest level: downloaded and inverted on the host
+  // the coarsest level: downloaded and inverted on the host (in double in either precision)
   const GLevel &C = K->glev[nl - 1];
   const int m = (int)K->lev[nl - 1].N;
   std::vector<double> blk((size_t)(2 + C.noff) * m), M, inv;
   PSP_HIP(hipMemcpyAsync(blk.data(), K->coef[nl - 1], sizeof(double) * blk.size(), hipMemcpyDeviceToHost, stream()));
+  if (single) PSP_TRY(g_round_level(K, nl - 1, flags + 2));
+  // the two flags of the chain, read once
+  int chain[2] = {0, 0};
+  PSP_HIP(hipMemcpyAsync(chain, flags + 1, 2 * sizeof(int), hipMemcpyDeviceToHost, stream()));
   PSP_HIP(hipStreamSynchronize(stream()));
+  if (single) g_release_double(K, nl - 1);
+  if (chain[0]) return fail(PSP_ESINGULAR, "multigrid(galerkin=True): a level operator's diagonal is not finite and > 0");
+  if (chain[1]) return fail(PSP_EINVAL, "%s", kSingleRange);
   g_dense(C, blk, &M);
   PSP_TRY(dense_inverse(m, M, &inv));
+  if (single) return mg_upload_tail(K, inv, [&](int l) { return K->glev32[l]; });
   return mg_upload_tail(K, inv, [&](int l) { return K->glev[l]; });
 }
 
-int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int steps, psp_mg **out) {
+int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, psp_mg **out) {
   int n[3];
   PSP_TRY(mg_check_args(A, ndim, grid, omega, steps, out, n));
   if (!(A->ind && A->col && A->val) || A->w4_only)
     return fail(PSP_EINVAL, "multigrid(galerkin=True): the handle no longer holds its index arrays on the device");
   PSP_TRY(ensure_device());
   int *flags = nullptr;
-  PSP_HIP(hipMalloc((void **)&flags, 2 * sizeof(int)));
-  const int rc = mg_make(A, ndim, omega, steps, true, out, [&](psp_mg *K) { return g_build(K, A, n, flags); });
+  PSP_HIP(hipMalloc((void **)&flags, 3 * sizeof(int)));
+  const int rc = mg_make(A, ndim, omega, steps, true, single, out, [&](psp_mg *K) { return g_build(K, A, n, flags); });
   (void)hipFree(flags);
   return rc;
 }
 
-template <class Op, bool FROMB>
-void launch_smooth(const typename Op::Level &A, long N, const double *xin, const double *b, double *xout) {
-  hipLaunchKernelGGL((mg_smooth_kernel<Op, FROMB>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream(), A, N, xin, b,
-                     xout);
+// A vector of the cycle: the handle's scalar type, or (wide) the caller's doubles, which only the finest level of a
+// single-precision handle mixes with its own floats.  ld: the leading dimension of a block of columns (column c at
+// p + c * ld), 0 for one vector.
+struct MVec {
+  void *p = nullptr;
+  long ld = 0;
+  bool wide = true;
+  template <class T>
+  T *as() const {
+    return static_cast<T *>(p);
+  }
+  bool operator==(const MVec &o) const { return p == o.p; }
+  bool operator!=(const MVec &o) const { return p != o.p; }
+};
+
+// f(b's element type *, the written vector's element type *): with S = double both are double -- the kernels of a double
+// handle exist in that one form; with S = float a wide b is the caller's (float vectors otherwise), and only next to a
+// wide b can the written vector be the caller's y.  FINEST = false: the level's shape (a stored level with the full
+// pattern) is never the finest level's, so the forms with wide vectors are not instantiated for it.
+template <class S, bool FINEST = true, class F>
+void mg_with_io(const MVec &b, const MVec &out, F &&f) {
+  if constexpr (std::is_same_v<S, double>) {
+    f(b.as<const double>(), out.as<double>());
+  } else if constexpr (!FINEST) {
+    f(b.as<const float>(), out.as<float>());
+  } else if (!b.wide) {
+    f(b.as<const float>(), out.as<float>());
+  } else if (!out.wide) {
+    f(b.as<const double>(), out.as<float>());
+  } else {
+    f(b.as<const double>(), out.as<double>());
+  }
+}
+template <class S, bool FINEST = true, class F>
+void mg_with_b(const MVec &b, F &&f) {
+  if constexpr (std::is_same_v<S, double>)
+    f(b.as<const double>());
+  else if constexpr (!FINEST)
+    f(b.as<const float>());
+  else if (b.wide)
+    f(b.as<const double>());
+  else
+    f(b.as<const float>());
 }
 
-template <class Op>
-void launch_restrict(const typename Op::Level &A, const double *x, const double *b, double *bc) {
-  const MgLevelArg &a = level_geo(A);
-  int tile[3];
+template <class S>
+void mg_restrict_grid(const MgLevelArgT<S> &a, int tile[3], long g[3]) {
   mg_tile(a, tile);
   // at most ceil(nc0 / t0) ceil(nc1 / t1) ceil(nc2 / t2) <= 2^31 / 256 + a few tiles: fits gridDim.x
-  const long g0n = (a.nc[0] + tile[0] - 1) / tile[0], g1n = (a.nc[1] + tile[1] - 1) / tile[1],
-             g2n = (a.nc[2] + tile[2] - 1) / tile[2];
-  hipLaunchKernelGGL((mg_restrict_kernel<Op>), dim3((unsigned)(g0n * g1n * g2n)), dim3(kResThreads), 0, stream(), A, tile[0],
-                     tile[1], tile[2], (int)g0n, (int)g1n, x, b, bc);
+  for (int x = 0; x < 3; ++x) g[x] = (a.nc[x] + tile[x] - 1) / tile[x];
 }
 
 // what the steps of the schedule below launch: the first pass from x = 0 (x = w b when steps = 1, else sweeps one and two
-// in one pass over b), a further sweep, b_c = R (b - A x), the tail -- the cycle kernels with the mode's policy
+// in one pass over b), a further sweep, b_c = R (b - A x), the tail -- the cycle kernels with the mode's policy, in the
+// handle's scalar type S
+template <class S>
 struct LevelOps {
   psp_mg *K;
-  using Vec = double *;
-  Vec lx(int l) const { return K->lev[l].x; }
-  Vec lb(int l) const { return K->lev[l].b; }
-  Vec lt(int l) const { return K->lev[l].t; }
-  void prolong(int l, const double *e, double *x) const {
-    const psp_mg::Level &L = K->lev[l];
-    hipLaunchKernelGGL(mg_prolong_kernel, dim3((unsigned)((L.N + 255) / 256)), dim3(256), 0, stream(), L.a, L.N, e, x);
+  using Vec = MVec;
+  static Vec vec(void *p) { return MVec{p, 0, std::is_same_v<S, double>}; }
+  Vec lx(int l) const { return vec(K->lev[l].x); }
+  Vec lb(int l) const { return vec(K->lev[l].b); }
+  Vec lt(int l) const { return vec(K->lev[l].t); }
+  void prolong(int l, Vec e, Vec x) const {
+    const long N = K->lev[l].N;
+    hipLaunchKernelGGL(mg_prolong_kernel<S>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream(), mf_level<S>(K, l), N,
+                       e.as<const S>(), x.as<S>());
+  }
+  template <class Op, bool FROMB>
+  void launch_smooth(const typename Op::Level &A, long N, Vec xin, Vec b, Vec xout) const {
+    mg_with_io<S, Op::kFinest>(b, xout, [&](auto *bp, auto *op) {
+      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
+      using TO = std::remove_pointer_t<decltype(op)>;
+      hipLaunchKernelGGL((mg_smooth_kernel<Op, FROMB, TB, TO>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream(), A, N,
+                         xin.as<const S>(), bp, op);
+    });
   }
   template <bool FROMB>
-  int smooth(int l, const double *xin, const double *b, double *xout) const {
+  int smooth(int l, Vec xin, Vec b, Vec xout) const {
     const long N = K->lev[l].N;
     if (K->galerkin) {
-      const GLevel &G = K->glev[l];
-      return g_dispatch(G, [&](auto sh) { launch_smooth<GOp<sh.nd, sh.noff>, FROMB>(G, N, xin, b, xout); });
+      const GLevelT<S> &G = g_level<S>(K, l);
+      return g_dispatch(G, [&](auto sh) { launch_smooth<GOp<sh.nd, sh.noff, S>, FROMB>(G, N, xin, b, xout); });
     }
-    const MgLevelArg &a = K->lev[l].a;
+    const MgLevelArgT<S> &a = mf_level<S>(K, l);
     switch (level_nd(a)) {
-      case 1: launch_smooth<MfOp<1>, FROMB>(a, N, xin, b, xout); break;
-      case 2: launch_smooth<MfOp<2>, FROMB>(a, N, xin, b, xout); break;
-      default: launch_smooth<MfOp<3>, FROMB>(a, N, xin, b, xout); break;
+      case 1: launch_smooth<MfOp<1, S>, FROMB>(a, N, xin, b, xout); break;
+      case 2: launch_smooth<MfOp<2, S>, FROMB>(a, N, xin, b, xout); break;
+      default: launch_smooth<MfOp<3, S>, FROMB>(a, N, xin, b, xout); break;
     }
     return PSP_OK;
   }
-  int first(int l, const double *b, double *dst) const {
-    if (K->steps > 1) return smooth<true>(l, nullptr, b, dst);
+  int first(int l, Vec b, Vec dst) const {
+    if (K->steps > 1) return smooth<true>(l, Vec(), b, dst);
     const long N = K->lev[l].N;
     const dim3 g((unsigned)((N + 255) / 256)), t(256);
-    if (K->galerkin)
-      hipLaunchKernelGGL(mg_scale_kernel<GW>, g, t, 0, stream(), N, GW{K->glev[l].w}, b, dst);
-    else
-      hipLaunchKernelGGL(mg_scale_kernel<MfW>, g, t, 0, stream(), N, MfW{K->lev[l].a.w}, b, dst);
+    mg_with_b<S>(b, [&](auto *bp) {
+      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
+      if (K->galerkin)
+        hipLaunchKernelGGL((mg_scale_kernel<GW<S>, TB>), g, t, 0, stream(), N, GW<S>{g_level<S>(K, l).w}, bp, dst.as<S>());
+      else
+        hipLaunchKernelGGL((mg_scale_kernel<MfW<S>, TB>), g, t, 0, stream(), N, MfW<S>{mf_level<S>(K, l).w}, bp, dst.as<S>());
+    });
     return PSP_OK;
   }
-  int sweep(int l, const double *xin, const double *b, double *xout) const { return smooth<false>(l, xin, b, xout); }
-  int restrict_to(int l, const double *x, const double *b, double *bc) const {
+  int sweep(int l, Vec xin, Vec b, Vec xout) const { return smooth<false>(l, xin, b, xout); }
+  template <class Op>
+  void launch_restrict(const typename Op::Level &A, Vec x, Vec b, Vec bc) const {
+    int tile[3];
+    long g[3];
+    mg_restrict_grid(level_geo(A), tile, g);
+    mg_with_b<S, Op::kFinest>(b, [&](auto *bp) {
+      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
+      hipLaunchKernelGGL((mg_restrict_kernel<Op, TB>), dim3((unsigned)(g[0] * g[1] * g[2])), dim3(kResThreads), 0, stream(), A,
+                         tile[0], tile[1], tile[2], (int)g[0], (int)g[1], x.as<const S>(), bp, bc.as<S>());
+    });
+  }
+  int restrict_to(int l, Vec x, Vec b, Vec bc) const {
     if (K->galerkin) {
-      const GLevel &G = K->glev[l];
-      return g_dispatch(G, [&](auto sh) { launch_restrict<GOp<sh.nd, sh.noff>>(G, x, b, bc); });
+      const GLevelT<S> &G = g_level<S>(K, l);
+      return g_dispatch(G, [&](auto sh) { launch_restrict<GOp<sh.nd, sh.noff, S>>(G, x, b, bc); });
     }
-    launch_restrict<MfOp<3>>(K->lev[l].a, x, b, bc);
+    launch_restrict<MfOp<3, S>>(mf_level<S>(K, l), x, b, bc);
     return PSP_OK;
   }
-  void tail(const double *b, double *x) const {
-    if (K->galerkin)
-      hipLaunchKernelGGL(mg_tail_kernel<GTailOp>, dim3(1), dim3(kTailThreads), 0, stream(),
-                         (const TailArg<GLevel> *)K->tail, (const double *)K->minv, b, x);
-    else
-      hipLaunchKernelGGL(mg_tail_kernel<MfOp<3>>, dim3(1), dim3(kTailThreads), 0, stream(),
-                         (const TailArg<MgLevelArg> *)K->tail, (const double *)K->minv, b, x);
+  // the tail's ends are both the caller's (the whole grid is the tail) or both the handle's
+  void tail(Vec b, Vec x) const {
+    mg_with_io<S>(b, x, [&](auto *bp, auto *xp) {
+      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
+      using TX = std::remove_pointer_t<decltype(xp)>;
+      if constexpr (std::is_same_v<TB, TX>) {
+        if (K->galerkin)
+          hipLaunchKernelGGL((mg_tail_kernel<GTailOp<S>, TB, TX>), dim3(1), dim3(kTailThreads), 0, stream(),
+                             (const TailArg<GLevelT<S>> *)K->tail, (const S *)K->minv, bp, xp);
+        else
+          hipLaunchKernelGGL((mg_tail_kernel<MfOp<3, S>, TB, TX>), dim3(1), dim3(kTailThreads), 0, stream(),
+                             (const TailArg<MgLevelArgT<S>> *)K->tail, (const S *)K->minv, bp, xp);
+      }
+    });
   }
-};
-
-// a block of vectors: column c at p + c * ld
-struct BVec {
-  double *p = nullptr;
-  long ld = 0;
-  const double *cp() const { return p; }
-  bool operator==(const BVec &o) const { return p == o.p; }
-  bool operator!=(const BVec &o) const { return p != o.p; }
 };
 
 // Columns per thread of the block kernels, by measurement (DESIGN.md section 9e has the register table and the figures).
@@ -1225,78 +1436,89 @@ int block_tuning(const char *name, int dflt, std::initializer_list<int> allowed)
 }
 
 // the block cycle's launches: LevelOps with the column count, the leading dimensions and the frozen flags
+template <class S>
 struct BlockOps {
   psp_mg *K;
   int k;
   const int *frozen;
   int kc, kcr;
-  using Vec = BVec;
+  using Vec = MVec;
   BlockOps(psp_mg *K_, int k_, const int *frozen_) : K(K_), k(k_), frozen(frozen_) {
     kc = k <= 2 ? 2 : block_tuning("PSP_MG_BLOCK_KC", K->galerkin ? kBlockKCGalerkin : kBlockKCMatrixFree, {2, 4});
     kcr = k == 1 ? 1 : block_tuning("PSP_MG_BLOCK_KCR", kBlockKCR, {1, 2, 4});
   }
-  Vec lx(int l) const { return BVec{K->blk[l].x, K->lev[l].N}; }
-  Vec lb(int l) const { return BVec{K->blk[l].b, K->lev[l].N}; }
-  Vec lt(int l) const { return BVec{K->blk[l].t, K->lev[l].N}; }
+  Vec vec(void *p, int l) const { return MVec{p, K->lev[l].N, std::is_same_v<S, double>}; }
+  Vec lx(int l) const { return vec(K->blk[l].x, l); }
+  Vec lb(int l) const { return vec(K->blk[l].b, l); }
+  Vec lt(int l) const { return vec(K->blk[l].t, l); }
   dim3 grid(long N) const { return dim3((unsigned)((N + 255) / 256), (unsigned)((k + kc - 1) / kc)); }
 
   template <class Op, bool FROMB>
-  void launch_smooth(const typename Op::Level &A, long N, BVec xin, BVec b, BVec xout) const {
-    if (kc == 4)
-      hipLaunchKernelGGL((mg_smooth_block_kernel<Op, FROMB, 4>), grid(N), dim3(256), 0, stream(), A, N, k, xin.cp(), xin.ld,
-                         b.cp(), b.ld, xout.p, xout.ld, frozen);
-    else
-      hipLaunchKernelGGL((mg_smooth_block_kernel<Op, FROMB, 2>), grid(N), dim3(256), 0, stream(), A, N, k, xin.cp(), xin.ld,
-                         b.cp(), b.ld, xout.p, xout.ld, frozen);
+  void launch_smooth(const typename Op::Level &A, long N, Vec xin, Vec b, Vec xout) const {
+    mg_with_io<S, Op::kFinest>(b, xout, [&](auto *bp, auto *op) {
+      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
+      using TO = std::remove_pointer_t<decltype(op)>;
+      if (kc == 4)
+        hipLaunchKernelGGL((mg_smooth_block_kernel<Op, FROMB, 4, TB, TO>), grid(N), dim3(256), 0, stream(), A, N, k,
+                           xin.as<const S>(), xin.ld, bp, b.ld, op, xout.ld, frozen);
+      else
+        hipLaunchKernelGGL((mg_smooth_block_kernel<Op, FROMB, 2, TB, TO>), grid(N), dim3(256), 0, stream(), A, N, k,
+                           xin.as<const S>(), xin.ld, bp, b.ld, op, xout.ld, frozen);
+    });
   }
   template <bool FROMB>
-  int smooth(int l, BVec xin, BVec b, BVec xout) const {
+  int smooth(int l, Vec xin, Vec b, Vec xout) const {
     const long N = K->lev[l].N;
     if (K->galerkin) {
-      const GLevel &G = K->glev[l];
-      return g_dispatch(G, [&](auto sh) { launch_smooth<GOp<sh.nd, sh.noff>, FROMB>(G, N, xin, b, xout); });
+      const GLevelT<S> &G = g_level<S>(K, l);
+      return g_dispatch(G, [&](auto sh) { launch_smooth<GOp<sh.nd, sh.noff, S>, FROMB>(G, N, xin, b, xout); });
     }
-    const MgLevelArg &a = K->lev[l].a;
+    const MgLevelArgT<S> &a = mf_level<S>(K, l);
     switch (level_nd(a)) {
-      case 1: launch_smooth<MfOp<1>, FROMB>(a, N, xin, b, xout); break;
-      case 2: launch_smooth<MfOp<2>, FROMB>(a, N, xin, b, xout); break;
-      default: launch_smooth<MfOp<3>, FROMB>(a, N, xin, b, xout); break;
+      case 1: launch_smooth<MfOp<1, S>, FROMB>(a, N, xin, b, xout); break;
+      case 2: launch_smooth<MfOp<2, S>, FROMB>(a, N, xin, b, xout); break;
+      default: launch_smooth<MfOp<3, S>, FROMB>(a, N, xin, b, xout); break;
     }
     return PSP_OK;
   }
   template <class W>
-  void launch_scale(long N, W w, BVec b, BVec dst) const {
-    if (kc == 4)
-      hipLaunchKernelGGL((mg_scale_block_kernel<W, 4>), grid(N), dim3(256), 0, stream(), N, w, k, b.cp(), b.ld, dst.p, dst.ld,
-                         frozen);
-    else
-      hipLaunchKernelGGL((mg_scale_block_kernel<W, 2>), grid(N), dim3(256), 0, stream(), N, w, k, b.cp(), b.ld, dst.p, dst.ld,
-                         frozen);
+  void launch_scale(long N, W w, Vec b, Vec dst) const {
+    mg_with_b<S>(b, [&](auto *bp) {
+      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
+      if (kc == 4)
+        hipLaunchKernelGGL((mg_scale_block_kernel<W, 4, TB>), grid(N), dim3(256), 0, stream(), N, w, k, bp, b.ld, dst.as<S>(),
+                           dst.ld, frozen);
+      else
+        hipLaunchKernelGGL((mg_scale_block_kernel<W, 2, TB>), grid(N), dim3(256), 0, stream(), N, w, k, bp, b.ld, dst.as<S>(),
+                           dst.ld, frozen);
+    });
   }
-  int first(int l, BVec b, BVec dst) const {
-    if (K->steps > 1) return smooth<true>(l, BVec(), b, dst);
+  int first(int l, Vec b, Vec dst) const {
+    if (K->steps > 1) return smooth<true>(l, Vec(), b, dst);
     const long N = K->lev[l].N;
     if (K->galerkin)
-      launch_scale(N, GW{K->glev[l].w}, b, dst);
+      launch_scale(N, GW<S>{g_level<S>(K, l).w}, b, dst);
     else
-      launch_scale(N, MfW{K->lev[l].a.w}, b, dst);
+      launch_scale(N, MfW<S>{mf_level<S>(K, l).w}, b, dst);
     return PSP_OK;
   }
-  int sweep(int l, BVec xin, BVec b, BVec xout) const { return smooth<false>(l, xin, b, xout); }
+  int sweep(int l, Vec xin, Vec b, Vec xout) const { return smooth<false>(l, xin, b, xout); }
 
   template <class Op, int KCR>
-  void launch_restrict_kc(const typename Op::Level &A, BVec x, BVec b, BVec bc) const {
-    const MgLevelArg &a = level_geo(A);
+  void launch_restrict_kc(const typename Op::Level &A, Vec x, Vec b, Vec bc) const {
     int tile[3];
-    mg_tile(a, tile);
-    const long g0n = (a.nc[0] + tile[0] - 1) / tile[0], g1n = (a.nc[1] + tile[1] - 1) / tile[1],
-               g2n = (a.nc[2] + tile[2] - 1) / tile[2];
-    hipLaunchKernelGGL((mg_restrict_block_kernel<Op, KCR>), dim3((unsigned)(g0n * g1n * g2n), (unsigned)((k + KCR - 1) / KCR)),
-                       dim3(kResThreads), 0, stream(), A, tile[0], tile[1], tile[2], (int)g0n, (int)g1n, k, x.cp(), x.ld,
-                       b.cp(), b.ld, bc.p, bc.ld, frozen);
+    long g[3];
+    mg_restrict_grid(level_geo(A), tile, g);
+    mg_with_b<S, Op::kFinest>(b, [&](auto *bp) {
+      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
+      hipLaunchKernelGGL((mg_restrict_block_kernel<Op, KCR, TB>),
+                         dim3((unsigned)(g[0] * g[1] * g[2]), (unsigned)((k + KCR - 1) / KCR)), dim3(kResThreads), 0, stream(), A,
+                         tile[0], tile[1], tile[2], (int)g[0], (int)g[1], k, x.as<const S>(), x.ld, bp, b.ld, bc.as<S>(), bc.ld,
+                         frozen);
+    });
   }
   template <class Op>
-  void launch_restrict(const typename Op::Level &A, BVec x, BVec b, BVec bc) const {
+  void launch_restrict(const typename Op::Level &A, Vec x, Vec b, Vec bc) const {
     if (kcr == 4)
       launch_restrict_kc<Op, 4>(A, x, b, bc);
     else if (kcr == 2)
@@ -1304,59 +1526,67 @@ struct BlockOps {
     else
       launch_restrict_kc<Op, 1>(A, x, b, bc);
   }
-  int restrict_to(int l, BVec x, BVec b, BVec bc) const {
+  int restrict_to(int l, Vec x, Vec b, Vec bc) const {
     if (K->galerkin) {
-      const GLevel &G = K->glev[l];
-      return g_dispatch(G, [&](auto sh) { launch_restrict<GOp<sh.nd, sh.noff>>(G, x, b, bc); });
+      const GLevelT<S> &G = g_level<S>(K, l);
+      return g_dispatch(G, [&](auto sh) { launch_restrict<GOp<sh.nd, sh.noff, S>>(G, x, b, bc); });
     }
-    launch_restrict<MfOp<3>>(K->lev[l].a, x, b, bc);
+    launch_restrict<MfOp<3, S>>(mf_level<S>(K, l), x, b, bc);
     return PSP_OK;
   }
-  void tail(BVec b, BVec x) const {
-    if (K->galerkin)
-      hipLaunchKernelGGL(mg_tail_block_kernel<GTailOp>, dim3(k), dim3(kTailThreads), 0, stream(),
-                         (const TailArg<GLevel> *)K->tail, (const double *)K->minv, b.cp(), b.ld, x.p, x.ld, frozen);
-    else
-      hipLaunchKernelGGL(mg_tail_block_kernel<MfOp<3>>, dim3(k), dim3(kTailThreads), 0, stream(),
-                         (const TailArg<MgLevelArg> *)K->tail, (const double *)K->minv, b.cp(), b.ld, x.p, x.ld, frozen);
+  void tail(Vec b, Vec x) const {
+    mg_with_io<S>(b, x, [&](auto *bp, auto *xp) {
+      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
+      using TX = std::remove_pointer_t<decltype(xp)>;
+      if constexpr (std::is_same_v<TB, TX>) {
+        if (K->galerkin)
+          hipLaunchKernelGGL((mg_tail_block_kernel<GTailOp<S>, TB, TX>), dim3(k), dim3(kTailThreads), 0, stream(),
+                             (const TailArg<GLevelT<S>> *)K->tail, (const S *)K->minv, bp, b.ld, xp, x.ld, frozen);
+        else
+          hipLaunchKernelGGL((mg_tail_block_kernel<MfOp<3, S>, TB, TX>), dim3(k), dim3(kTailThreads), 0, stream(),
+                             (const TailArg<MgLevelArgT<S>> *)K->tail, (const S *)K->minv, bp, b.ld, xp, x.ld, frozen);
+      }
+    });
   }
-  void prolong(int l, BVec e, BVec x) const {
-    const psp_mg::Level &L = K->lev[l];
+  void prolong(int l, Vec e, Vec x) const {
+    const long N = K->lev[l].N;
     if (kc == 4)
-      hipLaunchKernelGGL(mg_prolong_block_kernel<4>, grid(L.N), dim3(256), 0, stream(), L.a, L.N, k, e.cp(), e.ld, x.p, x.ld,
-                         frozen);
+      hipLaunchKernelGGL((mg_prolong_block_kernel<4, S>), grid(N), dim3(256), 0, stream(), mf_level<S>(K, l), N, k,
+                         e.as<const S>(), e.ld, x.as<S>(), x.ld, frozen);
     else
-      hipLaunchKernelGGL(mg_prolong_block_kernel<2>, grid(L.N), dim3(256), 0, stream(), L.a, L.N, k, e.cp(), e.ld, x.p, x.ld,
-                         frozen);
+      hipLaunchKernelGGL((mg_prolong_block_kernel<2, S>), grid(N), dim3(256), 0, stream(), mf_level<S>(K, l), N, k,
+                         e.as<const S>(), e.ld, x.as<S>(), x.ld, frozen);
   }
 };
 
 // the sss entry points: an sss_mat is read through its full device mirror
-int mg_create_sss(psp_sss_t *A, const char *fn, int (*create)(psp_csr *, int, const int *, double, int, psp_mg **), int ndim,
-                  const int *grid, double omega, int steps, psp_mg **out) {
+int mg_create_sss(psp_sss_t *A, const char *fn, int (*create)(psp_csr *, int, const int *, double, int, bool, psp_mg **),
+                  int ndim, const int *grid, double omega, int steps, bool single, psp_mg **out) {
   PSP_API_GUARD_H(A, A ? A->full : nullptr);
   if (!A) return fail(PSP_EINVAL, "%s: NULL argument", fn);
   if (A->host || cpu_mode())
     return fail(PSP_ENODEV, "precon.multigrid: not available with PSP_DEVICE=cpu (host mode covers csr / sss / jacobi / pcg / minres)");
   if (!A->full) return fail(PSP_EINVAL, "%s: the matrix has no device mirror", fn);
-  return create(A->full, ndim, grid, omega, steps, out);
+  return create(A->full, ndim, grid, omega, steps, single, out);
 }
 
-// one V-cycle: the schedule of launches and buffers, the same in both modes and for one vector (Ops::Vec = double *) or a
-// block of them (BVec): K->launches launches whatever the column count is.  b_dev is only read.
+// one V-cycle: the schedule of launches and buffers, the same in both modes, both precisions and for one vector or a block
+// of them: K->launches launches whatever the column count is.  b_dev is only read.  A double handle's finest level works
+// in y and one spare; a single-precision one in two float vectors of its own, and only its last sweep writes y.
 template <class Ops>
 int mg_schedule(psp_mg *K, typename Ops::Vec b_dev, typename Ops::Vec y_dev, const Ops &ops) {
   using V = typename Ops::Vec;
   const int steps = K->steps, tf = K->tail_first;
+  const bool own0 = K->single;
   // where each large level's iterate is after its pre-smoothing; every sweep writes the buffer the previous one did not
   V cur[kMaxLevels] = {};
   // down
   for (int l = 0; l < tf; ++l) {
     const V b = l == 0 ? b_dev : ops.lb(l);
-    const V own = l == 0 ? y_dev : ops.lx(l);
+    const V own = l == 0 && !own0 ? y_dev : ops.lx(l);
     // the finest level's last sweep must land in y: its writes are the pre-smoothing launches and `steps` more
     const int writes = (steps >= 2 ? steps - 1 : 1) + steps;
-    V dst = (l == 0 && (writes & 1) == 0) ? ops.lt(l) : own;
+    V dst = (l == 0 && !own0 && (writes & 1) == 0) ? ops.lt(l) : own;
     PSP_TRY(ops.first(l, b, dst));
     for (int k = 2; k < steps; ++k) {
       V nxt = dst == own ? ops.lt(l) : own;
@@ -1378,11 +1608,12 @@ int mg_schedule(psp_mg *K, typename Ops::Vec b_dev, typename Ops::Vec y_dev, con
   // up
   for (int l = tf - 1; l >= 0; --l) {
     const V b = l == 0 ? b_dev : ops.lb(l);
-    const V own = l == 0 ? y_dev : ops.lx(l);
+    const V own = l == 0 && !own0 ? y_dev : ops.lx(l);
     V x = cur[l];
     ops.prolong(l, cur[l + 1], x);
     for (int k = 0; k < steps; ++k) {
       V nxt = x == own ? ops.lt(l) : own;
+      if (l == 0 && own0 && k == steps - 1) nxt = y_dev;
       PSP_TRY(ops.sweep(l, x, b, nxt));
       x = nxt;
     }
@@ -1395,7 +1626,7 @@ int mg_schedule(psp_mg *K, typename Ops::Vec b_dev, typename Ops::Vec y_dev, con
 
 void mg_block_free(psp_mg *K) {
   for (psp_mg::BlockLevel &B : K->blk)
-    for (void *p : {(void *)B.x, (void *)B.b, (void *)B.t}) (void)hipFree(p);
+    for (void *p : {B.x, B.b, B.t}) (void)hipFree(p);
   K->blk.clear();
   K->blk_cols = 0;
   K->blk_bytes = 0;
@@ -1413,12 +1644,13 @@ int mg_block_reserve(psp_mg *K, int k) {
   K->blk.resize(K->lev.size());
   for (int l = 0; l <= K->tail_first; ++l) {
     psp_mg::BlockLevel &B = K->blk[l];
-    const size_t bytes = sizeof(double) * (size_t)K->lev[l].N * (size_t)k;
+    const size_t bytes = (K->single ? sizeof(float) : sizeof(double)) * (size_t)K->lev[l].N * (size_t)k;
+    const bool own_x = l > 0 || (K->single && K->tail_first > 0);  // as mg_alloc_vectors
     hipError_t e = hipSuccess;
     size_t got = 0;
-    if (l < K->tail_first) e = hipMalloc((void **)&B.t, bytes), got += e == hipSuccess ? bytes : 0;
-    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&B.x, bytes), got += e == hipSuccess ? bytes : 0;
-    if (l > 0 && e == hipSuccess) e = hipMalloc((void **)&B.b, bytes), got += e == hipSuccess ? bytes : 0;
+    if (l < K->tail_first) e = hipMalloc(&B.t, bytes), got += e == hipSuccess ? bytes : 0;
+    if (own_x && e == hipSuccess) e = hipMalloc(&B.x, bytes), got += e == hipSuccess ? bytes : 0;
+    if (l > 0 && e == hipSuccess) e = hipMalloc(&B.b, bytes), got += e == hipSuccess ? bytes : 0;
     K->blk_bytes += got;
     if (e != hipSuccess) {
       (void)hipGetLastError();
@@ -1436,7 +1668,9 @@ namespace psp {
 
 // y = V(0, b) on device vectors; y must not alias b.  The handle is locked by the caller.
 int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
-  return mg_schedule(K, const_cast<double *>(b_dev), y_dev, LevelOps{K});
+  const MVec b{const_cast<double *>(b_dev), 0, true}, y{y_dev, 0, true};
+  if (K->single) return mg_schedule(K, b, y, LevelOps<float>{K});
+  return mg_schedule(K, b, y, LevelOps<double>{K});
 }
 
 // Y[:, c] = V(0, X[:, c]) for every column c < k with frozen[c] == 0 (frozen == nullptr: every column), one block cycle:
@@ -1444,7 +1678,9 @@ int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
 // caller.
 int mg_apply_block_dev(psp_mg *K, int k, const double *X, long ldx, double *Y, long ldy, const int *frozen) {
   PSP_TRY(mg_block_reserve(K, k));
-  return mg_schedule(K, BVec{const_cast<double *>(X), ldx}, BVec{Y, ldy}, BlockOps(K, k, frozen));
+  const MVec x{const_cast<double *>(X), ldx, true}, y{Y, ldy, true};
+  if (K->single) return mg_schedule(K, x, y, BlockOps<float>(K, k, frozen));
+  return mg_schedule(K, x, y, BlockOps<double>(K, k, frozen));
 }
 
 int mg_launches(const psp_mg *K) { return K->launches; }
@@ -1457,22 +1693,49 @@ bool mg_block_routed(const psp_mg *K) { return K->galerkin ? kRouteBlockGalerkin
 
 extern "C" {
 
-int psp_mg_create_csr(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
+int psp_mg_create_csr_ex(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, unsigned flags, psp_mg_t **out) {
   PSP_API_GUARD_H(A);
-  return mg_create(A, ndim, grid, omega, steps, out);
+  if (flags & ~(unsigned)(PSP_MG_GALERKIN | PSP_MG_SINGLE)) return fail(PSP_EINVAL, "psp_mg_create_csr_ex: unknown flags 0x%x", flags);
+  const bool single = (flags & PSP_MG_SINGLE) != 0;
+  if (flags & PSP_MG_GALERKIN) return mg_create_galerkin(A, ndim, grid, omega, steps, single, out);
+  return mg_create(A, ndim, grid, omega, steps, single, out);
+}
+
+int psp_mg_create_sss_ex(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, unsigned flags, psp_mg_t **out) {
+  if (flags & ~(unsigned)(PSP_MG_GALERKIN | PSP_MG_SINGLE)) return fail(PSP_EINVAL, "psp_mg_create_sss_ex: unknown flags 0x%x", flags);
+  const bool single = (flags & PSP_MG_SINGLE) != 0;
+  if (flags & PSP_MG_GALERKIN)
+    return mg_create_sss(A, "psp_mg_create_sss_galerkin", mg_create_galerkin, ndim, grid, omega, steps, single, out);
+  return mg_create_sss(A, "psp_mg_create_sss", mg_create, ndim, grid, omega, steps, single, out);
+}
+
+int psp_mg_create_csr(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
+  return psp_mg_create_csr_ex(A, ndim, grid, omega, steps, 0u, out);
 }
 
 int psp_mg_create_sss(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
-  return mg_create_sss(A, "psp_mg_create_sss", mg_create, ndim, grid, omega, steps, out);
+  return psp_mg_create_sss_ex(A, ndim, grid, omega, steps, 0u, out);
 }
 
 int psp_mg_create_csr_galerkin(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
-  PSP_API_GUARD_H(A);
-  return mg_create_galerkin(A, ndim, grid, omega, steps, out);
+  return psp_mg_create_csr_ex(A, ndim, grid, omega, steps, PSP_MG_GALERKIN, out);
 }
 
 int psp_mg_create_sss_galerkin(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
-  return mg_create_sss(A, "psp_mg_create_sss_galerkin", mg_create_galerkin, ndim, grid, omega, steps, out);
+  return psp_mg_create_sss_ex(A, ndim, grid, omega, steps, PSP_MG_GALERKIN, out);
+}
+
+int psp_mg_precision(const psp_mg_t *K, int *bits) {
+  if (!K || !bits) return fail(PSP_EINVAL, "psp_mg_precision: NULL argument");
+  *bits = K->single ? 32 : 64;
+  return PSP_OK;
+}
+
+int psp_mg_bytes(const psp_mg_t *K, long long *operator_bytes, long long *vector_bytes) {
+  if (!K) return fail(PSP_EINVAL, "psp_mg_bytes: NULL handle");
+  if (operator_bytes) *operator_bytes = (long long)K->op_bytes;
+  if (vector_bytes) *vector_bytes = (long long)K->vec_bytes;
+  return PSP_OK;
 }
 
 int psp_mg_is_galerkin(const psp_mg_t *K, int *galerkin) {
@@ -1486,7 +1749,7 @@ int psp_mg_level_operator(psp_mg_t *K, int level, int *offsets_out, int *noff_in
   if (!K || !noff_inout) return fail(PSP_EINVAL, "psp_mg_level_operator: NULL argument");
   if (!K->galerkin) return fail(PSP_EINVAL, "psp_mg_level_operator: the handle stores no level operators (galerkin=False)");
   if (level < 0 || level >= (int)K->glev.size()) return fail(PSP_EINVAL, "psp_mg_level_operator: no level %d", level);
-  const GLevel &G = K->glev[level];
+  const GLevel &G = K->glev[level];  // a single-precision handle keeps the geometry here, the arrays in glev32
   const int cap = *noff_inout, cnt = 1 + G.noff;
   *noff_inout = cnt;
   if (!offsets_out && !values_host) return PSP_OK;
@@ -1499,6 +1762,16 @@ int psp_mg_level_operator(psp_mg_t *K, int level, int *offsets_out, int *noff_in
   if (values_host) {
     const size_t N = (size_t)K->lev[level].N;
     PSP_TRY(ensure_device());
+    if (K->single) {  // the stored floats, widened
+      const GLevelT<float> &F = K->glev32[level];
+      std::vector<float> tmp(N * (size_t)cnt);
+      PSP_HIP(hipMemcpyAsync(tmp.data(), F.diag, sizeof(float) * N, hipMemcpyDeviceToHost, stream()));
+      if (F.noff > 0)
+        PSP_HIP(hipMemcpyAsync(tmp.data() + N, F.lo[0], sizeof(float) * N * (size_t)F.noff, hipMemcpyDeviceToHost, stream()));
+      PSP_HIP(hipStreamSynchronize(stream()));
+      for (size_t i = 0; i < tmp.size(); ++i) values_host[i] = (double)tmp[i];
+      return PSP_OK;
+    }
     PSP_HIP(hipMemcpyAsync(values_host, G.diag, sizeof(double) * N, hipMemcpyDeviceToHost, stream()));
     if (G.noff > 0)  // the lower arrays follow omega / diagonal in the level's allocation
       PSP_HIP(hipMemcpyAsync(values_host + N, G.lo[0], sizeof(double) * N * (size_t)G.noff, hipMemcpyDeviceToHost, stream()));
@@ -1511,8 +1784,9 @@ int psp_mg_destroy(psp_mg_t *K) {
   if (!K) return PSP_OK;
   mg_block_free(K);
   for (double *p : K->coef) (void)hipFree(p);
+  for (float *p : K->coef32) (void)hipFree(p);
   for (psp_mg::Level &L : K->lev)
-    for (void *p : {(void *)L.x, (void *)L.b, (void *)L.t}) (void)hipFree(p);
+    for (void *p : {L.x, L.b, L.t}) (void)hipFree(p);
   (void)hipFree(K->minv);
   (void)hipFree(K->tail);
   delete K;

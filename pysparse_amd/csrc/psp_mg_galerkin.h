@@ -15,20 +15,26 @@ namespace {
 
 constexpr int kGMaxOff = 13;
 
-struct GLevel {
-  MgLevelArg a;  // n, co, nc, rs as in the matrix-free mode (c, d, w are not used)
-  int nd;        // axes of the level's index
-  int noff;      // lower arrays: nd on level 0, (3^nd - 1) / 2 below
-  const double *diag, *w;  // A_l[K, K] and omega / A_l[K, K]
-  const double *lo[kGMaxOff];
+// S: the scalar type of the stored arrays and of the cycle (float: section 9g, the arrays rounded once from the double ones)
+template <class S>
+struct GLevelT {
+  MgLevelArgT<S> a;  // n, co, nc, rs as in the matrix-free mode (c, d, w are not used)
+  int nd;            // axes of the level's index
+  int noff;          // lower arrays: nd on level 0, (3^nd - 1) / 2 below
+  const S *diag, *w;  // A_l[K, K] and omega / A_l[K, K]
+  const S *lo[kGMaxOff];
   int od[kGMaxOff][3];  // the lower offsets' components, for the tail's run-time loop (g_ax_rt)
 };
+using GLevel = GLevelT<double>;
 
 struct GOut {
   double *diag, *w, *lo[kGMaxOff];
 };
 
-__host__ __device__ inline const MgLevelArg &level_geo(const GLevel &G) { return G.a; }
+template <class S>
+__host__ __device__ inline const MgLevelArgT<S> &level_geo(const GLevelT<S> &G) {
+  return G.a;
+}
 
 constexpr int g_full_noff(int nd) { return nd == 1 ? 1 : nd == 2 ? 4 : 13; }
 constexpr int g_pow3(int nd) { return nd == 1 ? 3 : nd == 2 ? 9 : 27; }
@@ -80,9 +86,9 @@ __device__ __forceinline__ bool g_in(int v, int n) {
 }
 
 // (A_l x)[i]: the diagonal term, then per stored offset in its fixed order the lower and the upper neighbour
-template <int ND, int NOFF, class X>
-__device__ __forceinline__ double g_ax(const GLevel &L, const X &x, long i, int i0, int i1, int i2) {
-  double acc = L.diag[i] * x(i);
+template <int ND, int NOFF, class S, class X>
+__device__ __forceinline__ S g_ax(const GLevelT<S> &L, const X &x, long i, int i0, int i1, int i2) {
+  S acc = L.diag[i] * x(i);
   const int n0 = L.a.n[0], n1 = L.a.n[1], n2 = L.a.n[2];
   g_for<0, NOFF>([&](auto kc) {
     constexpr int k = decltype(kc)::value;
@@ -96,14 +102,14 @@ __device__ __forceinline__ double g_ax(const GLevel &L, const X &x, long i, int 
 
 // the same sum in the same order for a level whose shape is only known at run time (the tail, where L lives in global
 // memory: the offsets and the array pointers are loads, nothing is indexed in registers)
-template <class X>
-__device__ __forceinline__ double g_ax_rt(const GLevel &L, const X &x, int i, int i0, int i1, int i2) {
-  double acc = L.diag[i] * x(i);
+template <class S, class X>
+__device__ __forceinline__ S g_ax_rt(const GLevelT<S> &L, const X &x, int i, int i0, int i1, int i2) {
+  S acc = L.diag[i] * x(i);
   const int n0 = L.a.n[0], n1 = L.a.n[1], n2 = L.a.n[2], noff = L.noff;
   for (int k = 0; k < noff; ++k) {
     const int d0 = L.od[k][0], d1 = L.od[k][1], d2 = L.od[k][2];
     const int o = d0 + n0 * (d1 + n1 * d2);
-    const double *__restrict__ lo = L.lo[k];
+    const S *__restrict__ lo = L.lo[k];
     if ((unsigned)(i0 + d0) < (unsigned)n0 && (unsigned)(i1 + d1) < (unsigned)n1 && (unsigned)(i2 + d2) < (unsigned)n2)
       acc += lo[i] * x(i + o);
     if ((unsigned)(i0 - d0) < (unsigned)n0 && (unsigned)(i1 - d1) < (unsigned)n1 && (unsigned)(i2 - d2) < (unsigned)n2)
@@ -116,31 +122,33 @@ __device__ __forceinline__ double g_ax_rt(const GLevel &L, const X &x, int i, in
 // per stored offset the lower coupling (the array at i) and the upper one (the array at i - o), 0 where the neighbour
 // does not exist (mlo / mup say which do).  WN: also omega / diagonal of every neighbour, which the fused first pass
 // (xin = w .* b formed on the fly) multiplies the neighbours' b by.  Every index is a compile-time constant.
-template <int NOFF, bool WN>
+template <class S, int NOFF, bool WN>
 struct GRow {
-  double d, w;
-  double lo[NOFF], up[NOFF];
-  double wlo[WN ? NOFF : 1], wup[WN ? NOFF : 1];
+  S d, w;
+  S lo[NOFF], up[NOFF];
+  S wlo[WN ? NOFF : 1], wup[WN ? NOFF : 1];
   unsigned mlo, mup;
 };
 
 // The level-operator policies of the stored mode.  GOp: the launch-per-step kernels, the level's shape in the type (g_ax).
-template <int ND, int NOFF>
+template <int ND, int NOFF, class S>
 struct GOp {
-  using Level = GLevel;
-  const GLevel &G;
-  __device__ __forceinline__ explicit GOp(const GLevel &g) : G(g) {}
-  __device__ __forceinline__ const MgLevelArg &geo() const { return G.a; }
+  using Scalar = S;
+  static constexpr bool kFinest = NOFF == ND;  // level 0 stores the axis offsets only (in 1-D every level does)
+  using Level = GLevelT<S>;
+  const Level &G;
+  __device__ __forceinline__ explicit GOp(const Level &g) : G(g) {}
+  __device__ __forceinline__ const MgLevelArgT<S> &geo() const { return G.a; }
   template <class X>
-  __device__ __forceinline__ double ax(const X &x, long i, int i0, int i1, int i2) const {
+  __device__ __forceinline__ S ax(const X &x, long i, int i0, int i1, int i2) const {
     return g_ax<ND, NOFF>(G, x, i, i0, i1, i2);
   }
   // "load the row, then apply it to a column": every load of a coefficient happens in load_row, ax_row reads only the
   // column (x(j, w_j) is the column's value at j; w_j = omega / diagonal at j, 0.0 unless the row was loaded with WN).
   // The terms and their order are g_ax's.
   template <bool WN>
-  __device__ __forceinline__ GRow<NOFF, WN> load_row(long i, int i0, int i1, int i2) const {
-    GRow<NOFF, WN> r;
+  __device__ __forceinline__ GRow<S, NOFF, WN> load_row(long i, int i0, int i1, int i2) const {
+    GRow<S, NOFF, WN> r;
     r.d = G.diag[i];
     r.w = G.w[i];
     r.mlo = r.mup = 0u;
@@ -151,54 +159,72 @@ struct GOp {
       const long o = d0 + (long)n0 * (d1 + (long)n1 * d2);
       const bool inl = g_in<d0>(i0, n0) && g_in<d1>(i1, n1) && g_in<d2>(i2, n2);
       const bool inu = g_in<-d0>(i0, n0) && g_in<-d1>(i1, n1) && g_in<-d2>(i2, n2);
-      r.lo[k] = inl ? G.lo[k][i] : 0.0;
-      r.up[k] = inu ? G.lo[k][i - o] : 0.0;
+      r.lo[k] = inl ? G.lo[k][i] : S(0);
+      r.up[k] = inu ? G.lo[k][i - o] : S(0);
       if (inl) r.mlo |= 1u << k;
       if (inu) r.mup |= 1u << k;
       if constexpr (WN) {
-        r.wlo[k] = inl ? G.w[i + o] : 0.0;
-        r.wup[k] = inu ? G.w[i - o] : 0.0;
+        r.wlo[k] = inl ? G.w[i + o] : S(0);
+        r.wup[k] = inu ? G.w[i - o] : S(0);
       }
     });
     return r;
   }
   template <bool WN, class X>
-  __device__ __forceinline__ double ax_row(const GRow<NOFF, WN> &r, const X &x, long i, int, int, int) const {
-    double acc = r.d * x(i, r.w);
+  __device__ __forceinline__ S ax_row(const GRow<S, NOFF, WN> &r, const X &x, long i, int, int, int) const {
+    S acc = r.d * x(i, r.w);
     const int n0 = G.a.n[0], n1 = G.a.n[1];
     g_for<0, NOFF>([&](auto kc) {
       constexpr int k = decltype(kc)::value;
       constexpr int d0 = g_d(ND, NOFF, k, 0), d1 = g_d(ND, NOFF, k, 1), d2 = g_d(ND, NOFF, k, 2);
       const long o = d0 + (long)n0 * (d1 + (long)n1 * d2);
-      double wl = 0.0, wu = 0.0;
+      S wl = 0, wu = 0;
       if constexpr (WN) wl = r.wlo[k], wu = r.wup[k];
       if ((r.mlo >> k) & 1u) acc += r.lo[k] * x(i + o, wl);
       if ((r.mup >> k) & 1u) acc += r.up[k] * x(i - o, wu);
     });
     return acc;
   }
-  __device__ __forceinline__ double w(long i) const { return G.w[i]; }
+  __device__ __forceinline__ S w(long i) const { return G.w[i]; }
   __device__ __forceinline__ void split(long i, int &i0, int &i1, int &i2) const { mg_split<ND>(G.a, i, i0, i1, i2); }
 };
 // GTailOp: the tail, where the level stays in global memory (g_ax_rt) and only its geometry is copied into registers
+template <class S>
 struct GTailOp {
-  using Level = GLevel;
-  const GLevel &G;
-  const MgLevelArg L;
-  __device__ __forceinline__ explicit GTailOp(const GLevel &g) : G(g), L(g.a) {}
-  __device__ __forceinline__ const MgLevelArg &geo() const { return L; }
+  using Scalar = S;
+  using Level = GLevelT<S>;
+  const Level &G;
+  const MgLevelArgT<S> L;
+  __device__ __forceinline__ explicit GTailOp(const Level &g) : G(g), L(g.a) {}
+  __device__ __forceinline__ const MgLevelArgT<S> &geo() const { return L; }
   template <class X>
-  __device__ __forceinline__ double ax(const X &x, long i, int i0, int i1, int i2) const {
+  __device__ __forceinline__ S ax(const X &x, long i, int i0, int i1, int i2) const {
     return g_ax_rt(G, x, (int)i, i0, i1, i2);
   }
-  __device__ __forceinline__ double w(long i) const { return G.w[i]; }
+  __device__ __forceinline__ S w(long i) const { return G.w[i]; }
   __device__ __forceinline__ void split(long i, int &i0, int &i1, int &i2) const { mg_split(L, i, i0, i1, i2); }
 };
 // omega / diagonal as mg_scale_kernel takes it
+template <class S>
 struct GW {
-  const double *__restrict__ w;
-  __device__ __forceinline__ double operator()(long i) const { return w[i]; }
+  using Scalar = S;
+  const S *__restrict__ w;
+  __device__ __forceinline__ S operator()(long i) const { return w[i]; }
 };
+
+// precision='single' (section 9g): the level's arrays -- the diagonal, omega / diagonal, then the lower arrays, `total`
+// numbers of which the first `nchk` are the two that must be positive -- rounded once to float, round to nearest.  *flag
+// is set when a diagonal or an omega / diagonal is not a normal positive float afterwards (it overflowed, or fell below
+// FLT_MIN), or a coupling is not finite.
+__global__ __launch_bounds__(256) void mg_round_kernel(long total, long nchk, const double *__restrict__ src,
+                                                       float *__restrict__ dst, int *__restrict__ flag) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const float v = (float)src[i];
+  dst[i] = v;
+  const bool ok = i < nchk ? (v >= FLT_MIN && v <= FLT_MAX) : (fabsf(v) <= FLT_MAX);
+  if (!ok) *flag = 1;
+}
 
 // ------------------------------------------------------------------ creation: extraction and the Galerkin product
 

@@ -53,6 +53,9 @@ def _matmat(fn, h, shape, X, Y):
         Y[...] = yb
 
 
+PSP_MG_GALERKIN, PSP_MG_SINGLE = 1, 2  # psp_mg_create_*_ex flags (pysparse_hip.h)
+
+
 class DeviceBuffer:
     """n doubles (or raw bytes) of HBM."""
 
@@ -557,7 +560,10 @@ class DeviceMultigrid:
     """precon.multigrid(A, grid, omega=0.8, steps=2, galerkin=False): a matrix-free geometric V-cycle for the
     constant-coefficient grid operators A = sum_a c_a T_a + s I (psp_mg.hip; no reference analogue).  `levels` are the
     level grids, finest first.  galerkin=True: the same cycle for any symmetric 3- / 5- / 7-point operator on the grid
-    (varying coefficients) with stored level operators A_{l+1} = R A_l P."""
+    (varying coefficients) with stored level operators A_{l+1} = R A_l P.  The subclass
+    DeviceMultigrid32 is the single-precision cycle of either mode."""
+
+    _FLAGS = 0  # ORed into psp_mg_create_*_ex's flags; DeviceMultigrid32 sets PSP_MG_SINGLE
 
     def __init__(self, A, grid, omega=0.8, steps=2, galerkin=False):
         if not isinstance(galerkin, bool):
@@ -589,11 +595,9 @@ class DeviceMultigrid:
             raise ValueError("steps must be >= 1")
         h = C.c_void_p()
         g = (C.c_int * len(dims))(*dims)
-        if galerkin:
-            create = lib().psp_mg_create_csr_galerkin if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss_galerkin
-        else:
-            create = lib().psp_mg_create_csr if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss
-        _check_einval(create(A._h, len(dims), g, omega, steps, C.byref(h)))
+        create = lib().psp_mg_create_csr_ex if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss_ex
+        flags = (PSP_MG_GALERKIN if galerkin else 0) | self._FLAGS
+        _check_einval(create(A._h, len(dims), g, omega, steps, flags, C.byref(h)))
         self._A = A
         self._h = h
         self.shape = (shape[0], shape[0])
@@ -602,14 +606,24 @@ class DeviceMultigrid:
 
     def info(self):
         """levels, first level of the single-workgroup tail launch, kernel launches per application, level dimensions
-        (three per level, 1 on absent axes), and whether the handle stores Galerkin level operators"""
-        nl, tf, la, gk = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        (three per level, 1 on absent axes), whether the handle stores Galerkin level operators, and the precision
+        of the cycle ('double' or 'single')"""
+        nl, tf, la, gk, bits = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
         check(lib().psp_mg_is_galerkin(self._h, C.byref(gk)))
+        check(lib().psp_mg_precision(self._h, C.byref(bits)))
         check(lib().psp_mg_info(self._h, C.byref(nl), C.byref(tf), C.byref(la), None))
         d = (C.c_int * (3 * nl.value))()
         check(lib().psp_mg_info(self._h, None, None, None, d))
         return {"levels": nl.value, "tail_first_level": tf.value, "launches_per_apply": la.value,
-                "dims": tuple(tuple(d[3 * l:3 * l + 3]) for l in range(nl.value)), "galerkin": bool(gk.value)}
+                "dims": tuple(tuple(d[3 * l:3 * l + 3]) for l in range(nl.value)), "galerkin": bool(gk.value),
+                "precision": "single" if bits.value == 32 else "double"}
+
+    def bytes(self):
+        """{"operator", "vector"}: device bytes the handle holds at rest (psp_mg_bytes) -- the level operators with the
+        coarsest inverse and the tail's table, and the level vectors; the block cycle's vectors are block_info()'s"""
+        ob, vb = C.c_longlong(), C.c_longlong()
+        check(lib().psp_mg_bytes(self._h, C.byref(ob), C.byref(vb)))
+        return {"operator": ob.value, "vector": vb.value}
 
     def level_operator(self, level):
         """test hook (galerkin=True): ((d0, d1, d2) per stored array, values[array, point]) of a level's symmetric stencil,
@@ -661,6 +675,13 @@ class DeviceMultigrid:
             self.close()
         except Exception:
             pass
+
+
+class DeviceMultigrid32(DeviceMultigrid):
+    """precon.multigrid(..., precision='single'): DeviceMultigrid's cycle, either mode, evaluated in float32 on level
+    operators rounded once from the double ones.  x and y stay float64; every method is the parent's."""
+
+    _FLAGS = PSP_MG_SINGLE
 
 
 def _solve(fn, A, b, x, tol, maxit, K, hist):

@@ -250,9 +250,10 @@ static PyGetSetDef SSOR_getset[] = {{"shape", (getter)SSOR_get_shape, NULL, "(n,
 
 /* ------------------------------------------------------------------------- multigrid */
 
-/* multigrid(A, grid, omega=0.8, steps=2, galerkin=False): geometric V-cycle for the constant-coefficient grid operators
- * and, with the keyword galerkin=True (a real bool), for any symmetric 3- / 5- / 7-point operator on the grid (psp_mg.hip);
- * no reference analogue */
+/* multigrid(A, grid, omega=0.8, steps=2, galerkin=False, precision='double'): geometric V-cycle for the
+ * constant-coefficient grid operators and, with the keyword galerkin=True (a real bool), for any symmetric 3- / 5- /
+ * 7-point operator on the grid (psp_mg.hip); the keyword precision='single' (a str) selects the cycle evaluated in float32
+ * (DESIGN.md 9g); no reference analogue */
 #define MG_MAX_LEVELS 40
 
 typedef struct {
@@ -267,20 +268,36 @@ typedef struct {
 static PyTypeObject MGType;
 
 static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
-  static char *kwlist[] = {"A", "grid", "omega", "steps", "galerkin", NULL};
-  PyObject *matrix, *grid, *seq, *cap, *galerkin_obj = Py_False;
+  static char *kwlist[] = {"A", "grid", "omega", "steps", "galerkin", "precision", NULL};
+  PyObject *matrix, *grid, *seq, *cap, *galerkin_obj = Py_False, *precision_obj = NULL;
   int galerkin;
+  unsigned flags = 0;
   double omega = 0.8;
   int steps = 2, ndim, a, rc, shape[2], dims[3] = {1, 1, 1};
   int is_csr, is_sss, is_ll;
   long long prod = 1;
   MGObject *op;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|di$O", kwlist, &matrix, &grid, &omega, &steps, &galerkin_obj)) return NULL;
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|di$OO", kwlist, &matrix, &grid, &omega, &steps, &galerkin_obj,
+                                   &precision_obj))
+    return NULL;
   if (!PyBool_Check(galerkin_obj)) {
     PyErr_SetString(PyExc_TypeError, "multigrid() argument 'galerkin' must be a bool");
     return NULL;
   }
   galerkin = galerkin_obj == Py_True;
+  if (galerkin) flags |= PSP_MG_GALERKIN;
+  if (precision_obj != NULL) { /* exactly the str 'double' or 'single' */
+    if (!PyUnicode_Check(precision_obj)) {
+      PyErr_SetString(PyExc_TypeError, "multigrid() argument 'precision' must be a str, 'double' or 'single'");
+      return NULL;
+    }
+    if (PyUnicode_CompareWithASCIIString(precision_obj, "single") == 0)
+      flags |= PSP_MG_SINGLE;
+    else if (PyUnicode_CompareWithASCIIString(precision_obj, "double") != 0) {
+      PyErr_SetString(PyExc_ValueError, "multigrid() argument 'precision' must be 'double' or 'single'");
+      return NULL;
+    }
+  }
   is_csr = PyObject_TypeCheck(matrix, &CSRMatType);
   is_sss = PyObject_TypeCheck(matrix, &SSSMatType);
   is_ll = PyObject_TypeCheck(matrix, &LLMatType);
@@ -350,16 +367,11 @@ static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
   op->dev = NULL;
   op->op = NULL;
   Py_BEGIN_ALLOW_THREADS
-  if (is_sss && galerkin)
-    rc = psp_mg_create_sss_galerkin(((SSSMatObject *)matrix)->dev, ndim, dims, omega, steps, &op->dev);
-  else if (galerkin)
-    rc = psp_mg_create_csr_galerkin(is_csr ? ((CSRMatObject *)matrix)->dev : ((LLMatObject *)matrix)->mirror, ndim, dims,
-                                    omega, steps, &op->dev);
-  else if (is_sss)
-    rc = psp_mg_create_sss(((SSSMatObject *)matrix)->dev, ndim, dims, omega, steps, &op->dev);
+  if (is_sss)
+    rc = psp_mg_create_sss_ex(((SSSMatObject *)matrix)->dev, ndim, dims, omega, steps, flags, &op->dev);
   else
-    rc = psp_mg_create_csr(is_csr ? ((CSRMatObject *)matrix)->dev : ((LLMatObject *)matrix)->mirror, ndim, dims, omega,
-                           steps, &op->dev);
+    rc = psp_mg_create_csr_ex(is_csr ? ((CSRMatObject *)matrix)->dev : ((LLMatObject *)matrix)->mirror, ndim, dims, omega,
+                              steps, flags, &op->dev);
   Py_END_ALLOW_THREADS
   if (rc != PSP_OK) {
     Py_DECREF(op);
@@ -476,6 +488,12 @@ static PyObject *MG_get_galerkin(MGObject *self, void *c) {
   return PyBool_FromLong(g);
 }
 
+static PyObject *MG_get_precision(MGObject *self, void *c) {
+  int bits = 0, rc = psp_mg_precision(self->dev, &bits);
+  if (rc != PSP_OK) return raise_psp(rc);
+  return PyUnicode_FromString(bits == 32 ? "single" : "double");
+}
+
 static PyMethodDef MG_methods[] = {
     {"precon", (PyCFunction)MG_precon, METH_VARARGS,
      "self.precon(x, y)\n\napply preconditioner self on x, store result in y. x is unchanged."},
@@ -487,6 +505,7 @@ static PyMethodDef MG_methods[] = {
 static PyGetSetDef MG_getset[] = {{"shape", (getter)MG_get_shape, NULL, "(n, n)", NULL},
                                   {"levels", (getter)MG_get_levels, NULL, "the level grids, finest first", NULL},
                                   {"galerkin", (getter)MG_get_galerkin, NULL, "stored Galerkin level operators", NULL},
+                                  {"precision", (getter)MG_get_precision, NULL, "'double' or 'single'", NULL},
                                   {"_psp_op", (getter)MG_get_psp_op, NULL, "device operator", NULL},
                                   {NULL, NULL, NULL, NULL, NULL}};
 
@@ -500,14 +519,17 @@ static PyMethodDef precon_methods[] = {
      "omega  relaxation parameter (default value: 1.0)\n"
      "steps  number of SSOR steps"},
     {"multigrid", (PyCFunction)multigrid_prec, METH_VARARGS | METH_KEYWORDS,
-     "multigrid(A, grid, omega=0.8, steps=2, galerkin=False) -- return geometric multigrid preconditioner object\n\n"
+     "multigrid(A, grid, omega=0.8, steps=2, galerkin=False, precision='double') -- return geometric multigrid\n"
+     "preconditioner object\n\n"
      "One V-cycle with damped-Jacobi smoothing for A = sum_a c_a T_a + s I on a grid (no reference analogue).\n\n"
      "A      'csr_mat', 'sss_mat' or 'll_mat': the constant-coefficient [-1 2 -1] stencil on the grid\n"
      "grid   (n0[, n1[, n2]]), prod(grid) == n, row k = i0 + n0*i1 + n0*n1*i2\n"
      "omega  damping of the Jacobi sweeps, 0 < omega <= 1 (default value: 0.8)\n"
      "steps  sweeps before and after the coarse-grid correction (default value: 2)\n"
      "galerkin  keyword, a bool: True takes any symmetric 3- / 5- / 7-point operator on the grid (varying\n"
-     "       coefficients) and stores the level operators R A P (default value: False)"},
+     "       coefficients) and stores the level operators R A P (default value: False)\n"
+     "precision  keyword, a str: 'single' runs the cycle in float32 on level operators rounded once from the\n"
+     "       double ones; x and y stay double arrays, the outer solver is unchanged (default value: 'double')"},
     {NULL, NULL, 0, NULL}};
 
 static struct PyModuleDef precon_module = {PyModuleDef_HEAD_INIT, "precon",

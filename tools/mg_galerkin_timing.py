@@ -15,7 +15,11 @@ a csr_mat:
 
 Every grid runs in a child process of its own under `timeout`; the first child that fails ends the run.
 
+--precision single measures the float32 cycle of DESIGN.md section 9g (device.DeviceMultigrid32) with that section's byte
+model; the default output file then is profiles/mg_galerkin_timing_single.json.
+
     python tools/mg_galerkin_timing.py [--out profiles/mg_galerkin_timing.json] [--quick] [--grids 128^3,256^3]
+                                       [--precision double|single]
 """
 import argparse
 import ctypes as C
@@ -84,21 +88,26 @@ def smooth_operator(grid, seed=0):
     return ind.astype(np.int32), col, val.reshape(n, 2 * nd + 1)[have]
 
 
-def model_bytes(dims, tail_first, steps, nd):
+def model_bytes(dims, tail_first, steps, nd, single=False):
     """bytes one application moves through memory by the kernels' own reads and writes (the neighbours' rows
     of x and of the lower arrays come from the caches).  A level stores C = 1 + lower arrays coefficient arrays (ND + 1 on
     level 0, (3^ND + 1) / 2 below) and w.  Per level above the tail: the first pass (reads b, w and the C arrays, writes x),
     every further sweep (reads x, b, w, C arrays, writes x), the restriction (reads x, b, C arrays, writes b_c), the
     prolongation (reads x and e, writes x); the tail reads its b and writes its x (its coefficient arrays are a few hundred
-    kilobytes that stay in the L2 cache)."""
+    kilobytes that stay in the L2 cache).  single: every array and level vector is 4 B per point; the finest
+    level's b stays the caller's 8 B wherever it is read, and its last sweep writes the caller's 8 B."""
+    e = 4 if single else 8
     total = 0.0
     for l in range(tail_first):
         n, nc = float(np.prod(dims[l])), float(np.prod(dims[l + 1]))
         c = (nd + 1) if l == 0 else (3 ** nd + 1) // 2
-        first = 8 * (3 + c) * n if steps >= 2 else 24 * n
+        eb = 8 if l == 0 else e
+        first = (eb + e * (2 + c)) * n if steps >= 2 else (eb + 2 * e) * n
         sweeps = max(steps - 2, 0) + steps
-        total += first + sweeps * 8 * (4 + c) * n + (8 * (2 + c) * n + 8 * nc) + (16 * n + 8 * nc)
-    return total + 16.0 * float(np.prod(dims[tail_first]))
+        total += first + sweeps * (eb + e * (3 + c)) * n + ((eb + e * (1 + c)) * n + e * nc) + (2 * e * n + e * nc)
+        if l == 0:
+            total += (8 - e) * n
+    return total + (16.0 if tail_first == 0 else 2.0 * e) * float(np.prod(dims[tail_first]))
 
 
 def fill_random(L, check, buf, n, seed=0):
@@ -109,11 +118,13 @@ def fill_random(L, check, buf, n, seed=0):
         check(L.psp_memcpy_h2d(buf.ptr + 8 * k, v.ctypes.data, 8 * v.size))
 
 
-def run_case(name, grid):
+def run_case(name, grid, precision="double"):
     from pysparse_amd import device as dev
     from pysparse_amd._capi import check, lib
     L = lib()
     nd, n = len(grid), int(np.prod(grid))
+    single = precision == "single"
+    Multigrid = dev.DeviceMultigrid32 if single else dev.DeviceMultigrid
     t = time.perf_counter()
     ind, col, val = smooth_operator(grid)
     t_host = time.perf_counter() - t
@@ -121,14 +132,15 @@ def run_case(name, grid):
     del ind, col, val
     check(L.psp_synchronize())
     t = time.perf_counter()
-    K = dev.DeviceMultigrid(A, grid, 0.8, 2, galerkin=True)
+    K = Multigrid(A, grid, 0.8, 2, galerkin=True)
     check(L.psp_synchronize())
     t_create = time.perf_counter() - t
     J = dev.DeviceJacobi(A)
     info = K.info()
     out = {"grid": list(grid), "n": n, "device": dev.device_info()[0], "levels": info["levels"],
            "tail_first_level": info["tail_first_level"], "launches_per_apply": info["launches_per_apply"],
-           "operator": "smooth kappa, seed 0", "host_assembly_seconds": t_host, "handle_creation_seconds": t_create}
+           "operator": "smooth kappa, seed 0", "host_assembly_seconds": t_host, "handle_creation_seconds": t_create,
+           "precision": info["precision"], "bytes": K.bytes()}
     bb, xb = dev.DeviceBuffer(n), dev.DeviceBuffer(n)
     fill_random(L, check, bb, n)
     stream_bytes = max(4096, (8 * n) // 4096 * 4096)
@@ -137,7 +149,7 @@ def run_case(name, grid):
     probe = 3.0 * stream_bytes / avg.value / 1e6
     out["stream_probe_2r1w"] = {"bytes_per_stream": stream_bytes, "avg_ms": avg.value, "min_ms": mn.value, "GBps": probe}
     cyc = cycle_time(L, K, bb, xb)
-    mb = model_bytes(info["dims"], info["tail_first_level"], 2, nd)
+    mb = model_bytes(info["dims"], info["tail_first_level"], 2, nd, single)
     cyc.update({"model_bytes": mb, "model_bytes_per_fine_point": mb / n, "GBps_model": mb / cyc["median_ms"] / 1e6,
                 "fraction_of_stream_probe": mb / cyc["median_ms"] / 1e6 / probe})
     out["vcycle"] = cyc
@@ -178,10 +190,10 @@ def run_case(name, grid):
     del K, J, A, aop, jop, kop
     # the constant-coefficient operator: the Galerkin cycle beside the matrix-free one
     Ac = dev.DeviceCSR.poisson(*grid)
-    Kg = dev.DeviceMultigrid(Ac, grid, 0.8, 2, galerkin=True)
-    Km = dev.DeviceMultigrid(Ac, grid, 0.8, 2)
+    Kg = Multigrid(Ac, grid, 0.8, 2, galerkin=True)
+    Km = Multigrid(Ac, grid, 0.8, 2)
     cg, cm = cycle_time(L, Kg, bb, xb), cycle_time(L, Km, bb, xb)
-    mm = model_bytes_matrix_free(info["dims"], info["tail_first_level"], 2)
+    mm = model_bytes_matrix_free(info["dims"], info["tail_first_level"], 2, single)
     out["constant_coefficients"] = {"galerkin_cycle": cg, "matrix_free_cycle": cm, "matrix_free_model_bytes": mm,
                                     "galerkin_model_bytes": mb, "time_ratio_galerkin_over_matrix_free":
                                         cg["median_ms"] / cm["median_ms"], "byte_ratio": mb / mm}
@@ -190,16 +202,20 @@ def run_case(name, grid):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "mg_galerkin_timing.json"))
+    p.add_argument("--out")
+    p.add_argument("--precision", choices=["double", "single"], default="double")
     p.add_argument("--quick", action="store_true", help="two small grids: a rehearsal of the tool, not a measurement")
     p.add_argument("--grids", help="comma-separated subset of the grids; results are merged into --out")
     p.add_argument("--case", help="(internal) run one grid in this process and print its JSON record")
     a = p.parse_args()
+    if not a.out:
+        a.out = os.path.join(ROOT, "profiles",
+                             "mg_galerkin_timing.json" if a.precision == "double" else "mg_galerkin_timing_single.json")
     cases = QUICK if a.quick else CASES
     if a.case:
-        print("RESULT " + json.dumps(run_case(a.case, cases[a.case][0])), flush=True)
+        print("RESULT " + json.dumps(run_case(a.case, cases[a.case][0], a.precision)), flush=True)
         return 0
-    res = {"quick": a.quick, "cases": {}}
+    res = {"quick": a.quick, "precision": a.precision, "cases": {}}
     if a.grids and os.path.exists(a.out):
         with open(a.out) as f:
             old = json.load(f)
@@ -208,7 +224,8 @@ def main():
     for name, (grid, limit) in cases.items():
         if a.grids and name not in a.grids.split(","):
             continue
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--case", name]
+        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--case", name,
+               "--precision", a.precision]
         if a.quick:
             cmd.append("--quick")
         r = subprocess.run(cmd, capture_output=True, text=True)

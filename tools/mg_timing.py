@@ -14,7 +14,10 @@ Per grid (256^3, 512^3, 4096^2, and 128^3 for the tail's share), on the Poisson 
 
 Every grid runs in a child process of its own under `timeout`; the first child that fails ends the run.
 
-    python tools/mg_timing.py [--out profiles/mg_timing.json] [--quick]
+--precision single measures the float32 cycle of DESIGN.md section 9g (device.DeviceMultigrid32) with that section's byte
+model; the default output file then is profiles/mg_timing_single.json.
+
+    python tools/mg_timing.py [--out profiles/mg_timing.json] [--quick] [--precision double|single]
 """
 import argparse
 import ctypes as C
@@ -35,16 +38,22 @@ CASES = {"128^3": ((128, 128, 128), 300), "256^3": ((256, 256, 256), 400), "512^
 QUICK = {"32^3": ((32, 32, 32), 120), "96^2": ((96, 96), 120)}
 
 
-def model_bytes(dims, tail_first, steps):
+def model_bytes(dims, tail_first, steps, single=False):
     """bytes one application moves through memory by the kernels' own reads and writes (neighbours come from the caches):
     per level above the tail the pre-smoothing (first pass: read b, write x; 24 B per point and further sweep), the
     restriction (read x and b, write b_c), the prolongation (read x and e, write x) and `steps` sweeps of 24 B; the tail reads
-    its b and writes its x once"""
+    its b and writes its x once.  single: every level vector is 4 B per point; the finest level's b stays
+    the caller's 8 B wherever it is read, and its last sweep writes the caller's 8 B"""
+    e = 4 if single else 8
     total = 0.0
     for l in range(tail_first):
         n, nc = float(np.prod(dims[l])), float(np.prod(dims[l + 1]))
-        total += n * (16 + 24 * max(steps - 2, 0)) + (16 * n + 8 * nc) + (16 * n + 8 * nc) + 24 * steps * n
-    return total + 16.0 * float(np.prod(dims[tail_first]))
+        eb = 8 if l == 0 else e
+        sweep = 2 * e + eb
+        total += n * ((eb + e) + sweep * max(steps - 2, 0)) + ((e + eb) * n + e * nc) + (2 * e * n + e * nc) + sweep * steps * n
+        if l == 0:
+            total += (8 - e) * n
+    return total + (16.0 if tail_first == 0 else 2.0 * e) * float(np.prod(dims[tail_first]))
 
 
 def window_ms(L, ev, fn, reps):
@@ -77,17 +86,20 @@ def cycle_time(L, K, xb, yb, min_total_s=0.5, windows=5):
             "windows": windows}
 
 
-def run_case(name, grid):
+def run_case(name, grid, precision="double"):
     from pysparse_amd import device as dev
     from pysparse_amd._capi import check, lib
     L = lib()
     n = int(np.prod(grid))
+    single = precision == "single"
+    Multigrid = dev.DeviceMultigrid32 if single else dev.DeviceMultigrid
     A = dev.DeviceCSR.poisson_big(*grid)
-    K = dev.DeviceMultigrid(A, grid, 0.8, 2)
+    K = Multigrid(A, grid, 0.8, 2)
     J = dev.DeviceJacobi(A)
     info = K.info()
     out = {"grid": list(grid), "n": n, "device": dev.device_info()[0], "levels": info["levels"],
-           "tail_first_level": info["tail_first_level"], "launches_per_apply": info["launches_per_apply"]}
+           "tail_first_level": info["tail_first_level"], "launches_per_apply": info["launches_per_apply"],
+           "precision": info["precision"], "bytes": K.bytes()}
     bb, xb = dev.DeviceBuffer(n), dev.DeviceBuffer(n)
     g = np.random.default_rng(0)
     chunk = 1 << 24
@@ -101,7 +113,7 @@ def run_case(name, grid):
     probe = 3.0 * stream_bytes / avg.value / 1e6
     out["stream_probe_2r1w"] = {"bytes_per_stream": stream_bytes, "avg_ms": avg.value, "min_ms": mn.value, "GBps": probe}
     cyc = cycle_time(L, K, bb, xb)
-    mb = model_bytes(info["dims"], info["tail_first_level"], 2)
+    mb = model_bytes(info["dims"], info["tail_first_level"], 2, single)
     cyc.update({"model_bytes": mb, "model_bytes_per_fine_point": mb / n, "GBps_model": mb / cyc["median_ms"] / 1e6,
                 "fraction_of_stream_probe": mb / cyc["median_ms"] / 1e6 / probe})
     out["vcycle"] = cyc
@@ -112,7 +124,7 @@ def run_case(name, grid):
         nt = int(np.prod(tgrid))
         At = dev.DeviceCSR.poisson_big(*tgrid) if len(tgrid) > 1 else None
         if At is not None:
-            Kt = dev.DeviceMultigrid(At, tgrid, 0.8, 2)
+            Kt = Multigrid(At, tgrid, 0.8, 2)
             tb, tx = dev.DeviceBuffer.from_host(np.ones(nt)), dev.DeviceBuffer(nt)
             tail = cycle_time(L, Kt, tb, tx, min_total_s=0.2)
             tail["grid"] = list(tgrid)
@@ -154,17 +166,21 @@ def run_case(name, grid):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "mg_timing.json"))
+    p.add_argument("--out")
+    p.add_argument("--precision", choices=["double", "single"], default="double")
     p.add_argument("--quick", action="store_true", help="two small grids: a rehearsal of the tool, not a measurement")
     p.add_argument("--case", help="(internal) run one grid in this process and print its JSON record")
     a = p.parse_args()
+    if not a.out:
+        a.out = os.path.join(ROOT, "profiles", "mg_timing.json" if a.precision == "double" else "mg_timing_single.json")
     cases = QUICK if a.quick else CASES
     if a.case:
-        print("RESULT " + json.dumps(run_case(a.case, cases[a.case][0])), flush=True)
+        print("RESULT " + json.dumps(run_case(a.case, cases[a.case][0], a.precision)), flush=True)
         return 0
-    res = {"quick": a.quick, "cases": {}}
+    res = {"quick": a.quick, "precision": a.precision, "cases": {}}
     for name, (grid, limit) in cases.items():
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--case", name]
+        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--case", name,
+               "--precision", a.precision]
         if a.quick:
             cmd.append("--quick")
         r = subprocess.run(cmd, capture_output=True, text=True)
