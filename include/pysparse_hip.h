@@ -449,6 +449,26 @@ int psp_mg_precision(const psp_mg_t *K, int *bits);
  * psp_mg_level_operator on a single-precision handle returns the stored floats widened to double. */
 int psp_mg_bytes(const psp_mg_t *K, long long *operator_bytes, long long *vector_bytes);
 
+/* precon.multigrid(A, grid, omega, steps, galerkin=True, line=a): the Galerkin cycle with a line smoother, for grids
+ * whose cells are graded or stretched along axis a.  The accepted operators, the checking pass and its
+ * refusals are psp_mg_create_*_galerkin's.  Axis a is never coarsened; every other axis is halved while it has at least 2
+ * points (n' = n / 2; 3 -> 1 and 2 -> 1 included), so that the last level is the single line (1, .., n_a, .., 1).  The
+ * smoother is x += omega T_l^-1 (b - A_l x) with T_l the diagonal of A_l and its entries at offset -+stride_a: one
+ * tridiagonal solve per grid line, factorised once per level at creation (p_0 = d_0, p_i = d_i - l_i (l_i / p_{i-1}); 1 / p
+ * is stored where the point smoother stores omega / diagonal).  The last level is solved exactly by one such solve.  There
+ * is no tail kernel and no dense inverse: psp_mg_info reports tail_first_level == levels and
+ * launches_per_apply = (levels - 1)(2 steps + 2) + 1.  Symmetric positive definite for 0 < omega <= 1; no atomics, the
+ * same bits from call to call, from csr and sss handles and from host and device entry points.
+ * PSP_EINVAL (before any device call) for ndim == 1, line_axis outside 0 .. ndim - 1 and a line axis of fewer than 2
+ * points; PSP_ESINGULAR when a pivot p_i is not finite and > 0.  There is no single-precision form.  The handle is used
+ * like any other (psp_mg_precon*, psp_op_from_mg, psp_mg_level_operator, _bytes, _info, _destroy); psp_mg_precon_block*
+ * applies the single cycle column by column (column c has the bits of psp_mg_precon, psp_mg_block_info reports 0
+ * columns and psp_mg_block_reserve does nothing). */
+int psp_mg_create_csr_line(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, int line_axis, psp_mg_t **out);
+int psp_mg_create_sss_line(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, int line_axis, psp_mg_t **out);
+/* the line axis of a handle created by psp_mg_create_*_line, -1 for every other handle */
+int psp_mg_line_axis(const psp_mg_t *K, int *axis);
+
 /* --------------------------------------------------------- operator protocol */
 
 /* Host callback operator: the C image of SpMatrix_Matvec / SpMatrix_Precon

@@ -24,6 +24,12 @@
 // split -- MfOp here (c_a and d are kernel arguments), GOp / GTailOp in psp_mg_galerkin.h (stored arrays), which this
 // file includes and which holds what only the stored mode has; its creation is below, next to the matrix-free one.
 //
+// line = a (psp_mg_create_*_line; psp_mg_line.h) is the stored mode with a line smoother for grids
+// graded or stretched along axis a: that axis is never coarsened, every other one is halved down to a single point, a
+// sweep is x <- x + omega T_l^-1 (b - A_l x) with T_l the tridiagonal part of A_l along the grid lines of axis a (one
+// thread per line, factorised at creation), and the last level, a single line, is solved exactly.  The schedule, the
+// restriction and the prolongation are the ones below; there is no tail launch and no dense inverse.
+//
 // Blocks of k vectors (psp_mg_precon_block): block forms of the five cycle kernels, one thread per
 // point and up to KC columns, the row's coefficients loaded once per point (Op::load_row / ax_row); the same schedule, the
 // same launches whatever k is, column c with the bits of the single cycle on column c.
@@ -662,6 +668,7 @@ __global__ __launch_bounds__(256) void mg_check_w4_kernel(int n, MgStencil S, Mg
 }  // namespace
 
 #include "psp_mg_galerkin.h"
+#include "psp_mg_line.h"
 
 // ====================================================================== the handle
 
@@ -693,6 +700,12 @@ struct psp_mg {
   std::vector<double *> coef;
   std::vector<float *> coef32;
   size_t op_bytes = 0, vec_bytes = 0;  // what the handle holds at rest (psp_mg_bytes)
+  // line = a (psp_mg_line.h; section 9h): the axis that is solved exactly and never coarsened, -1 without.  Per level the
+  // geometry of its grid lines and the lower array of offset -st_a; the level's second array holds q, not omega / diagonal.
+  // Every level is launches: `tail_first` is the last level, which the schedule's tail step solves as the one line it is.
+  int line_axis = -1;
+  std::vector<MgLine> lines;
+  std::vector<const double *> line_lo;
   // the level vectors of the block cycle (section 9e): per level what `lev` holds, for blk_cols columns of leading
   // dimension N, and a spare for the finest level; allocated by the first block call, grown on demand
   struct BlockLevel {
@@ -934,7 +947,7 @@ int mg_check_args(const psp_csr *A, int ndim, const int *grid, double omega, int
 
 // the geometry of the cycle, the same in both modes: the level grids (n, co, nc, rs, N of every level; c, d, w are left
 // 0), the first level of the tail and the launches of one application
-int mg_level_grids(psp_mg *K, const int n[3], int steps) {
+int mg_level_grids(psp_mg *K, const int n[3], int steps, int line = -1) {
   int cur[3] = {n[0], n[1], n[2]};
   for (;;) {
     psp_mg::Level L;
@@ -943,7 +956,7 @@ int mg_level_grids(psp_mg *K, const int n[3], int steps) {
     int coarsened = 0;
     for (int a = 0; a < 3; ++a) {
       L.a.n[a] = cur[a];
-      L.a.co[a] = cur[a] >= 4;
+      L.a.co[a] = line < 0 ? cur[a] >= 4 : (a != line && cur[a] >= 2);  // section 9h: 3 -> 1 and 2 -> 1 included
       L.a.nc[a] = L.a.co[a] ? cur[a] / 2 : cur[a];
       coarsened += L.a.co[a];
     }
@@ -956,6 +969,13 @@ int mg_level_grids(psp_mg *K, const int n[3], int steps) {
   }
   const int nl = (int)K->lev.size();
   K->tail_first = nl - 1;
+  if (line >= 0) {
+    // no tail kernel: per level above the last `steps` sweeps, the restriction, the prolongation and `steps` sweeps; one
+    // solve of the last level, which is a single line
+    K->launches = (nl - 1) * (2 * steps + 2) + 1;
+    if (nl > kMaxLevels) return fail(PSP_EINVAL, "multigrid: too many levels");
+    return PSP_OK;
+  }
   while (K->tail_first > 0 && K->lev[K->tail_first - 1].N <= kTailT) --K->tail_first;
   // launches of one application: per large level the pre-smoothing (the first two sweeps are one pass), the restriction,
   // the prolongation and the post-smoothing; one for the tail
@@ -1187,13 +1207,43 @@ void g_release_double(psp_mg *K, int l) {
   for (int k = 0; k < kGMaxOff; ++k) G.lo[k] = nullptr;
 }
 
+// line = a (section 9h): the grid lines of every level and the factorisation of its line operator, q over omega / diagonal
+// (which nothing of this mode reads); *flag is the Galerkin chain's, where the factorisation adds bit 1
+int g_build_lines(psp_mg *K, int *flag) {
+  const int nl = (int)K->lev.size(), a = K->line_axis, au = a == 0 ? 1 : 0, av = a == 2 ? 1 : 2;
+  K->lines.resize(nl);
+  K->line_lo.resize(nl);
+  for (int l = 0; l < nl; ++l) {
+    const GLevel &G = K->glev[l];
+    const long st[3] = {1, G.a.n[0], (long)G.a.n[0] * G.a.n[1]};
+    MgLine &g = K->lines[l];
+    g.n = G.a.n[a], g.nu = G.a.n[au], g.nv = G.a.n[av];
+    g.a = a, g.au = au, g.av = av;
+    g.st = st[a], g.su = st[au], g.sv = st[av];
+    const int slot = g_slot(G.nd, G.noff, a == 0 ? -1 : 0, a == 1 ? -1 : 0, a == 2 ? -1 : 0);
+    if (slot < 0) return g_bad_shape(G.nd, G.noff);
+    K->line_lo[l] = G.lo[slot];
+    const long lines = (long)g.nu * g.nv;
+    hipLaunchKernelGGL(mg_line_factor_kernel, dim3((unsigned)((lines + kLineThreads - 1) / kLineThreads)), dim3(kLineThreads), 0,
+                       stream(), g, G.diag, K->line_lo[l], const_cast<double *>(G.w), flag);
+    PSP_LAUNCH_CHECK();
+  }
+  int bad = 0;
+  PSP_TRY(read_flag(flag, &bad));
+  if (bad & 1) return fail(PSP_ESINGULAR, "multigrid(galerkin=True): a level operator's diagonal is not finite and > 0");
+  if (bad & 2)
+    return fail(PSP_ESINGULAR, "multigrid(line=%d): a pivot of a level's line operator is not finite and > 0 (the matrix is not "
+                "positive definite along the lines of axis %d)", a, a);
+  return PSP_OK;
+}
+
 // mg_create_galerkin's part of mg_make; flags: three ints on the device (the extraction's, the Galerkin product's, the
 // rounding's)
 int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
   const double omega = K->omega;
   const bool single = K->single;
   const int nd = n[2] > 1 ? 3 : n[1] > 1 ? 2 : 1;
-  PSP_TRY(mg_level_grids(K, n, K->steps));  // section 9c's
+  PSP_TRY(mg_level_grids(K, n, K->steps, K->line_axis));  // section 9c's, or with a line axis section 9h's
   const int nl = (int)K->lev.size();
   // the level vectors and the level operators' arrays (a single-precision handle allocates a level's double arrays only
   // when it builds the level)
@@ -1240,6 +1290,7 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
       g_release_double(K, l);
     }
   }
+  if (K->line_axis >= 0) return g_build_lines(K, flags + 1);
   // the coarsest level: downloaded and inverted on the host (in double in either precision)
   const GLevel &C = K->glev[nl - 1];
   const int m = (int)K->lev[nl - 1].N;
@@ -1259,17 +1310,32 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
   return mg_upload_tail(K, inv, [&](int l) { return K->glev[l]; });
 }
 
-int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, psp_mg **out) {
+// line: -1, or the axis of the line smoother (section 9h), which has no single-precision form
+int mg_create_galerkin_line(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, int line,
+                            psp_mg **out) {
   int n[3];
   PSP_TRY(mg_check_args(A, ndim, grid, omega, steps, out, n));
+  if (line != -1) {
+    if (ndim < 2) return fail(PSP_EINVAL, "multigrid(line=%d): a grid of one axis has no axis left to coarsen", line);
+    if (line < 0 || line >= ndim) return fail(PSP_EINVAL, "multigrid(line=%d): the grid has the axes 0 .. %d", line, ndim - 1);
+    if (n[line] < 2) return fail(PSP_EINVAL, "multigrid(line=%d): the line axis has %d point, at least 2 are needed", line, n[line]);
+    if (single) return fail(PSP_EINVAL, "multigrid(line=%d): the line smoother has no single-precision form", line);
+  }
   if (!(A->ind && A->col && A->val) || A->w4_only)
     return fail(PSP_EINVAL, "multigrid(galerkin=True): the handle no longer holds its index arrays on the device");
   PSP_TRY(ensure_device());
   int *flags = nullptr;
   PSP_HIP(hipMalloc((void **)&flags, 3 * sizeof(int)));
-  const int rc = mg_make(A, ndim, omega, steps, true, single, out, [&](psp_mg *K) { return g_build(K, A, n, flags); });
+  const int rc = mg_make(A, ndim, omega, steps, true, single, out, [&](psp_mg *K) {
+    K->line_axis = line;
+    return g_build(K, A, n, flags);
+  });
   (void)hipFree(flags);
   return rc;
+}
+
+int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, psp_mg **out) {
+  return mg_create_galerkin_line(A, ndim, grid, omega, steps, single, -1, out);
 }
 
 // A vector of the cycle: the handle's scalar type, or (wide) the caller's doubles, which only the finest level of a
@@ -1364,7 +1430,24 @@ struct LevelOps {
     }
     return PSP_OK;
   }
+  // line = a (section 9h): one line sweep of level l, xout = xin + omega T^-1 (b - A xin); FROM0: from xin = 0
+  template <bool FROM0>
+  int line_sweep(int l, double omega, Vec xin, Vec b, Vec xout) const {
+    if constexpr (std::is_same_v<S, double>) {
+      const GLevel &G = K->glev[l];
+      const MgLine &g = K->lines[l];
+      const long lines = (long)g.nu * g.nv;
+      return g_dispatch(G, [&](auto sh) {
+        hipLaunchKernelGGL((mg_line_sweep_kernel<GOp<sh.nd, sh.noff, double>, FROM0>),
+                           dim3((unsigned)((lines + kLineThreads - 1) / kLineThreads)), dim3(kLineThreads), 0, stream(), G, g,
+                           omega, K->line_lo[l], xin.as<const double>(), b.as<const double>(), xout.as<double>());
+      });
+    } else {
+      return fail(PSP_EINVAL, "multigrid: internal error (a single-precision handle with a line axis)");
+    }
+  }
   int first(int l, Vec b, Vec dst) const {
+    if (K->line_axis >= 0) return line_sweep<true>(l, K->omega, Vec(), b, dst);
     if (K->steps > 1) return smooth<true>(l, Vec(), b, dst);
     const long N = K->lev[l].N;
     const dim3 g((unsigned)((N + 255) / 256)), t(256);
@@ -1377,7 +1460,10 @@ struct LevelOps {
     });
     return PSP_OK;
   }
-  int sweep(int l, Vec xin, Vec b, Vec xout) const { return smooth<false>(l, xin, b, xout); }
+  int sweep(int l, Vec xin, Vec b, Vec xout) const {
+    if (K->line_axis >= 0) return line_sweep<false>(l, K->omega, xin, b, xout);
+    return smooth<false>(l, xin, b, xout);
+  }
   template <class Op>
   void launch_restrict(const typename Op::Level &A, Vec x, Vec b, Vec bc) const {
     int tile[3];
@@ -1397,8 +1483,13 @@ struct LevelOps {
     launch_restrict<MfOp<3, S>>(mf_level<S>(K, l), x, b, bc);
     return PSP_OK;
   }
-  // the tail's ends are both the caller's (the whole grid is the tail) or both the handle's
+  // the tail's ends are both the caller's (the whole grid is the tail) or both the handle's.  With a line axis the step
+  // is the last level's x = T^-1 b: that level is one line and A = T there (section 9h)
   void tail(Vec b, Vec x) const {
+    if (K->line_axis >= 0) {
+      (void)line_sweep<true>(K->tail_first, 1.0, Vec(), b, x);
+      return;
+    }
     mg_with_io<S>(b, x, [&](auto *bp, auto *xp) {
       using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
       using TX = std::remove_pointer_t<decltype(xp)>;
@@ -1560,14 +1651,14 @@ struct BlockOps {
 };
 
 // the sss entry points: an sss_mat is read through its full device mirror
-int mg_create_sss(psp_sss_t *A, const char *fn, int (*create)(psp_csr *, int, const int *, double, int, bool, psp_mg **),
-                  int ndim, const int *grid, double omega, int steps, bool single, psp_mg **out) {
+template <class Create>  // create(the mirror)
+int mg_create_sss(psp_sss_t *A, const char *fn, Create &&create) {
   PSP_API_GUARD_H(A, A ? A->full : nullptr);
   if (!A) return fail(PSP_EINVAL, "%s: NULL argument", fn);
   if (A->host || cpu_mode())
     return fail(PSP_ENODEV, "precon.multigrid: not available with PSP_DEVICE=cpu (host mode covers csr / sss / jacobi / pcg / minres)");
   if (!A->full) return fail(PSP_EINVAL, "%s: the matrix has no device mirror", fn);
-  return create(A->full, ndim, grid, omega, steps, single, out);
+  return create(A->full);
 }
 
 // one V-cycle: the schedule of launches and buffers, the same in both modes, both precisions and for one vector or a block
@@ -1585,10 +1676,12 @@ int mg_schedule(psp_mg *K, typename Ops::Vec b_dev, typename Ops::Vec y_dev, con
     const V b = l == 0 ? b_dev : ops.lb(l);
     const V own = l == 0 && !own0 ? y_dev : ops.lx(l);
     // the finest level's last sweep must land in y: its writes are the pre-smoothing launches and `steps` more
-    const int writes = (steps >= 2 ? steps - 1 : 1) + steps;
+    // (a line sweep is a launch of its own each: the first two are not one pass)
+    const int pre = K->line_axis >= 0 ? steps : steps >= 2 ? steps - 1 : 1;
+    const int writes = pre + steps;
     V dst = (l == 0 && !own0 && (writes & 1) == 0) ? ops.lt(l) : own;
     PSP_TRY(ops.first(l, b, dst));
-    for (int k = 2; k < steps; ++k) {
+    for (int k = 1; k < pre; ++k) {
       V nxt = dst == own ? ops.lt(l) : own;
       PSP_TRY(ops.sweep(l, dst, b, nxt));
       dst = nxt;
@@ -1639,7 +1732,7 @@ int mg_block_reserve(psp_mg *K, int k) {
     mg_block_free(K);
     return PSP_OK;
   }
-  if (k <= K->blk_cols) return PSP_OK;
+  if (k <= K->blk_cols || K->line_axis >= 0) return PSP_OK;  // a line handle has no block vectors to reserve
   mg_block_free(K);
   K->blk.resize(K->lev.size());
   for (int l = 0; l <= K->tail_first; ++l) {
@@ -1677,6 +1770,13 @@ int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
 // the bits of mg_apply_dev on the column, K's launches whatever k is.  Y must not overlap X.  The handle is locked by the
 // caller.
 int mg_apply_block_dev(psp_mg *K, int k, const double *X, long ldx, double *Y, long ldy, const int *frozen) {
+  if (K->line_axis >= 0) {
+    // the line kernels have no block form (section 9h): the single cycle column by column, no block vectors.  The frozen
+    // flags live on the device, so a caller that has some goes column by column itself (mg_block_routed is false).
+    if (frozen) return fail(PSP_EINVAL, "multigrid: internal error (a block cycle with frozen columns on a line handle)");
+    for (int c = 0; c < k; ++c) PSP_TRY(mg_apply_dev(K, X + (size_t)c * ldx, Y + (size_t)c * ldy));
+    return PSP_OK;
+  }
   PSP_TRY(mg_block_reserve(K, k));
   const MVec x{const_cast<double *>(X), ldx, true}, y{Y, ldy, true};
   if (K->single) return mg_schedule(K, x, y, BlockOps<float>(K, k, frozen));
@@ -1687,7 +1787,10 @@ int mg_launches(const psp_mg *K) { return K->launches; }
 
 // Where op_apply_block and the batched PCG loop run the block cycle and where they keep the column-by-column path: by the
 // measurements of DESIGN.md section 9e (profiles/mg_block_timing.json).
-bool mg_block_routed(const psp_mg *K) { return K->galerkin ? kRouteBlockGalerkin : kRouteBlockMatrixFree; }
+bool mg_block_routed(const psp_mg *K) {
+  if (K->line_axis >= 0) return false;
+  return K->galerkin ? kRouteBlockGalerkin : kRouteBlockMatrixFree;
+}
 
 }  // namespace psp
 
@@ -1705,8 +1808,29 @@ int psp_mg_create_sss_ex(psp_sss_t *A, int ndim, const int *grid, double omega, 
   if (flags & ~(unsigned)(PSP_MG_GALERKIN | PSP_MG_SINGLE)) return fail(PSP_EINVAL, "psp_mg_create_sss_ex: unknown flags 0x%x", flags);
   const bool single = (flags & PSP_MG_SINGLE) != 0;
   if (flags & PSP_MG_GALERKIN)
-    return mg_create_sss(A, "psp_mg_create_sss_galerkin", mg_create_galerkin, ndim, grid, omega, steps, single, out);
-  return mg_create_sss(A, "psp_mg_create_sss", mg_create, ndim, grid, omega, steps, single, out);
+    return mg_create_sss(A, "psp_mg_create_sss_galerkin",
+                         [&](psp_csr *F) { return mg_create_galerkin(F, ndim, grid, omega, steps, single, out); });
+  return mg_create_sss(A, "psp_mg_create_sss", [&](psp_csr *F) { return mg_create(F, ndim, grid, omega, steps, single, out); });
+}
+
+// galerkin=True with the line smoother along line_axis (section 9h).  Calls of their own: the flags of psp_mg_create_*_ex
+// stay what they are.
+int psp_mg_create_csr_line(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, int line_axis, psp_mg_t **out) {
+  PSP_API_GUARD_H(A);
+  if (line_axis < 0) return fail(PSP_EINVAL, "multigrid(line=%d): the line axis must be one of the grid's axes, 0 .. ndim - 1", line_axis);
+  return mg_create_galerkin_line(A, ndim, grid, omega, steps, false, line_axis, out);
+}
+
+int psp_mg_create_sss_line(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, int line_axis, psp_mg_t **out) {
+  if (line_axis < 0) return fail(PSP_EINVAL, "multigrid(line=%d): the line axis must be one of the grid's axes, 0 .. ndim - 1", line_axis);
+  return mg_create_sss(A, "psp_mg_create_sss_line",
+                       [&](psp_csr *F) { return mg_create_galerkin_line(F, ndim, grid, omega, steps, false, line_axis, out); });
+}
+
+int psp_mg_line_axis(const psp_mg_t *K, int *axis) {
+  if (!K || !axis) return fail(PSP_EINVAL, "psp_mg_line_axis: NULL argument");
+  *axis = K->line_axis;
+  return PSP_OK;
 }
 
 int psp_mg_create_csr(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, psp_mg_t **out) {
@@ -1796,7 +1920,8 @@ int psp_mg_destroy(psp_mg_t *K) {
 int psp_mg_info(const psp_mg_t *K, int *levels, int *tail_first_level, int *launches_per_apply, int *dims) {
   if (!K) return fail(PSP_EINVAL, "psp_mg_info: NULL handle");
   if (levels) *levels = (int)K->lev.size();
-  if (tail_first_level) *tail_first_level = K->tail_first;
+  // a line handle has no tail launch: its last level is one more ordinary launch
+  if (tail_first_level) *tail_first_level = K->line_axis >= 0 ? (int)K->lev.size() : K->tail_first;
   if (launches_per_apply) *launches_per_apply = K->launches;
   if (dims)
     for (size_t l = 0; l < K->lev.size(); ++l)

@@ -135,6 +135,7 @@ template <int ND, int NOFF, class S>
 struct GOp {
   using Scalar = S;
   static constexpr bool kFinest = NOFF == ND;  // level 0 stores the axis offsets only (in 1-D every level does)
+  static constexpr int kNoff = NOFF;
   using Level = GLevelT<S>;
   const Level &G;
   __device__ __forceinline__ explicit GOp(const Level &g) : G(g) {}

@@ -566,8 +566,14 @@ class DeviceMultigrid:
     _FLAGS = 0  # ORed into psp_mg_create_*_ex's flags; DeviceMultigrid32 sets PSP_MG_SINGLE
 
     def __init__(self, A, grid, omega=0.8, steps=2, galerkin=False):
+        self._create(A, grid, omega, steps, galerkin, None)
+
+    def _create(self, A, grid, omega, steps, galerkin, line):
+        """every check, then the handle; line: None, or the axis of DeviceMultigridLine"""
         if not isinstance(galerkin, bool):
             raise TypeError("galerkin must be a bool")
+        if line is not None and (isinstance(line, bool) or not isinstance(line, int)):
+            raise TypeError("line must be None or an int, the axis of the line smoother")
         if not isinstance(A, (DeviceCSR, DeviceSSS)):
             raise TypeError("multigrid() argument 1 must be a csr_mat or sss_mat handle")
         if isinstance(grid, (str, bytes)) or not hasattr(grid, "__len__") or not hasattr(grid, "__getitem__"):
@@ -593,11 +599,26 @@ class DeviceMultigrid:
             raise ValueError("omega must satisfy 0 < omega <= 1")
         if steps < 1:
             raise ValueError("steps must be >= 1")
+        if line is not None:
+            if not galerkin:
+                raise ValueError("line needs galerkin=True: the line smoother works on stored level operators")
+            if self._FLAGS & PSP_MG_SINGLE:
+                raise ValueError("line with precision='single': the line smoother has no single-precision form")
+            if len(dims) < 2:
+                raise ValueError("line on a grid of one axis: there is no axis left to coarsen")
+            if not 0 <= line < len(dims):
+                raise ValueError("line must be one of the grid's axes, 0 .. %d" % (len(dims) - 1))
+            if dims[line] < 2:
+                raise ValueError("the line axis must have at least 2 points")
         h = C.c_void_p()
         g = (C.c_int * len(dims))(*dims)
-        create = lib().psp_mg_create_csr_ex if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss_ex
-        flags = (PSP_MG_GALERKIN if galerkin else 0) | self._FLAGS
-        _check_einval(create(A._h, len(dims), g, omega, steps, flags, C.byref(h)))
+        if line is not None:
+            create = lib().psp_mg_create_csr_line if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss_line
+            _check_einval(create(A._h, len(dims), g, omega, steps, line, C.byref(h)))
+        else:
+            create = lib().psp_mg_create_csr_ex if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss_ex
+            flags = (PSP_MG_GALERKIN if galerkin else 0) | self._FLAGS
+            _check_einval(create(A._h, len(dims), g, omega, steps, flags, C.byref(h)))
         self._A = A
         self._h = h
         self.shape = (shape[0], shape[0])
@@ -607,16 +628,18 @@ class DeviceMultigrid:
     def info(self):
         """levels, first level of the single-workgroup tail launch, kernel launches per application, level dimensions
         (three per level, 1 on absent axes), whether the handle stores Galerkin level operators, and the precision
-        of the cycle ('double' or 'single')"""
-        nl, tf, la, gk, bits = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        of the cycle ('double' or 'single'), and the axis of the line smoother (None without one; with one there is no
+        tail launch and tail_first_level == levels)"""
+        nl, tf, la, gk, bits, ax = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
         check(lib().psp_mg_is_galerkin(self._h, C.byref(gk)))
         check(lib().psp_mg_precision(self._h, C.byref(bits)))
+        check(lib().psp_mg_line_axis(self._h, C.byref(ax)))
         check(lib().psp_mg_info(self._h, C.byref(nl), C.byref(tf), C.byref(la), None))
         d = (C.c_int * (3 * nl.value))()
         check(lib().psp_mg_info(self._h, None, None, None, d))
         return {"levels": nl.value, "tail_first_level": tf.value, "launches_per_apply": la.value,
                 "dims": tuple(tuple(d[3 * l:3 * l + 3]) for l in range(nl.value)), "galerkin": bool(gk.value),
-                "precision": "single" if bits.value == 32 else "double"}
+                "precision": "single" if bits.value == 32 else "double", "line": ax.value if ax.value >= 0 else None}
 
     def bytes(self):
         """{"operator", "vector"}: device bytes the handle holds at rest (psp_mg_bytes) -- the level operators with the
@@ -682,6 +705,16 @@ class DeviceMultigrid32(DeviceMultigrid):
     operators rounded once from the double ones.  x and y stay float64; every method is the parent's."""
 
     _FLAGS = PSP_MG_SINGLE
+
+
+class DeviceMultigridLine(DeviceMultigrid):
+    """precon.multigrid(..., galerkin=True, line=a): the Galerkin cycle with a line smoother along axis `line`, for grids
+    graded or stretched along that axis (psp_mg_create_*_line).  Axis `line` is never coarsened, the
+    smoother solves the tridiagonal part of every level operator along each of its grid lines exactly.  line=None is
+    DeviceMultigrid.  Every method is the parent's; info()["line"] is the axis."""
+
+    def __init__(self, A, grid, omega=0.8, steps=2, galerkin=True, line=None):
+        self._create(A, grid, omega, steps, galerkin, line)
 
 
 def _solve(fn, A, b, x, tol, maxit, K, hist):

@@ -250,10 +250,11 @@ static PyGetSetDef SSOR_getset[] = {{"shape", (getter)SSOR_get_shape, NULL, "(n,
 
 /* ------------------------------------------------------------------------- multigrid */
 
-/* multigrid(A, grid, omega=0.8, steps=2, galerkin=False, precision='double'): geometric V-cycle for the
+/* multigrid(A, grid, omega=0.8, steps=2, galerkin=False, precision='double', line=None): geometric V-cycle for the
  * constant-coefficient grid operators and, with the keyword galerkin=True (a real bool), for any symmetric 3- / 5- /
  * 7-point operator on the grid (psp_mg.hip); the keyword precision='single' (a str) selects the cycle evaluated in float32
- * (DESIGN.md 9g); no reference analogue */
+ * (DESIGN.md 9g); the keyword line=a (an int, with galerkin=True) the line smoother along axis a for graded and
+ * stretched grids; no reference analogue */
 #define MG_MAX_LEVELS 40
 
 typedef struct {
@@ -268,17 +269,18 @@ typedef struct {
 static PyTypeObject MGType;
 
 static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
-  static char *kwlist[] = {"A", "grid", "omega", "steps", "galerkin", "precision", NULL};
-  PyObject *matrix, *grid, *seq, *cap, *galerkin_obj = Py_False, *precision_obj = NULL;
+  static char *kwlist[] = {"A", "grid", "omega", "steps", "galerkin", "precision", "line", NULL};
+  PyObject *matrix, *grid, *seq, *cap, *galerkin_obj = Py_False, *precision_obj = NULL, *line_obj = Py_None;
   int galerkin;
+  long line = -1;
   unsigned flags = 0;
   double omega = 0.8;
   int steps = 2, ndim, a, rc, shape[2], dims[3] = {1, 1, 1};
   int is_csr, is_sss, is_ll;
   long long prod = 1;
   MGObject *op;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|di$OO", kwlist, &matrix, &grid, &omega, &steps, &galerkin_obj,
-                                   &precision_obj))
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|di$OOO", kwlist, &matrix, &grid, &omega, &steps, &galerkin_obj,
+                                   &precision_obj, &line_obj))
     return NULL;
   if (!PyBool_Check(galerkin_obj)) {
     PyErr_SetString(PyExc_TypeError, "multigrid() argument 'galerkin' must be a bool");
@@ -295,6 +297,27 @@ static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
       flags |= PSP_MG_SINGLE;
     else if (PyUnicode_CompareWithASCIIString(precision_obj, "double") != 0) {
       PyErr_SetString(PyExc_ValueError, "multigrid() argument 'precision' must be 'double' or 'single'");
+      return NULL;
+    }
+  }
+  if (line_obj != Py_None) { /* an int (no bool), the axis of the line smoother */
+    if (PyBool_Check(line_obj) || !PyLong_Check(line_obj)) {
+      PyErr_SetString(PyExc_TypeError, "multigrid() argument 'line' must be None or an int, the axis of the line smoother");
+      return NULL;
+    }
+    line = PyLong_AsLong(line_obj);
+    if (line == -1 && PyErr_Occurred()) {
+      PyErr_Clear();
+      line = -2; /* out of every range */
+    }
+    if (!galerkin) {
+      PyErr_SetString(PyExc_ValueError, "multigrid() argument 'line' needs galerkin=True: the line smoother works on stored "
+                                        "level operators");
+      return NULL;
+    }
+    if (flags & PSP_MG_SINGLE) {
+      PyErr_SetString(PyExc_ValueError, "multigrid() argument 'line' with precision='single': the line smoother has no "
+                                        "single-precision form");
       return NULL;
     }
   }
@@ -333,6 +356,20 @@ static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
     if (prod > 0x7fffffffLL) prod = 0x80000000LL; /* matches no matrix order */
   }
   Py_DECREF(seq);
+  if (line_obj != Py_None) {
+    if (ndim < 2) {
+      PyErr_SetString(PyExc_ValueError, "multigrid() argument 'line' on a grid of one axis: there is no axis left to coarsen");
+      return NULL;
+    }
+    if (line < 0 || line >= ndim) {
+      PyErr_Format(PyExc_ValueError, "multigrid() argument 'line' must be one of the grid's axes, 0 .. %d", ndim - 1);
+      return NULL;
+    }
+    if (dims[line] < 2) {
+      PyErr_SetString(PyExc_ValueError, "multigrid() argument 'line': the line axis must have at least 2 points");
+      return NULL;
+    }
+  }
   if (SpMatrix_GetShape(matrix, shape)) return NULL;
   if (shape[0] != shape[1]) {
     PyErr_SetString(PyExc_ValueError, "matrix is not square");
@@ -367,7 +404,12 @@ static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
   op->dev = NULL;
   op->op = NULL;
   Py_BEGIN_ALLOW_THREADS
-  if (is_sss)
+  if (line_obj != Py_None && is_sss)
+    rc = psp_mg_create_sss_line(((SSSMatObject *)matrix)->dev, ndim, dims, omega, steps, (int)line, &op->dev);
+  else if (line_obj != Py_None)
+    rc = psp_mg_create_csr_line(is_csr ? ((CSRMatObject *)matrix)->dev : ((LLMatObject *)matrix)->mirror, ndim, dims, omega,
+                                steps, (int)line, &op->dev);
+  else if (is_sss)
     rc = psp_mg_create_sss_ex(((SSSMatObject *)matrix)->dev, ndim, dims, omega, steps, flags, &op->dev);
   else
     rc = psp_mg_create_csr_ex(is_csr ? ((CSRMatObject *)matrix)->dev : ((LLMatObject *)matrix)->mirror, ndim, dims, omega,
@@ -494,6 +536,14 @@ static PyObject *MG_get_precision(MGObject *self, void *c) {
   return PyUnicode_FromString(bits == 32 ? "single" : "double");
 }
 
+/* the axis of the line smoother, None without one */
+static PyObject *MG_get_line(MGObject *self, void *c) {
+  int axis = -1, rc = psp_mg_line_axis(self->dev, &axis);
+  if (rc != PSP_OK) return raise_psp(rc);
+  if (axis < 0) Py_RETURN_NONE;
+  return PyLong_FromLong(axis);
+}
+
 static PyMethodDef MG_methods[] = {
     {"precon", (PyCFunction)MG_precon, METH_VARARGS,
      "self.precon(x, y)\n\napply preconditioner self on x, store result in y. x is unchanged."},
@@ -506,6 +556,7 @@ static PyGetSetDef MG_getset[] = {{"shape", (getter)MG_get_shape, NULL, "(n, n)"
                                   {"levels", (getter)MG_get_levels, NULL, "the level grids, finest first", NULL},
                                   {"galerkin", (getter)MG_get_galerkin, NULL, "stored Galerkin level operators", NULL},
                                   {"precision", (getter)MG_get_precision, NULL, "'double' or 'single'", NULL},
+                                  {"line", (getter)MG_get_line, NULL, "the axis of the line smoother, or None", NULL},
                                   {"_psp_op", (getter)MG_get_psp_op, NULL, "device operator", NULL},
                                   {NULL, NULL, NULL, NULL, NULL}};
 
@@ -519,7 +570,7 @@ static PyMethodDef precon_methods[] = {
      "omega  relaxation parameter (default value: 1.0)\n"
      "steps  number of SSOR steps"},
     {"multigrid", (PyCFunction)multigrid_prec, METH_VARARGS | METH_KEYWORDS,
-     "multigrid(A, grid, omega=0.8, steps=2, galerkin=False, precision='double') -- return geometric multigrid\n"
+     "multigrid(A, grid, omega=0.8, steps=2, galerkin=False, precision='double', line=None) -- return geometric multigrid\n"
      "preconditioner object\n\n"
      "One V-cycle with damped-Jacobi smoothing for A = sum_a c_a T_a + s I on a grid (no reference analogue).\n\n"
      "A      'csr_mat', 'sss_mat' or 'll_mat': the constant-coefficient [-1 2 -1] stencil on the grid\n"
@@ -529,7 +580,10 @@ static PyMethodDef precon_methods[] = {
      "galerkin  keyword, a bool: True takes any symmetric 3- / 5- / 7-point operator on the grid (varying\n"
      "       coefficients) and stores the level operators R A P (default value: False)\n"
      "precision  keyword, a str: 'single' runs the cycle in float32 on level operators rounded once from the\n"
-     "       double ones; x and y stay double arrays, the outer solver is unchanged (default value: 'double')"},
+     "       double ones; x and y stay double arrays, the outer solver is unchanged (default value: 'double')\n"
+     "line   keyword, None or an int: with galerkin=True, the grid axis along which the cells are graded or stretched;\n"
+     "       that axis is never coarsened and the smoother solves the level operator's tridiagonal part along each of\n"
+     "       its grid lines exactly instead of point Jacobi; double precision only (default value: None)"},
     {NULL, NULL, 0, NULL}};
 
 static struct PyModuleDef precon_module = {PyModuleDef_HEAD_INIT, "precon",
