@@ -384,10 +384,10 @@ __global__ __launch_bounds__(256) void mg_smooth_block_kernel(typename Op::Level
   }
 }
 
-// b_c = R (b - A x) for KC columns: points outer, columns inner -- a fine point's row is loaded once and applied to every
-// column of the group, whose residual tiles lie side by side in LDS.  KC = 1 with the columns in gridDim.y is the other
-// form (one tile, reused by nobody: every column is a workgroup of its own).
-template <class Op, int KC, class TB>
+// b_c = R (b - A x), one column per workgroup: blockIdx.y = the column, blockIdx.x = its tile as in mg_restrict_kernel.
+// The row of a fine point comes through load_row / ax_row like the other block kernels' (holding 2 or 4 columns' residual
+// tiles in LDS to share the rows was measured slower in every row of section 9e's table and is gone).
+template <class Op, class TB>
 __global__ __launch_bounds__(kResThreads) void mg_restrict_block_kernel(typename Op::Level A, int t0, int t1, int t2,
                                                                         int g0n, int g1n, int k,
                                                                         const typename Op::Scalar *__restrict__ x, long ldx,
@@ -395,10 +395,9 @@ __global__ __launch_bounds__(kResThreads) void mg_restrict_block_kernel(typename
                                                                         typename Op::Scalar *__restrict__ bc, long ldc,
                                                                         const int *__restrict__ frozen) {
   using S = typename Op::Scalar;
-  __shared__ S r[KC][kResLds];
-  const int c0 = blockIdx.y * KC;
-  const unsigned live = mg_live<KC>(c0, k, frozen);
-  if (!live) return;  // uniform: before any barrier
+  __shared__ S r[kResLds];
+  const int c = blockIdx.y;
+  if (!mg_live<1>(c, k, frozen)) return;  // uniform: before any barrier
   const Op op(A);
   const MgLevelArgT<S> &L = op.geo();
   const unsigned bq = blockIdx.x / (unsigned)g0n;
@@ -413,16 +412,11 @@ __global__ __launch_bounds__(kResThreads) void mg_restrict_block_kernel(typename
     if (g0 < L.n[0] && g1 < L.n[1] && g2 < L.n[2]) {
       const long i = g0 + (long)L.n[0] * (g1 + (long)L.n[1] * g2);
       const auto row = op.template load_row<false>(i, g0, g1, g2);
-#pragma unroll
-      for (int c = 0; c < KC; ++c) {
-        if (!((live >> c) & 1u)) continue;
-        const S *__restrict__ xc = x + (size_t)(c0 + c) * ldx;
-        auto X = [&](long j, S) { return xc[j]; };
-        r[c][t] = (S)b[(size_t)(c0 + c) * ldb + i] - op.ax_row(row, X, i, g0, g1, g2);
-      }
+      const S *__restrict__ xc = x + (size_t)c * ldx;
+      auto X = [&](long j, S) { return xc[j]; };
+      r[t] = (S)b[(size_t)c * ldb + i] - op.ax_row(row, X, i, g0, g1, g2);
     } else {
-#pragma unroll
-      for (int c = 0; c < KC; ++c) r[c][t] = 0;
+      r[t] = 0;
     }
   }
   __syncthreads();
@@ -431,13 +425,8 @@ __global__ __launch_bounds__(kResThreads) void mg_restrict_block_kernel(typename
     const int j0 = t % t0, q = t / t0, j1 = q % t1, j2 = q / t1;
     if (J0 + j0 < L.nc[0] && J1 + j1 < L.nc[1] && J2 + j2 < L.nc[2]) {
       const long jc = (J0 + j0) + (long)L.nc[0] * ((J1 + j1) + (long)L.nc[1] * (J2 + j2));
-#pragma unroll
-      for (int c = 0; c < KC; ++c) {
-        if (!((live >> c) & 1u)) continue;
-        const S *rc = r[c];
-        auto at = [&](int a0, int a1, int a2) { return rc[a0 + F0 * (a1 + F1 * a2)]; };
-        bc[(size_t)(c0 + c) * ldc + jc] = mg_restrict_point(L, at, j0, j1, j2);
-      }
+      auto at = [&](int a0, int a1, int a2) { return r[a0 + F0 * (a1 + F1 * a2)]; };
+      bc[(size_t)c * ldc + jc] = mg_restrict_point(L, at, j0, j1, j2);
     }
   }
 }
@@ -682,11 +671,17 @@ struct psp_mg {
     MgLevelArg a;
     MgLevelArgT<float> af;
     long N = 0;
-    // the level's vectors (levels in the tail have none): doubles, or floats on a single-precision handle, which also
-    // owns the finest level's x (a double handle works in the caller's y there)
-    void *x = nullptr, *b = nullptr, *t = nullptr;
   };
   std::vector<Level> lev;
+  // a level's vectors (mg_alloc_vectors has the rule for which exist): doubles, or floats on a single-precision handle;
+  // cols columns of leading dimension N.  `vec`: the single cycle's, one column, allocated at creation.  `blk`: the block
+  // cycle's (section 9e), blk_cols columns, allocated by the first block call and grown on demand.
+  struct Vecs {
+    void *x = nullptr, *b = nullptr, *t = nullptr;
+  };
+  std::vector<Vecs> vec, blk;
+  int blk_cols = 0;
+  size_t blk_bytes = 0;
   int tail_first = 0;  // first level of the tail launch
   int launches = 0;    // kernel launches of one application
   void *minv = nullptr;  // the coarsest level's inverse, in the handle's scalar type
@@ -706,14 +701,6 @@ struct psp_mg {
   int line_axis = -1;
   std::vector<MgLine> lines;
   std::vector<const double *> line_lo;
-  // the level vectors of the block cycle (section 9e): per level what `lev` holds, for blk_cols columns of leading
-  // dimension N, and a spare for the finest level; allocated by the first block call, grown on demand
-  struct BlockLevel {
-    void *x = nullptr, *b = nullptr, *t = nullptr;
-  };
-  std::vector<BlockLevel> blk;
-  int blk_cols = 0;
-  size_t blk_bytes = 0;
 };
 
 namespace {
@@ -985,25 +972,39 @@ int mg_level_grids(psp_mg *K, const int n[3], int steps, int line = -1) {
   return PSP_OK;
 }
 
-// level vectors: the finest level works in the caller's vectors and one spare; a level that heads the tail needs its
-// b and x in memory (the restriction above it writes b, the prolongation reads x); the levels inside the tail have none.
-// A single-precision handle holds floats, and an x of its own for the finest level too when that level is not the tail:
-// the caller's y is double and takes only the last sweep (mg_schedule).
-int mg_alloc_vectors(psp_mg *K) {
+// hipFree waits for the device, so nothing that still runs loses its buffers
+void mg_free_vectors(std::vector<psp_mg::Vecs> *set) {
+  for (psp_mg::Vecs &V : *set)
+    for (void *p : {V.x, V.b, V.t}) (void)hipFree(p);
+  set->clear();
+}
+
+// The level vectors of the handle, `cols` columns wide, into *set; *total grows by the bytes allocated.  The finest level
+// works in the caller's vectors and one spare; a level that heads the tail needs its b and x in memory (the restriction
+// above it writes b, the prolongation reads x); the levels inside the tail have none.  A single-precision handle holds
+// floats, and an x of its own for the finest level too when that level is not the tail: the caller's y is double and takes
+// only the last sweep (mg_schedule).  false: an allocation failed; what was allocated is in *set for the caller to free.
+bool mg_alloc_vectors(const psp_mg *K, int cols, std::vector<psp_mg::Vecs> *set, size_t *total) {
+  set->assign(K->lev.size(), psp_mg::Vecs());
   for (int l = 0; l <= K->tail_first; ++l) {
-    psp_mg::Level &L = K->lev[l];
-    const size_t bytes = (K->single ? sizeof(float) : sizeof(double)) * (size_t)L.N;
+    psp_mg::Vecs &V = (*set)[l];
+    const size_t bytes = (K->single ? sizeof(float) : sizeof(double)) * (size_t)K->lev[l].N * (size_t)cols;
     const bool own_x = l > 0 || (K->single && K->tail_first > 0);
-    hipError_t e = hipSuccess;
-    if (l < K->tail_first) e = hipMalloc(&L.t, bytes);
-    if (own_x && e == hipSuccess) e = hipMalloc(&L.x, bytes);
-    if (l > 0 && e == hipSuccess) e = hipMalloc(&L.b, bytes);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(PSP_ENOMEM, "multigrid: level vector allocation failed");
+    void **const want[3] = {l < K->tail_first ? &V.t : nullptr, own_x ? &V.x : nullptr, l > 0 ? &V.b : nullptr};
+    for (void **p : want) {
+      if (!p) continue;
+      if (hipMalloc(p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+      }
+      *total += bytes;
     }
-    K->vec_bytes += bytes * ((L.t != nullptr) + (L.x != nullptr) + (L.b != nullptr));
   }
+  return true;
+}
+// the single cycle's set, at creation (the handle is destroyed when this fails)
+int mg_alloc_own_vectors(psp_mg *K) {
+  if (!mg_alloc_vectors(K, 1, &K->vec, &K->vec_bytes)) return fail(PSP_ENOMEM, "multigrid: level vector allocation failed");
   return PSP_OK;
 }
 
@@ -1092,7 +1093,7 @@ int mg_create(psp_csr *A, int ndim, const int *grid, double omega, int steps, bo
           return fail(PSP_EINVAL, "%s", kSingleRange);
       }
     }
-    PSP_TRY(mg_alloc_vectors(K));
+    PSP_TRY(mg_alloc_own_vectors(K));
     std::vector<double> inv;
     PSP_TRY(coarsest_inverse(K->lev.back().a, &inv));
     if (single) return mg_upload_tail(K, inv, [&](int l) { return K->lev[l].af; });
@@ -1247,7 +1248,7 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
   const int nl = (int)K->lev.size();
   // the level vectors and the level operators' arrays (a single-precision handle allocates a level's double arrays only
   // when it builds the level)
-  PSP_TRY(mg_alloc_vectors(K));
+  PSP_TRY(mg_alloc_own_vectors(K));
   K->glev.resize(nl);
   K->coef.assign(nl, nullptr);
   if (single) {
@@ -1390,47 +1391,102 @@ void mg_restrict_grid(const MgLevelArgT<S> &a, int tile[3], long g[3]) {
   for (int x = 0; x < 3; ++x) g[x] = (a.nc[x] + tile[x] - 1) / tile[x];
 }
 
-// what the steps of the schedule below launch: the first pass from x = 0 (x = w b when steps = 1, else sweeps one and two
-// in one pass over b), a further sweep, b_c = R (b - A x), the tail -- the cycle kernels with the mode's policy, in the
-// handle's scalar type S
+// Columns per thread of the block kernels, by measurement (DESIGN.md section 9e has the register table and the figures).
+// The sweep, scale and prolongation kernels take groups of four columns with stored level operators, whose row of up to 27
+// coefficients is then loaded once for four columns, and of two in the matrix-free mode, which has nothing to share
+// but the index split (two where k <= 2 in both).  The restriction and the tail take one column per workgroup.
+constexpr int kBlockKCGalerkin = 4;
+constexpr int kBlockKCMatrixFree = 2;
+// op_apply_block and psp_pcg_batch run the block cycle in these modes (section 9e's routing decision)
+constexpr bool kRouteBlockMatrixFree = true;
+constexpr bool kRouteBlockGalerkin = true;
+
+template <class Op>
+struct OpTag {
+  using type = Op;
+};
+template <int KC>
+struct KCols {
+  static constexpr int kc = KC;
+};
+template <class P>
+using Elem = std::remove_const_t<std::remove_pointer_t<P>>;
+
+// What the steps of the schedule below launch: the first pass from x = 0 (x = w b when steps = 1, else sweeps one and two
+// in one pass over b), a further sweep, b_c = R (b - A x), the tail, x += P e -- the cycle kernels with the mode's policy,
+// in the handle's scalar type S.  For one vector (k = 0: the single kernels on the handle's own level vectors) or a block
+// of k columns (the block kernels on K->blk, groups of kc columns in gridDim.y, the frozen flags as the kernels take
+// them).  The mode, the level's shape and the element types are decided once each (with_op, mg_with_io / mg_with_b); only
+// the innermost launch statement knows whether there are columns.
 template <class S>
-struct LevelOps {
+struct CycleOps {
   psp_mg *K;
+  const std::vector<psp_mg::Vecs> &set;
+  int k = 0;
+  const int *frozen = nullptr;
+  int kc = 0;
   using Vec = MVec;
-  static Vec vec(void *p) { return MVec{p, 0, std::is_same_v<S, double>}; }
-  Vec lx(int l) const { return vec(K->lev[l].x); }
-  Vec lb(int l) const { return vec(K->lev[l].b); }
-  Vec lt(int l) const { return vec(K->lev[l].t); }
-  void prolong(int l, Vec e, Vec x) const {
-    const long N = K->lev[l].N;
-    hipLaunchKernelGGL(mg_prolong_kernel<S>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream(), mf_level<S>(K, l), N,
-                       e.as<const S>(), x.as<S>());
+  explicit CycleOps(psp_mg *K_) : K(K_), set(K_->vec) {}
+  CycleOps(psp_mg *K_, int k_, const int *frozen_) : K(K_), set(K_->blk), k(k_), frozen(frozen_) {
+    kc = k <= 2 ? 2 : K->galerkin ? kBlockKCGalerkin : kBlockKCMatrixFree;
+    const char *e = k <= 2 ? nullptr : tuning_env("PSP_MG_BLOCK_KC");  // 2 or 4: the group size that is not the default
+    if (e && (atoi(e) == 2 || atoi(e) == 4)) kc = atoi(e);
   }
-  template <class Op, bool FROMB>
-  void launch_smooth(const typename Op::Level &A, long N, Vec xin, Vec b, Vec xout) const {
-    mg_with_io<S, Op::kFinest>(b, xout, [&](auto *bp, auto *op) {
-      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
-      using TO = std::remove_pointer_t<decltype(op)>;
-      hipLaunchKernelGGL((mg_smooth_kernel<Op, FROMB, TB, TO>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream(), A, N,
-                         xin.as<const S>(), bp, op);
-    });
+  Vec vec(void *p, int l) const { return MVec{p, k ? K->lev[l].N : 0, std::is_same_v<S, double>}; }
+  Vec lx(int l) const { return vec(set[l].x, l); }
+  Vec lb(int l) const { return vec(set[l].b, l); }
+  Vec lt(int l) const { return vec(set[l].t, l); }
+  // one thread per point; a block's column groups in gridDim.y
+  dim3 grid(long N) const {
+    const unsigned nb = (unsigned)((N + 255) / 256);
+    return k ? dim3(nb, (unsigned)((k + kc - 1) / kc)) : dim3(nb);
   }
+  template <class F>
+  void with_kc(F &&f) const {
+    if (kc == 4)
+      f(KCols<4>{});
+    else
+      f(KCols<2>{});
+  }
+  // f(OpTag<the policy of level l>, what its kernels take of the level).  SPLIT = false: a matrix-free level of any shape
+  // goes through MfOp<3> (the restriction, whose shapes are run-time)
+  template <bool SPLIT, class F>
+  int with_op(int l, F &&f) const {
+    if (K->galerkin) {
+      const GLevelT<S> &G = g_level<S>(K, l);
+      return g_dispatch(G, [&](auto sh) { f(OpTag<GOp<sh.nd, sh.noff, S>>{}, G); });
+    }
+    const MgLevelArgT<S> &a = mf_level<S>(K, l);
+    const int nd = SPLIT ? level_nd(a) : 3;
+    if constexpr (SPLIT) {
+      if (nd == 1) f(OpTag<MfOp<1, S>>{}, a);
+      if (nd == 2) f(OpTag<MfOp<2, S>>{}, a);
+    }
+    if (nd == 3) f(OpTag<MfOp<3, S>>{}, a);
+    return PSP_OK;
+  }
+
   template <bool FROMB>
   int smooth(int l, Vec xin, Vec b, Vec xout) const {
     const long N = K->lev[l].N;
-    if (K->galerkin) {
-      const GLevelT<S> &G = g_level<S>(K, l);
-      return g_dispatch(G, [&](auto sh) { launch_smooth<GOp<sh.nd, sh.noff, S>, FROMB>(G, N, xin, b, xout); });
-    }
-    const MgLevelArgT<S> &a = mf_level<S>(K, l);
-    switch (level_nd(a)) {
-      case 1: launch_smooth<MfOp<1, S>, FROMB>(a, N, xin, b, xout); break;
-      case 2: launch_smooth<MfOp<2, S>, FROMB>(a, N, xin, b, xout); break;
-      default: launch_smooth<MfOp<3, S>, FROMB>(a, N, xin, b, xout); break;
-    }
-    return PSP_OK;
+    return with_op<true>(l, [&](auto tag, const auto &A) {
+      using Op = typename decltype(tag)::type;
+      mg_with_io<S, Op::kFinest>(b, xout, [&](auto *bp, auto *op) {
+        using TB = Elem<decltype(bp)>;
+        using TO = Elem<decltype(op)>;
+        if (!k)
+          hipLaunchKernelGGL((mg_smooth_kernel<Op, FROMB, TB, TO>), grid(N), dim3(256), 0, stream(), A, N, xin.as<const S>(), bp,
+                             op);
+        else
+          with_kc([&](auto c) {
+            hipLaunchKernelGGL((mg_smooth_block_kernel<Op, FROMB, c.kc, TB, TO>), grid(N), dim3(256), 0, stream(), A, N, k,
+                               xin.as<const S>(), xin.ld, bp, b.ld, op, xout.ld, frozen);
+          });
+      });
+    });
   }
-  // line = a (section 9h): one line sweep of level l, xout = xin + omega T^-1 (b - A xin); FROM0: from xin = 0
+  // line = a (section 9h): one line sweep of level l, xout = xin + omega T^-1 (b - A xin); FROM0: from xin = 0.  The line
+  // kernels have no block form: mg_apply_block_dev sends a line handle's columns through here one at a time
   template <bool FROM0>
   int line_sweep(int l, double omega, Vec xin, Vec b, Vec xout) const {
     if constexpr (std::is_same_v<S, double>) {
@@ -1446,207 +1502,90 @@ struct LevelOps {
       return fail(PSP_EINVAL, "multigrid: internal error (a single-precision handle with a line axis)");
     }
   }
+  template <class W>  // MfW or GW
+  void scale(int l, W w, Vec b, Vec dst) const {
+    const long N = K->lev[l].N;
+    mg_with_b<S>(b, [&](auto *bp) {
+      using TB = Elem<decltype(bp)>;
+      if (!k)
+        hipLaunchKernelGGL((mg_scale_kernel<W, TB>), grid(N), dim3(256), 0, stream(), N, w, bp, dst.as<S>());
+      else
+        with_kc([&](auto c) {
+          hipLaunchKernelGGL((mg_scale_block_kernel<W, c.kc, TB>), grid(N), dim3(256), 0, stream(), N, w, k, bp, b.ld,
+                             dst.as<S>(), dst.ld, frozen);
+        });
+    });
+  }
   int first(int l, Vec b, Vec dst) const {
     if (K->line_axis >= 0) return line_sweep<true>(l, K->omega, Vec(), b, dst);
     if (K->steps > 1) return smooth<true>(l, Vec(), b, dst);
-    const long N = K->lev[l].N;
-    const dim3 g((unsigned)((N + 255) / 256)), t(256);
-    mg_with_b<S>(b, [&](auto *bp) {
-      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
-      if (K->galerkin)
-        hipLaunchKernelGGL((mg_scale_kernel<GW<S>, TB>), g, t, 0, stream(), N, GW<S>{g_level<S>(K, l).w}, bp, dst.as<S>());
-      else
-        hipLaunchKernelGGL((mg_scale_kernel<MfW<S>, TB>), g, t, 0, stream(), N, MfW<S>{mf_level<S>(K, l).w}, bp, dst.as<S>());
-    });
+    if (K->galerkin)
+      scale(l, GW<S>{g_level<S>(K, l).w}, b, dst);
+    else
+      scale(l, MfW<S>{mf_level<S>(K, l).w}, b, dst);
     return PSP_OK;
   }
   int sweep(int l, Vec xin, Vec b, Vec xout) const {
     if (K->line_axis >= 0) return line_sweep<false>(l, K->omega, xin, b, xout);
     return smooth<false>(l, xin, b, xout);
   }
-  template <class Op>
-  void launch_restrict(const typename Op::Level &A, Vec x, Vec b, Vec bc) const {
-    int tile[3];
-    long g[3];
-    mg_restrict_grid(level_geo(A), tile, g);
-    mg_with_b<S, Op::kFinest>(b, [&](auto *bp) {
-      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
-      hipLaunchKernelGGL((mg_restrict_kernel<Op, TB>), dim3((unsigned)(g[0] * g[1] * g[2])), dim3(kResThreads), 0, stream(), A,
-                         tile[0], tile[1], tile[2], (int)g[0], (int)g[1], x.as<const S>(), bp, bc.as<S>());
+  // a workgroup per tile of coarse points; a block's columns in gridDim.y, one each
+  int restrict_to(int l, Vec x, Vec b, Vec bc) const {
+    return with_op<false>(l, [&](auto tag, const auto &A) {
+      using Op = typename decltype(tag)::type;
+      int tile[3];
+      long g[3];
+      mg_restrict_grid(level_geo(A), tile, g);
+      const unsigned tiles = (unsigned)(g[0] * g[1] * g[2]);
+      mg_with_b<S, Op::kFinest>(b, [&](auto *bp) {
+        using TB = Elem<decltype(bp)>;
+        if (!k)
+          hipLaunchKernelGGL((mg_restrict_kernel<Op, TB>), dim3(tiles), dim3(kResThreads), 0, stream(), A, tile[0], tile[1],
+                             tile[2], (int)g[0], (int)g[1], x.as<const S>(), bp, bc.as<S>());
+        else
+          hipLaunchKernelGGL((mg_restrict_block_kernel<Op, TB>), dim3(tiles, (unsigned)k), dim3(kResThreads), 0, stream(), A,
+                             tile[0], tile[1], tile[2], (int)g[0], (int)g[1], k, x.as<const S>(), x.ld, bp, b.ld, bc.as<S>(),
+                             bc.ld, frozen);
+      });
     });
   }
-  int restrict_to(int l, Vec x, Vec b, Vec bc) const {
-    if (K->galerkin) {
-      const GLevelT<S> &G = g_level<S>(K, l);
-      return g_dispatch(G, [&](auto sh) { launch_restrict<GOp<sh.nd, sh.noff, S>>(G, x, b, bc); });
-    }
-    launch_restrict<MfOp<3, S>>(mf_level<S>(K, l), x, b, bc);
-    return PSP_OK;
+  // the tail's ends are both the caller's (the whole grid is the tail) or both the handle's; a block's columns are a
+  // workgroup each
+  template <class Op>  // MfOp<3> or GTailOp: K->tail is that mode's table
+  void launch_tail(Vec b, Vec x) const {
+    const auto *T = (const TailArg<typename Op::Level> *)K->tail;
+    const S *minv = (const S *)K->minv;
+    mg_with_io<S>(b, x, [&](auto *bp, auto *xp) {
+      using TB = Elem<decltype(bp)>;
+      using TX = Elem<decltype(xp)>;
+      if constexpr (std::is_same_v<TB, TX>) {
+        if (!k)
+          hipLaunchKernelGGL((mg_tail_kernel<Op, TB, TX>), dim3(1), dim3(kTailThreads), 0, stream(), T, minv, bp, xp);
+        else
+          hipLaunchKernelGGL((mg_tail_block_kernel<Op, TB, TX>), dim3(k), dim3(kTailThreads), 0, stream(), T, minv, bp, b.ld, xp,
+                             x.ld, frozen);
+      }
+    });
   }
-  // the tail's ends are both the caller's (the whole grid is the tail) or both the handle's.  With a line axis the step
-  // is the last level's x = T^-1 b: that level is one line and A = T there (section 9h)
+  // with a line axis the step is the last level's x = T^-1 b: that level is one line and A = T there (section 9h)
   void tail(Vec b, Vec x) const {
-    if (K->line_axis >= 0) {
+    if (K->line_axis >= 0)
       (void)line_sweep<true>(K->tail_first, 1.0, Vec(), b, x);
-      return;
-    }
-    mg_with_io<S>(b, x, [&](auto *bp, auto *xp) {
-      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
-      using TX = std::remove_pointer_t<decltype(xp)>;
-      if constexpr (std::is_same_v<TB, TX>) {
-        if (K->galerkin)
-          hipLaunchKernelGGL((mg_tail_kernel<GTailOp<S>, TB, TX>), dim3(1), dim3(kTailThreads), 0, stream(),
-                             (const TailArg<GLevelT<S>> *)K->tail, (const S *)K->minv, bp, xp);
-        else
-          hipLaunchKernelGGL((mg_tail_kernel<MfOp<3, S>, TB, TX>), dim3(1), dim3(kTailThreads), 0, stream(),
-                             (const TailArg<MgLevelArgT<S>> *)K->tail, (const S *)K->minv, bp, xp);
-      }
-    });
-  }
-};
-
-// Columns per thread of the block kernels, by measurement (DESIGN.md section 9e has the register table and the figures).
-// The sweep, scale and prolongation kernels take groups of four columns with stored level operators, whose row of up to 27
-// coefficients is then loaded once for four columns, and of two in the matrix-free mode, which has nothing to share
-// but the index split (two where k <= 2 in both).  The restriction takes ONE column per workgroup (kBlockKCR = 1, the
-// columns in gridDim.y): holding 2 or 4 residual tiles in LDS to share the rows was 5 to 22 % and 40 to 70 % slower.
-constexpr int kBlockKCGalerkin = 4;
-constexpr int kBlockKCMatrixFree = 2;
-constexpr int kBlockKCR = 1;
-// op_apply_block and psp_pcg_batch run the block cycle in these modes (section 9e's routing decision)
-constexpr bool kRouteBlockMatrixFree = true;
-constexpr bool kRouteBlockGalerkin = true;
-
-int block_tuning(const char *name, int dflt, std::initializer_list<int> allowed) {
-  const char *e = tuning_env(name);
-  if (!e) return dflt;
-  const int v = atoi(e);
-  for (int a : allowed)
-    if (a == v) return v;
-  return dflt;
-}
-
-// the block cycle's launches: LevelOps with the column count, the leading dimensions and the frozen flags
-template <class S>
-struct BlockOps {
-  psp_mg *K;
-  int k;
-  const int *frozen;
-  int kc, kcr;
-  using Vec = MVec;
-  BlockOps(psp_mg *K_, int k_, const int *frozen_) : K(K_), k(k_), frozen(frozen_) {
-    kc = k <= 2 ? 2 : block_tuning("PSP_MG_BLOCK_KC", K->galerkin ? kBlockKCGalerkin : kBlockKCMatrixFree, {2, 4});
-    kcr = k == 1 ? 1 : block_tuning("PSP_MG_BLOCK_KCR", kBlockKCR, {1, 2, 4});
-  }
-  Vec vec(void *p, int l) const { return MVec{p, K->lev[l].N, std::is_same_v<S, double>}; }
-  Vec lx(int l) const { return vec(K->blk[l].x, l); }
-  Vec lb(int l) const { return vec(K->blk[l].b, l); }
-  Vec lt(int l) const { return vec(K->blk[l].t, l); }
-  dim3 grid(long N) const { return dim3((unsigned)((N + 255) / 256), (unsigned)((k + kc - 1) / kc)); }
-
-  template <class Op, bool FROMB>
-  void launch_smooth(const typename Op::Level &A, long N, Vec xin, Vec b, Vec xout) const {
-    mg_with_io<S, Op::kFinest>(b, xout, [&](auto *bp, auto *op) {
-      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
-      using TO = std::remove_pointer_t<decltype(op)>;
-      if (kc == 4)
-        hipLaunchKernelGGL((mg_smooth_block_kernel<Op, FROMB, 4, TB, TO>), grid(N), dim3(256), 0, stream(), A, N, k,
-                           xin.as<const S>(), xin.ld, bp, b.ld, op, xout.ld, frozen);
-      else
-        hipLaunchKernelGGL((mg_smooth_block_kernel<Op, FROMB, 2, TB, TO>), grid(N), dim3(256), 0, stream(), A, N, k,
-                           xin.as<const S>(), xin.ld, bp, b.ld, op, xout.ld, frozen);
-    });
-  }
-  template <bool FROMB>
-  int smooth(int l, Vec xin, Vec b, Vec xout) const {
-    const long N = K->lev[l].N;
-    if (K->galerkin) {
-      const GLevelT<S> &G = g_level<S>(K, l);
-      return g_dispatch(G, [&](auto sh) { launch_smooth<GOp<sh.nd, sh.noff, S>, FROMB>(G, N, xin, b, xout); });
-    }
-    const MgLevelArgT<S> &a = mf_level<S>(K, l);
-    switch (level_nd(a)) {
-      case 1: launch_smooth<MfOp<1, S>, FROMB>(a, N, xin, b, xout); break;
-      case 2: launch_smooth<MfOp<2, S>, FROMB>(a, N, xin, b, xout); break;
-      default: launch_smooth<MfOp<3, S>, FROMB>(a, N, xin, b, xout); break;
-    }
-    return PSP_OK;
-  }
-  template <class W>
-  void launch_scale(long N, W w, Vec b, Vec dst) const {
-    mg_with_b<S>(b, [&](auto *bp) {
-      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
-      if (kc == 4)
-        hipLaunchKernelGGL((mg_scale_block_kernel<W, 4, TB>), grid(N), dim3(256), 0, stream(), N, w, k, bp, b.ld, dst.as<S>(),
-                           dst.ld, frozen);
-      else
-        hipLaunchKernelGGL((mg_scale_block_kernel<W, 2, TB>), grid(N), dim3(256), 0, stream(), N, w, k, bp, b.ld, dst.as<S>(),
-                           dst.ld, frozen);
-    });
-  }
-  int first(int l, Vec b, Vec dst) const {
-    if (K->steps > 1) return smooth<true>(l, Vec(), b, dst);
-    const long N = K->lev[l].N;
-    if (K->galerkin)
-      launch_scale(N, GW<S>{g_level<S>(K, l).w}, b, dst);
+    else if (K->galerkin)
+      launch_tail<GTailOp<S>>(b, x);
     else
-      launch_scale(N, MfW<S>{mf_level<S>(K, l).w}, b, dst);
-    return PSP_OK;
-  }
-  int sweep(int l, Vec xin, Vec b, Vec xout) const { return smooth<false>(l, xin, b, xout); }
-
-  template <class Op, int KCR>
-  void launch_restrict_kc(const typename Op::Level &A, Vec x, Vec b, Vec bc) const {
-    int tile[3];
-    long g[3];
-    mg_restrict_grid(level_geo(A), tile, g);
-    mg_with_b<S, Op::kFinest>(b, [&](auto *bp) {
-      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
-      hipLaunchKernelGGL((mg_restrict_block_kernel<Op, KCR, TB>),
-                         dim3((unsigned)(g[0] * g[1] * g[2]), (unsigned)((k + KCR - 1) / KCR)), dim3(kResThreads), 0, stream(), A,
-                         tile[0], tile[1], tile[2], (int)g[0], (int)g[1], k, x.as<const S>(), x.ld, bp, b.ld, bc.as<S>(), bc.ld,
-                         frozen);
-    });
-  }
-  template <class Op>
-  void launch_restrict(const typename Op::Level &A, Vec x, Vec b, Vec bc) const {
-    if (kcr == 4)
-      launch_restrict_kc<Op, 4>(A, x, b, bc);
-    else if (kcr == 2)
-      launch_restrict_kc<Op, 2>(A, x, b, bc);
-    else
-      launch_restrict_kc<Op, 1>(A, x, b, bc);
-  }
-  int restrict_to(int l, Vec x, Vec b, Vec bc) const {
-    if (K->galerkin) {
-      const GLevelT<S> &G = g_level<S>(K, l);
-      return g_dispatch(G, [&](auto sh) { launch_restrict<GOp<sh.nd, sh.noff, S>>(G, x, b, bc); });
-    }
-    launch_restrict<MfOp<3, S>>(mf_level<S>(K, l), x, b, bc);
-    return PSP_OK;
-  }
-  void tail(Vec b, Vec x) const {
-    mg_with_io<S>(b, x, [&](auto *bp, auto *xp) {
-      using TB = std::remove_const_t<std::remove_pointer_t<decltype(bp)>>;
-      using TX = std::remove_pointer_t<decltype(xp)>;
-      if constexpr (std::is_same_v<TB, TX>) {
-        if (K->galerkin)
-          hipLaunchKernelGGL((mg_tail_block_kernel<GTailOp<S>, TB, TX>), dim3(k), dim3(kTailThreads), 0, stream(),
-                             (const TailArg<GLevelT<S>> *)K->tail, (const S *)K->minv, bp, b.ld, xp, x.ld, frozen);
-        else
-          hipLaunchKernelGGL((mg_tail_block_kernel<MfOp<3, S>, TB, TX>), dim3(k), dim3(kTailThreads), 0, stream(),
-                             (const TailArg<MgLevelArgT<S>> *)K->tail, (const S *)K->minv, bp, b.ld, xp, x.ld, frozen);
-      }
-    });
+      launch_tail<MfOp<3, S>>(b, x);
   }
   void prolong(int l, Vec e, Vec x) const {
     const long N = K->lev[l].N;
-    if (kc == 4)
-      hipLaunchKernelGGL((mg_prolong_block_kernel<4, S>), grid(N), dim3(256), 0, stream(), mf_level<S>(K, l), N, k,
-                         e.as<const S>(), e.ld, x.as<S>(), x.ld, frozen);
+    const MgLevelArgT<S> &a = mf_level<S>(K, l);
+    if (!k)
+      hipLaunchKernelGGL(mg_prolong_kernel<S>, grid(N), dim3(256), 0, stream(), a, N, e.as<const S>(), x.as<S>());
     else
-      hipLaunchKernelGGL((mg_prolong_block_kernel<2, S>), grid(N), dim3(256), 0, stream(), mf_level<S>(K, l), N, k,
-                         e.as<const S>(), e.ld, x.as<S>(), x.ld, frozen);
+      with_kc([&](auto c) {
+        hipLaunchKernelGGL((mg_prolong_block_kernel<c.kc, S>), grid(N), dim3(256), 0, stream(), a, N, k, e.as<const S>(), e.ld,
+                           x.as<S>(), x.ld, frozen);
+      });
   }
 };
 
@@ -1718,38 +1657,19 @@ int mg_schedule(psp_mg *K, typename Ops::Vec b_dev, typename Ops::Vec y_dev, con
 }
 
 void mg_block_free(psp_mg *K) {
-  for (psp_mg::BlockLevel &B : K->blk)
-    for (void *p : {B.x, B.b, B.t}) (void)hipFree(p);
-  K->blk.clear();
+  mg_free_vectors(&K->blk);
   K->blk_cols = 0;
   K->blk_bytes = 0;
 }
 
-// the block cycle's level vectors for at least k columns (k = 0: none); what mg_alloc_vectors allocates, k columns wide.
-// hipFree waits for the device, so nothing that still runs loses its buffers.
+// the block cycle's level vectors for at least k columns (k = 0: none)
 int mg_block_reserve(psp_mg *K, int k) {
-  if (k == 0) {
-    mg_block_free(K);
-    return PSP_OK;
-  }
-  if (k <= K->blk_cols || K->line_axis >= 0) return PSP_OK;  // a line handle has no block vectors to reserve
+  if (k > 0 && (k <= K->blk_cols || K->line_axis >= 0)) return PSP_OK;  // a line handle has no block vectors to reserve
   mg_block_free(K);
-  K->blk.resize(K->lev.size());
-  for (int l = 0; l <= K->tail_first; ++l) {
-    psp_mg::BlockLevel &B = K->blk[l];
-    const size_t bytes = (K->single ? sizeof(float) : sizeof(double)) * (size_t)K->lev[l].N * (size_t)k;
-    const bool own_x = l > 0 || (K->single && K->tail_first > 0);  // as mg_alloc_vectors
-    hipError_t e = hipSuccess;
-    size_t got = 0;
-    if (l < K->tail_first) e = hipMalloc(&B.t, bytes), got += e == hipSuccess ? bytes : 0;
-    if (own_x && e == hipSuccess) e = hipMalloc(&B.x, bytes), got += e == hipSuccess ? bytes : 0;
-    if (l > 0 && e == hipSuccess) e = hipMalloc(&B.b, bytes), got += e == hipSuccess ? bytes : 0;
-    K->blk_bytes += got;
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      mg_block_free(K);
-      return fail(PSP_ENOMEM, "multigrid: block level vector allocation failed (%d columns)", k);
-    }
+  if (k == 0) return PSP_OK;
+  if (!mg_alloc_vectors(K, k, &K->blk, &K->blk_bytes)) {
+    mg_block_free(K);
+    return fail(PSP_ENOMEM, "multigrid: block level vector allocation failed (%d columns)", k);
   }
   K->blk_cols = k;
   return PSP_OK;
@@ -1762,8 +1682,8 @@ namespace psp {
 // y = V(0, b) on device vectors; y must not alias b.  The handle is locked by the caller.
 int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
   const MVec b{const_cast<double *>(b_dev), 0, true}, y{y_dev, 0, true};
-  if (K->single) return mg_schedule(K, b, y, LevelOps<float>{K});
-  return mg_schedule(K, b, y, LevelOps<double>{K});
+  if (K->single) return mg_schedule(K, b, y, CycleOps<float>(K));
+  return mg_schedule(K, b, y, CycleOps<double>(K));
 }
 
 // Y[:, c] = V(0, X[:, c]) for every column c < k with frozen[c] == 0 (frozen == nullptr: every column), one block cycle:
@@ -1779,8 +1699,8 @@ int mg_apply_block_dev(psp_mg *K, int k, const double *X, long ldx, double *Y, l
   }
   PSP_TRY(mg_block_reserve(K, k));
   const MVec x{const_cast<double *>(X), ldx, true}, y{Y, ldy, true};
-  if (K->single) return mg_schedule(K, x, y, BlockOps<float>(K, k, frozen));
-  return mg_schedule(K, x, y, BlockOps<double>(K, k, frozen));
+  if (K->single) return mg_schedule(K, x, y, CycleOps<float>(K, k, frozen));
+  return mg_schedule(K, x, y, CycleOps<double>(K, k, frozen));
 }
 
 int mg_launches(const psp_mg *K) { return K->launches; }
@@ -1793,6 +1713,37 @@ bool mg_block_routed(const psp_mg *K) {
 }
 
 }  // namespace psp
+
+namespace {
+
+// The body of the host entry points `fn`: the caller's vector (k = 0) or its k columns of n to scratch, apply(x, y) on the
+// device copies (columns of leading dimension n), y back.  The cycle's own error comes before the copies'.
+template <class Apply>
+int mg_staged(const char *fn, size_t n, int k, const double *x_host, long ldx, double *y_host, long ldy, Apply &&apply) {
+  const size_t nk = n * (size_t)std::max(k, 1), row = sizeof(double) * n;
+  auto copy = [&](void *dst, size_t dpitch, const void *src, size_t spitch, hipMemcpyKind kind) {
+    return k ? hipMemcpy2DAsync(dst, dpitch, src, spitch, row, k, kind, stream())
+             : hipMemcpyAsync(dst, src, row, kind, stream());
+  };
+  double *x = nullptr, *y = nullptr;
+  PSP_TRY(scratch_get(nk, &x));
+  int rc = scratch_get(nk, &y);
+  if (rc != PSP_OK) {
+    scratch_put(x, nk);
+    return rc;
+  }
+  hipError_t e = copy(x, row, x_host, sizeof(double) * ldx, hipMemcpyHostToDevice);
+  if (e == hipSuccess) rc = apply(x, y);
+  if (e == hipSuccess && rc == PSP_OK) e = copy(y_host, sizeof(double) * ldy, y, row, hipMemcpyDeviceToHost);
+  const hipError_t e2 = hipStreamSynchronize(stream());
+  scratch_put(x, nk);
+  scratch_put(y, nk);
+  if (rc != PSP_OK) return rc;
+  if (e != hipSuccess || e2 != hipSuccess) return fail(PSP_ENODEV, "%s: %s", fn, hipGetErrorString(e != hipSuccess ? e : e2));
+  return PSP_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1909,8 +1860,7 @@ int psp_mg_destroy(psp_mg_t *K) {
   mg_block_free(K);
   for (double *p : K->coef) (void)hipFree(p);
   for (float *p : K->coef32) (void)hipFree(p);
-  for (psp_mg::Level &L : K->lev)
-    for (void *p : {L.x, L.b, L.t}) (void)hipFree(p);
+  mg_free_vectors(&K->vec);
   (void)hipFree(K->minv);
   (void)hipFree(K->tail);
   delete K;
@@ -1950,24 +1900,8 @@ int psp_mg_precon(psp_mg_t *K, const double *x_host, double *y_host) {
   PSP_API_GUARD_H(K);
   if (!K || !x_host || !y_host) return fail(PSP_EINVAL, "psp_mg_precon: NULL argument");
   PSP_TRY(ensure_device());
-  const size_t n = (size_t)K->n, bytes = sizeof(double) * n;
-  double *x = nullptr, *y = nullptr;
-  PSP_TRY(scratch_get(n, &x));
-  int rc = scratch_get(n, &y);
-  if (rc != PSP_OK) {
-    scratch_put(x, n);
-    return rc;
-  }
-  hipError_t e = hipMemcpyAsync(x, x_host, bytes, hipMemcpyHostToDevice, stream());
-  if (e == hipSuccess) rc = mg_apply_dev(K, x, y);
-  if (e == hipSuccess && rc == PSP_OK) e = hipMemcpyAsync(y_host, y, bytes, hipMemcpyDeviceToHost, stream());
-  const hipError_t e2 = hipStreamSynchronize(stream());
-  scratch_put(x, n);
-  scratch_put(y, n);
-  if (rc != PSP_OK) return rc;
-  if (e != hipSuccess || e2 != hipSuccess)
-    return fail(PSP_ENODEV, "psp_mg_precon: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  return PSP_OK;
+  return mg_staged("psp_mg_precon", (size_t)K->n, 0, x_host, K->n, y_host, K->n,
+                   [&](const double *x, double *y) { return mg_apply_dev(K, x, y); });
 }
 
 int psp_mg_precon_block_dev(psp_mg_t *K, int k, const double *X_dev, long ldx, double *Y_dev, long ldy) {
@@ -1985,25 +1919,9 @@ int psp_mg_precon_block(psp_mg_t *K, int k, const double *X_host, long ldx, doub
   if (!K) return fail(PSP_EINVAL, "psp_mg_precon_block: NULL handle");
   PSP_TRY(block_args("psp_mg_precon_block", K->n, K->n, k, X_host, ldx, Y_host, ldy));
   PSP_TRY(ensure_device());
-  const size_t n = (size_t)K->n, nk = n * (size_t)k, row = sizeof(double) * n;
-  double *x = nullptr, *y = nullptr;
-  PSP_TRY(scratch_get(nk, &x));
-  int rc = scratch_get(nk, &y);
-  if (rc != PSP_OK) {
-    scratch_put(x, nk);
-    return rc;
-  }
-  hipError_t e = hipMemcpy2DAsync(x, row, X_host, sizeof(double) * ldx, row, k, hipMemcpyHostToDevice, stream());
-  if (e == hipSuccess) rc = mg_apply_block_dev(K, k, x, (long)n, y, (long)n, nullptr);
-  if (e == hipSuccess && rc == PSP_OK)
-    e = hipMemcpy2DAsync(Y_host, sizeof(double) * ldy, y, row, row, k, hipMemcpyDeviceToHost, stream());
-  const hipError_t e2 = hipStreamSynchronize(stream());
-  scratch_put(x, nk);
-  scratch_put(y, nk);
-  if (rc != PSP_OK) return rc;
-  if (e != hipSuccess || e2 != hipSuccess)
-    return fail(PSP_ENODEV, "psp_mg_precon_block: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  return PSP_OK;
+  return mg_staged("psp_mg_precon_block", (size_t)K->n, k, X_host, ldx, Y_host, ldy, [&](const double *x, double *y) {
+    return mg_apply_block_dev(K, k, x, (long)K->n, y, (long)K->n, nullptr);
+  });
 }
 
 int psp_mg_block_reserve(psp_mg_t *K, int k) {

@@ -366,6 +366,52 @@ def test_refusals():
     K.close()
 
 
+# ------------------------------------------------------------------------------------------------ 6: the retired switch
+
+RETIRED_CHILD = """
+import sys
+sys.path[:0] = [%r, %r]
+import numpy as np
+from pysparse_amd import device as dev
+from test_gpu_multigrid_block import columns, device_csr, singles
+grid, k = (36, 34, 33), 5
+n = int(np.prod(grid))
+X = columns(n, k, 9)
+for mode in ("poisson", "smooth"):
+    for cls in (dev.DeviceMultigrid, dev.DeviceMultigrid32):
+        K = cls(device_csr(grid, mode), grid, 0.8, 2, galerkin=mode != "poisson")
+        info = K.info()
+        assert [int(np.prod(d)) for d in info["dims"][:3]] == [40392, 4896, 576] and info["tail_first_level"] == 2, info
+        Z = singles(K, X)
+        assert np.isfinite(Z).all() and np.abs(Z).max() > 0.0
+        Y = np.full((n, k), np.nan, order="F")
+        K.precon_block(X, Y)
+        for c in range(k):
+            assert np.array_equal(Y[:, c].view(np.int64), Z[:, c].view(np.int64)), (mode, info["precision"], c)
+        print("same bits", mode, info["precision"])
+        K.close()
+"""
+
+
+def test_retired_restriction_switch_is_inert():
+    """PSP_MG_BLOCK_KCR (2 or 4 residual tiles per workgroup of the block restriction) is gone: a fresh process started
+    with PSP_TUNING=1 PSP_MG_BLOCK_KCR=4 still gives every column of precon_block the bits of precon on that column.  The
+    grid (36, 34, 33) is the smallest with two launch-per-step levels (40392 and 4896 points above the 576-point tail), so
+    the restriction runs on a level-0 shape and on a full 13-offset shape; k = 5 leaves a KC = 4 group a remainder
+    column; both modes, both precisions."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PSP_TUNING="1", PSP_MG_BLOCK_KCR="4")
+    p = subprocess.run([sys.executable, "-c", RETIRED_CHILD % (root, os.path.join(root, "tests"))], env=env,
+                       capture_output=True, text=True, cwd=root, timeout=300)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
+    for mode in ("poisson", "smooth"):
+        for precision in ("double", "single"):
+            assert "same bits %s %s" % (mode, precision) in p.stdout, p.stdout
+
+
 def test_two_threads_with_a_handle_each_on_one_matrix():
     grid, mode = (33, 31, 35), "rand1e4"
     n = int(np.prod(grid))

@@ -10,9 +10,10 @@ tools/mg_galerkin_timing.py) and k in {2, 4, 8}:
    stands the byte model: galerkin (coef + vec k) / ((coef + vec) k) with coef = the bytes of a cycle that are level
    operators and w, vec = the rest (tools/mg_galerkin_timing.py's model_bytes split in two); matrix-free 1.0 (nothing
    is shared but the launches).  psp_stream_probe (2 read + 1 write) runs in the same process.
-2. --variants: the same block window for the restriction's two forms and column counts (PSP_MG_BLOCK_KCR = 1: a
-   column per workgroup; 2, 4: points outer, that many residual tiles in LDS) and the sweep's KC (PSP_MG_BLOCK_KC = 2, 4),
-   through the tuning switches (the child runs with PSP_TUNING=1).
+2. --variants: the same block window for the sweep's column counts (PSP_MG_BLOCK_KC = 2, 4) through the tuning switch
+   (the child runs with PSP_TUNING=1); records "kc2", "kc4".  Records of earlier runs in the profile are keyed
+   "kcr<R>_kc<C>": they also swept the restriction's residual tiles per workgroup, R = 2 and 4 of which are gone from the
+   library (R = 1 is what it does); they are kept as they were.
 3. --pcg: psp_pcg_batch_dev against k psp_pcg_dev to 1e-8 with the Galerkin cycle, host clock around synchronised calls,
    the two alternating twice.
 
@@ -130,13 +131,11 @@ def measure_mode(L, K, n, nd, galerkin, xb, yb, probe, variants):
         r["block_storage"] = K.block_info()
         if variants:
             r["variants"] = {}
-            for kcr in (1, 2, 4):
-                for kc in (2, 4):
-                    if k <= 2 and kc != 2:
-                        continue
-                    os.environ["PSP_MG_BLOCK_KCR"], os.environ["PSP_MG_BLOCK_KC"] = str(kcr), str(kc)
-                    r["variants"]["kcr%d_kc%d" % (kcr, kc)] = block_window(L, K, k, n, xb, yb)
-            os.environ.pop("PSP_MG_BLOCK_KCR")
+            for kc in (2, 4):
+                if k <= 2 and kc != 2:
+                    continue
+                os.environ["PSP_MG_BLOCK_KC"] = str(kc)
+                r["variants"]["kc%d" % kc] = block_window(L, K, k, n, xb, yb)
             os.environ.pop("PSP_MG_BLOCK_KC")
         out["k"][str(k)] = r
         print(json.dumps({"galerkin": galerkin, "k": k, **{a: r[a] for a in ("ratio_block_over_singles", "ratio_spread",
@@ -216,7 +215,7 @@ def main():
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "mg_block_timing.json"))
     p.add_argument("--quick", action="store_true", help="two small grids: a rehearsal of the tool, not a measurement")
     p.add_argument("--grids", help="comma-separated subset of the grids; results are merged into --out")
-    p.add_argument("--variants", action="store_true", help="also time the restriction / sweep column counts")
+    p.add_argument("--variants", action="store_true", help="also time the sweep's column counts (KC = 2, 4)")
     p.add_argument("--pcg", action="store_true", help="also time psp_pcg_batch_dev against k psp_pcg_dev")
     p.add_argument("--case", help="(internal) run one grid in this process and print its JSON record")
     a = p.parse_args()
