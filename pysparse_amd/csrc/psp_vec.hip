@@ -10,7 +10,9 @@
 // follows the reference expression order; the library is built with -ffp-contract=off.
 #include <algorithm>
 #include <cstdlib>
+#include <initializer_list>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #include "psp_internal.h"
@@ -50,6 +52,19 @@ __device__ __forceinline__ void st(double *p, long i, const Pack<V> &x) {
 #endif
 }
 
+// the preconditioner's factors for elements i .. i + V - 1.  PRE: 0 no preconditioner (nothing read, the result unused),
+// 1 the dinv array, 2 dinv is the constant dc everywhere (the same products value * dinv_i, one 8-byte stream less)
+template <int V, int PRE>
+__device__ __forceinline__ Pack<V> ld_dinv(const double *dinv, double dc, long i) {
+  Pack<V> dd = {};
+  if constexpr (PRE == 1) dd = ld<V>(dinv, i);
+  if constexpr (PRE == 2) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) dd.v[u] = dc;
+  }
+  return dd;
+}
+
 __device__ __forceinline__ double wave_sum(double v) { return psp::psp_wave_sum(v); }
 
 // sums NV per-thread values over the block; thread 0 stores them to partials[j*kMaxParts + block]
@@ -67,6 +82,19 @@ __device__ __forceinline__ void block_reduce_store(double (&v)[NV], double *part
     for (int j = 0; j < NV; ++j)
       partials[(size_t)j * kMaxParts + blockIdx.x] = sh[j][0] + sh[j][1] + sh[j][2] + sh[j][3];
   }
+}
+
+// the end of the stagnation scan (pcg.c:138-139): dmax = a lane's largest |alpha p_i / x_i|; partial slot 2 = nonstag,
+// the number of waves of the workgroup whose maximum still has 1 + dmax != 1
+__device__ __forceinline__ void nonstag_store(double dmax, double *partials) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double o = __shfl_down(dmax, off, 64);
+    if (o > dmax) dmax = o;
+  }
+  double acc[1];
+  acc[0] = ((threadIdx.x & 63) == 0 && (1.0 + dmax != 1.0)) ? 1.0 : 0.0;
+  block_reduce_store<1>(acc, partials + 2 * (size_t)kMaxParts);
 }
 
 // workgroup b streams the contiguous span [b*kVecSpan, (b+1)*kVecSpan) (and b + grid, ...).  Thread t owns
@@ -106,12 +134,7 @@ __global__ __launch_bounds__(kBlock) void residual_kernel(long n, const double *
   PSP_VEC_LOOP(i, n) {
     const Pack<V> bb = ld<V>(b, i);
     Pack<V> rr = ld<V>(r, i);
-    Pack<V> dd;
-    if constexpr (PRE == 1) dd = ld<V>(dinv, i);
-    if constexpr (PRE == 2) {
-#pragma unroll
-      for (int u = 0; u < V; ++u) dd.v[u] = dc;
-    }
+    const Pack<V> dd = ld_dinv<V, PRE>(dinv, dc, i);
 #pragma unroll
     for (int u = 0; u < V; ++u) {
       const double t = bb.v[u] - rr.v[u];
@@ -143,14 +166,10 @@ __global__ __launch_bounds__(kBlock) void pupdate_kernel(long n, const double *_
   }
   PSP_VEC_LOOP(i, n) {
     Pack<V> z = ld<V>(r, i);
-    if constexpr (PRE == 1) {
-      const Pack<V> dd = ld<V>(dinv, i);
+    if constexpr (PRE != 0) {
+      const Pack<V> dd = ld_dinv<V, PRE>(dinv, dc, i);
 #pragma unroll
       for (int u = 0; u < V; ++u) z.v[u] = z.v[u] * dd.v[u];
-    }
-    if constexpr (PRE == 2) {
-#pragma unroll
-      for (int u = 0; u < V; ++u) z.v[u] = z.v[u] * dc;
     }
     if (!first) {
       const Pack<V> pp = ld<V>(p, i);
@@ -196,14 +215,10 @@ __global__ __launch_bounds__(kBlock) void px_update_kernel(long n, const double 
       }
       st<V>(x, i, xx);
     }
-    if constexpr (PRE == 1) {
-      const Pack<V> dd = ld<V>(dinv, i);
+    if constexpr (PRE != 0) {
+      const Pack<V> dd = ld_dinv<V, PRE>(dinv, dc, i);
 #pragma unroll
       for (int u = 0; u < V; ++u) z.v[u] = z.v[u] * dd.v[u];
-    }
-    if constexpr (PRE == 2) {
-#pragma unroll
-      for (int u = 0; u < V; ++u) z.v[u] = z.v[u] * dc;
     }
     if (!first) {
 #pragma unroll
@@ -211,14 +226,7 @@ __global__ __launch_bounds__(kBlock) void px_update_kernel(long n, const double 
     }
     st<V>(p, i, z);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_down(dmax, off, 64);
-    if (o > dmax) dmax = o;
-  }
-  double acc[1];
-  acc[0] = ((threadIdx.x & 63) == 0 && (1.0 + dmax != 1.0)) ? 1.0 : 0.0;
-  block_reduce_store<1>(acc, partials + 2 * (size_t)kMaxParts);
+  nonstag_store(dmax, partials);
 }
 
 // ---- pcg.c:127-152 as TWO streaming kernels.  One fused pass over x, p, r, q, dinv (7 HBM
@@ -255,14 +263,7 @@ __global__ __launch_bounds__(kBlock) void x_update_kernel(long n, double alpha,
     }
     st<V>(x, i, xx);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_down(dmax, off, 64);
-    if (o > dmax) dmax = o;
-  }
-  double acc[1];
-  acc[0] = ((threadIdx.x & 63) == 0 && (1.0 + dmax != 1.0)) ? 1.0 : 0.0;
-  block_reduce_store<1>(acc, partials + 2 * (size_t)kMaxParts);
+  nonstag_store(dmax, partials);
 }
 
 //      r_update: r -= alpha q (:142-143); partial slots 0, 1 = {r.r, r.z}, z = dinv.*r or r
@@ -283,12 +284,7 @@ __global__ __launch_bounds__(kBlock) void r_update_kernel(long n, double alpha,
   PSP_VEC_LOOP(i, n) {
     const Pack<V> qq = ld<V>(q, i);
     Pack<V> rr = ld<V>(r, i);
-    Pack<V> dd;
-    if constexpr (PRE == 1) dd = ld<V>(dinv, i);
-    if constexpr (PRE == 2) {
-#pragma unroll
-      for (int u = 0; u < V; ++u) dd.v[u] = dc;
-    }
+    const Pack<V> dd = ld_dinv<V, PRE>(dinv, dc, i);
 #pragma unroll
     for (int u = 0; u < V; ++u) {
       const double t = upd ? rr.v[u] + malpha * qq.v[u] : rr.v[u];
@@ -390,12 +386,8 @@ __global__ __launch_bounds__(kBlock) void lanczos_kernel(
     const Pack<V> a = ld<V>(av, i);
     const Pack<V> vh = ld<V>(v_hat, i);
     Pack<V> vo = ld<V>(v_hat_old, i);
-    Pack<V> dd, yy;
-    if constexpr (PRE == 1) dd = ld<V>(dinv, i);
-    if constexpr (PRE == 2) {
-#pragma unroll
-      for (int u = 0; u < V; ++u) dd.v[u] = dc;
-    }
+    const Pack<V> dd = ld_dinv<V, PRE>(dinv, dc, i);
+    Pack<V> yy;
 #pragma unroll
     for (int u = 0; u < V; ++u) {
       const double nv = a.v[u] - c1 * vh.v[u] - c2 * vo.v[u];
@@ -515,15 +507,10 @@ __global__ __launch_bounds__(kBlock) void bicg_p_kernel(long n, const double *__
     }
     st<V>(p, i, pp);
     if constexpr (PRE != 0) {
+      const Pack<V> dd = ld_dinv<V, PRE>(dinv, dc, i);
       Pack<V> ph;
-      if constexpr (PRE == 1) {
-        const Pack<V> dd = ld<V>(dinv, i);
 #pragma unroll
-        for (int u = 0; u < V; ++u) ph.v[u] = pp.v[u] * dd.v[u];
-      } else {
-#pragma unroll
-        for (int u = 0; u < V; ++u) ph.v[u] = pp.v[u] * dc;
-      }
+      for (int u = 0; u < V; ++u) ph.v[u] = pp.v[u] * dd.v[u];
       st<V>(phat, i, ph);
     }
   }
@@ -546,15 +533,10 @@ __global__ __launch_bounds__(kBlock) void bicg_s_kernel(long n, const double *__
     for (int u = 0; u < V; ++u) ss.v[u] = 1.0 * rr.v[u] + (-alpha) * vv.v[u];
     st<V>(sv, i, ss);
     if constexpr (PRE != 0) {
+      const Pack<V> dd = ld_dinv<V, PRE>(dinv, dc, i);
       Pack<V> sh;
-      if constexpr (PRE == 1) {
-        const Pack<V> dd = ld<V>(dinv, i);
 #pragma unroll
-        for (int u = 0; u < V; ++u) sh.v[u] = ss.v[u] * dd.v[u];
-      } else {
-#pragma unroll
-        for (int u = 0; u < V; ++u) sh.v[u] = ss.v[u] * dc;
-      }
+      for (int u = 0; u < V; ++u) sh.v[u] = ss.v[u] * dd.v[u];
       st<V>(shat, i, sh);
     }
   }
@@ -610,13 +592,12 @@ __global__ __launch_bounds__(kBlock) void cgs_q_kernel(long n, const double *__r
   PSP_VEC_LOOP(i, n) {
     const Pack<V> uu = ld<V>(u, i), vv = ld<V>(v, i);
     Pack<V> xx = ld<V>(x, i), qq, t2;
-    Pack<V> dd;
-    if constexpr (PRE == 1) dd = ld<V>(dinv, i);
+    const Pack<V> dd = ld_dinv<V, PRE>(dinv, dc, i);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       qq.v[k] = upd ? 1.0 * uu.v[k] + (-alpha) * vv.v[k] : uu.v[k];
       const double t = 1.0 * uu.v[k] + 1.0 * qq.v[k];
-      t2.v[k] = PRE == 0 ? t : (PRE == 1 ? t * dd.v[k] : t * dc);
+      t2.v[k] = PRE == 0 ? t : t * dd.v[k];
       if (upd) xx.v[k] = 1.0 * xx.v[k] + alpha * t2.v[k];
     }
     st<V>(q, i, qq);
@@ -673,15 +654,10 @@ __global__ __launch_bounds__(kBlock) void cgs_p_kernel(long n, const double *__r
     st<V>(u, i, uu);
     st<V>(p, i, pn);
     if constexpr (PRE != 0) {
+      const Pack<V> dd = ld_dinv<V, PRE>(dinv, dc, i);
       Pack<V> kk;
-      if constexpr (PRE == 1) {
-        const Pack<V> dd = ld<V>(dinv, i);
 #pragma unroll
-        for (int k = 0; k < V; ++k) kk.v[k] = pn.v[k] * dd.v[k];
-      } else {
-#pragma unroll
-        for (int k = 0; k < V; ++k) kk.v[k] = pn.v[k] * dc;
-      }
+      for (int k = 0; k < V; ++k) kk.v[k] = pn.v[k] * dd.v[k];
       st<V>(kp, i, kk);
     }
   }
@@ -698,16 +674,12 @@ __global__ __launch_bounds__(kBlock) void qmrs_kv_kernel(long n, const double *_
   PSP_VEC_LOOP(i, n) {
     const Pack<V> vv = ld<V>(v1, i);
     Pack<V> ww = vv;
-    if constexpr (PRE == 1) {
-      const Pack<V> dd = ld<V>(dinv, i);
+    if constexpr (PRE != 0) {
+      const Pack<V> dd = ld_dinv<V, PRE>(dinv, dc, i);
 #pragma unroll
       for (int k = 0; k < V; ++k) ww.v[k] = vv.v[k] * dd.v[k];
+      st<V>(wrk1, i, ww);
     }
-    if constexpr (PRE == 2) {
-#pragma unroll
-      for (int k = 0; k < V; ++k) ww.v[k] = vv.v[k] * dc;
-    }
-    if constexpr (PRE != 0) st<V>(wrk1, i, ww);
 #pragma unroll
     for (int k = 0; k < V; ++k) acc[0] += ww.v[k] * vv.v[k];
   }
@@ -775,14 +747,13 @@ __global__ __launch_bounds__(kBlock) void qmrs_dx_kernel(long n, const double *_
   PSP_VEC_LOOP(i, n) {
     const Pack<V> pp = ld<V>(p, i);
     Pack<V> dd = ld<V>(d, i), xx = ld<V>(x, i), vv = ld<V>(v1, i), ww;
-    Pack<V> di;
-    if constexpr (PRE == 1) di = ld<V>(dinv, i);
+    const Pack<V> di = ld_dinv<V, PRE>(dinv, dc, i);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       dd.v[k] = eta * pp.v[k] + cc * dd.v[k];
       xx.v[k] = 1.0 * xx.v[k] + 1.0 * dd.v[k];
       vv.v[k] = rho1inv * vv.v[k];
-      ww.v[k] = PRE == 0 ? vv.v[k] : (PRE == 1 ? vv.v[k] * di.v[k] : vv.v[k] * dc);
+      ww.v[k] = PRE == 0 ? vv.v[k] : vv.v[k] * di.v[k];
       acc[0] += ww.v[k] * vv.v[k];
     }
     st<V>(d, i, dd);
@@ -883,13 +854,6 @@ __global__ void gather_kernel(int count, const int *__restrict__ idx, const doub
     out[i] = v[idx[i]];
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-template <typename... P>
-inline bool can_vec2(long n, P... ptrs) {
-  return (n % 2 == 0) && (aligned16(ptrs) && ...);
-}
-
 }  // namespace
 
 namespace {
@@ -955,496 +919,289 @@ bool dinv_constant(const double *v, long n, double *c) {
   return true;
 }
 
-// Launch helpers (device pointers, library stream).  `partials` = slot base in the workspace.
+// ---- Launch helpers (device pointers, library stream).  `partials` = slot base in the workspace.
+// One launch of a vector kernel is launch_vec / launch_vec_pre below; a k_* wrapper states what differs: the pointers its
+// kernel dereferences as Pack<V>, and the launch itself.  V = 2 (one 16-byte access per lane) needs n even and every
+// such pointer 16-byte aligned -- one missing from a wrapper's list is a misaligned access on the device.
+
+namespace {
+
+using Ptrs = std::initializer_list<const void *>;
+
+inline bool aligned16(Ptrs ptrs) {  // (a null pointer -- an operand the chosen form does not read -- passes)
+  for (const void *p : ptrs)
+    if ((uintptr_t)p & 15) return false;
+  return true;
+}
+
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+// f(std::true_type / std::false_type): a run-time flag as a template argument of the kernel
+template <typename F>
+inline void with_flag(bool flag, F &&f) {
+  if (flag) f(std::true_type{}); else f(std::false_type{});
+}
+
+// kernels without a preconditioner form: launch(grid, V) with V an Int<>; *nparts = grid for the wrappers that reduce
+template <typename F>
+int launch_vec(long n, Ptrs always, int *nparts, F &&launch) {
+  Workspace *w;
+  PSP_TRY(workspace(&w));
+  const int grid = vec_grid(*w, n);
+  if (n % 2 == 0 && aligned16(always)) launch(grid, Int<2>{}); else launch(grid, Int<1>{});
+  PSP_LAUNCH_CHECK();
+  if (nparts) *nparts = grid;
+  return PSP_OK;
+}
+
+// kernels with one: launch(grid, dc, V, PRE), PRE = 0 no dinv, 1 the dinv array, 2 dinv holds dc everywhere (one lookup
+// per launch: dinv_constant takes a lock).  `with_pre` are the pointers only the PRE != 0 forms dereference; the PRE = 1
+// form reads dinv as well.
+template <typename F>
+int launch_vec_pre(long n, const double *dinv, Ptrs always, Ptrs with_pre, int *nparts, F &&launch) {
+  Workspace *w;
+  PSP_TRY(workspace(&w));
+  const int grid = vec_grid(*w, n);
+  double dc = 0.0;
+  const int pre = !dinv ? 0 : dinv_constant(dinv, n, &dc) ? 2 : 1;
+  const bool v2 = n % 2 == 0 && aligned16(always) && (pre == 0 || aligned16(with_pre)) && (pre != 1 || aligned16({dinv}));
+  auto with_pre_form = [&](auto V) {
+    if (pre == 2) launch(grid, dc, V, Int<2>{});
+    else if (pre == 1) launch(grid, dc, V, Int<1>{});
+    else launch(grid, dc, V, Int<0>{});
+  };
+  if (v2) with_pre_form(Int<2>{}); else with_pre_form(Int<1>{});
+  PSP_LAUNCH_CHECK();
+  if (nparts) *nparts = grid;
+  return PSP_OK;
+}
+
+}  // namespace
+
+// (in the lambdas below V, PRE and the flags are std::integral_constant objects: decltype(V)::value is the constant)
 
 int k_dot(long n, const double *x, const double *y, double *partials, int *nparts) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, x, y))
-    hipLaunchKernelGGL(dot_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, x, y, partials);
-  else
-    hipLaunchKernelGGL(dot_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, x, y, partials);
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+  return launch_vec(n, {x, y}, nparts, [&](int grid, auto V) {
+    hipLaunchKernelGGL(dot_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, x, y, partials);
+  });
 }
 
-int k_residual(long n, const double *b, double *r, const double *dinv, double *partials,
-               int *nparts) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv && !cst ? can_vec2(n, b, r, dinv) : can_vec2(n, b, r);
-#define L(V, PRE)                                                                              \
-  hipLaunchKernelGGL((residual_kernel<V, PRE>), dim3(grid), dim3(kBlock), 0, stream(), n, b, r, \
-                     dinv, dc, partials)
-  if (cst) { if (v2) L(2, 2); else L(1, 2); }
-  else if (dinv) { if (v2) L(2, 1); else L(1, 1); }
-  else { if (v2) L(2, 0); else L(1, 0); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+int k_residual(long n, const double *b, double *r, const double *dinv, double *partials, int *nparts) {
+  return launch_vec_pre(n, dinv, {b, r}, {}, nparts, [&](int grid, double dc, auto V, auto PRE) {
+    hipLaunchKernelGGL((residual_kernel<decltype(V)::value, decltype(PRE)::value>), dim3(grid), dim3(kBlock), 0, stream(),
+                       n, b, r, dinv, dc, partials);
+  });
 }
 
-int k_pupdate(long n, const double *r, const double *dinv, double beta, bool first, double *p,
-              const PcgDev *dstate) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv && !cst ? can_vec2(n, r, p, dinv) : can_vec2(n, r, p);
-#define L(V, PRE, FIRST)                                                                  \
-  hipLaunchKernelGGL((pupdate_kernel<V, PRE, FIRST>), dim3(grid), dim3(kBlock), 0, stream(), n, \
-                     r, dinv, dc, beta, p, dstate)
-  if (cst) {
-    if (first) { if (v2) L(2, 2, true); else L(1, 2, true); }
-    else { if (v2) L(2, 2, false); else L(1, 2, false); }
-  } else if (dinv) {
-    if (first) { if (v2) L(2, 1, true); else L(1, 1, true); }
-    else { if (v2) L(2, 1, false); else L(1, 1, false); }
-  } else {
-    if (first) { if (v2) L(2, 0, true); else L(1, 0, true); }
-    else { if (v2) L(2, 0, false); else L(1, 0, false); }
-  }
-#undef L
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+int k_pupdate(long n, const double *r, const double *dinv, double beta, bool first, double *p, const PcgDev *dstate) {
+  return launch_vec_pre(n, dinv, {r, p}, {}, nullptr, [&](int grid, double dc, auto V, auto PRE) {
+    with_flag(first, [&](auto FIRST) {
+      hipLaunchKernelGGL((pupdate_kernel<decltype(V)::value, decltype(PRE)::value, decltype(FIRST)::value>), dim3(grid),
+                         dim3(kBlock), 0, stream(), n, r, dinv, dc, beta, p, dstate);
+    });
+  });
 }
 
-int k_px_update(long n, const double *r, const double *dinv, double *p, double *x, double *partials,
-                int *nparts, const PcgDev *dstate, double beta, double alpha, bool first, bool xpend) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv && !cst ? can_vec2(n, r, p, x, dinv) : can_vec2(n, r, p, x);
-#define L(V, PRE)                                                                          \
-  hipLaunchKernelGGL((px_update_kernel<V, PRE>), dim3(grid), dim3(kBlock), 0, stream(), n, r, \
-                     dinv, dc, p, x, partials, dstate, beta, alpha, first ? 1 : 0, xpend ? 1 : 0)
-  if (cst) { if (v2) L(2, 2); else L(1, 2); }
-  else if (dinv) { if (v2) L(2, 1); else L(1, 1); }
-  else { if (v2) L(2, 0); else L(1, 0); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+int k_px_update(long n, const double *r, const double *dinv, double *p, double *x, double *partials, int *nparts,
+                const PcgDev *dstate, double beta, double alpha, bool first, bool xpend) {
+  return launch_vec_pre(n, dinv, {r, p, x}, {}, nparts, [&](int grid, double dc, auto V, auto PRE) {
+    hipLaunchKernelGGL((px_update_kernel<decltype(V)::value, decltype(PRE)::value>), dim3(grid), dim3(kBlock), 0, stream(),
+                       n, r, dinv, dc, p, x, partials, dstate, beta, alpha, first ? 1 : 0, xpend ? 1 : 0);
+  });
 }
 
 // the two halves of k_xr_update on their own (lazy loop: r update per iteration, x update at the end)
-int k_x_update(long n, double alpha, const double *p, double *x, double *partials, int *nparts,
+int k_x_update(long n, double alpha, const double *p, double *x, double *partials, int *nparts, const PcgDev *dstate) {
+  return launch_vec(n, {p, x}, nparts, [&](int grid, auto V) {
+    hipLaunchKernelGGL(x_update_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, alpha, p, x,
+                       partials, dstate);
+  });
+}
+
+int k_r_update(long n, double alpha, const double *q, const double *dinv, double *r, double *partials, int *nparts,
                const PcgDev *dstate) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, p, x))
-    hipLaunchKernelGGL(x_update_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, alpha, p, x, partials, dstate);
-  else
-    hipLaunchKernelGGL(x_update_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, alpha, p, x, partials, dstate);
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+  return launch_vec_pre(n, dinv, {q, r}, {}, nparts, [&](int grid, double dc, auto V, auto PRE) {
+    hipLaunchKernelGGL((r_update_kernel<decltype(V)::value, decltype(PRE)::value>), dim3(grid), dim3(kBlock), 0, stream(),
+                       n, alpha, q, dinv, dc, r, partials, dstate);
+  });
 }
 
-int k_r_update(long n, double alpha, const double *q, const double *dinv, double *r, double *partials,
-               int *nparts, const PcgDev *dstate) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv && !cst ? can_vec2(n, q, r, dinv) : can_vec2(n, q, r);
-#define L(V, PRE)                                                                         \
-  hipLaunchKernelGGL((r_update_kernel<V, PRE>), dim3(grid), dim3(kBlock), 0, stream(), n, \
-                     alpha, q, dinv, dc, r, partials, dstate)
-  if (cst) { if (v2) L(2, 2); else L(1, 2); }
-  else if (dinv) { if (v2) L(2, 1); else L(1, 1); }
-  else { if (v2) L(2, 0); else L(1, 0); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
-}
-
-int k_xr_update(long n, double alpha, const double *p, const double *q, const double *dinv,
-                double *x, double *r, double *partials, int *nparts, const PcgDev *dstate) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, p, x))
-    hipLaunchKernelGGL(x_update_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, alpha, p, x,
-                       partials, dstate);
-  else
-    hipLaunchKernelGGL(x_update_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, alpha, p, x,
-                       partials, dstate);
-  PSP_LAUNCH_CHECK();
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv && !cst ? can_vec2(n, q, r, dinv) : can_vec2(n, q, r);
-#define L(V, PRE)                                                                         \
-  hipLaunchKernelGGL((r_update_kernel<V, PRE>), dim3(grid), dim3(kBlock), 0, stream(), n, \
-                     alpha, q, dinv, dc, r, partials, dstate)
-  if (cst) { if (v2) L(2, 2); else L(1, 2); }
-  else if (dinv) { if (v2) L(2, 1); else L(1, 1); }
-  else { if (v2) L(2, 0); else L(1, 0); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+int k_xr_update(long n, double alpha, const double *p, const double *q, const double *dinv, double *x, double *r,
+                double *partials, int *nparts, const PcgDev *dstate) {
+  PSP_TRY(k_x_update(n, alpha, p, x, partials, nparts, dstate));
+  return k_r_update(n, alpha, q, dinv, r, partials, nparts, dstate);
 }
 
 int k_jacobi_first(long n, const double *x, const double *dinv, double *y) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, x, dinv, y))
-    hipLaunchKernelGGL(jacobi_first_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, x, dinv, y);
-  else
-    hipLaunchKernelGGL(jacobi_first_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, x, dinv, y);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+  return launch_vec(n, {x, dinv, y}, nullptr, [&](int grid, auto V) {
+    hipLaunchKernelGGL(jacobi_first_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, x, dinv, y);
+  });
 }
 
 int k_jacobi_sweep(long n, const double *x, const double *dinv, const double *temp, double *y) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, x, dinv, temp, y))
-    hipLaunchKernelGGL(jacobi_sweep_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, x, dinv,
-                       temp, y);
-  else
-    hipLaunchKernelGGL(jacobi_sweep_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, x, dinv,
-                       temp, y);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+  return launch_vec(n, {x, dinv, temp, y}, nullptr, [&](int grid, auto V) {
+    hipLaunchKernelGGL(jacobi_sweep_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, x, dinv, temp, y);
+  });
 }
 
 int k_dinv(long n, const double *diag, double omega, double *dinv, double *partials, int *nparts) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, diag, dinv))
-    hipLaunchKernelGGL(dinv_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, diag, omega, dinv,
+  return launch_vec(n, {diag, dinv}, nparts, [&](int grid, auto V) {
+    hipLaunchKernelGGL(dinv_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, diag, omega, dinv,
                        partials);
-  else
-    hipLaunchKernelGGL(dinv_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, diag, omega, dinv,
-                       partials);
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+  });
 }
 
 int k_scale_div(long n, const double *y, double beta, double *v, const MinresDev *ds) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, y, v))
-    hipLaunchKernelGGL(scale_div_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, y, beta, v, ds);
-  else
-    hipLaunchKernelGGL(scale_div_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, y, beta, v, ds);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+  return launch_vec(n, {y, v}, nullptr, [&](int grid, auto V) {
+    hipLaunchKernelGGL(scale_div_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, y, beta, v, ds);
+  });
 }
 
-int k_lanczos(long n, const double *av, double c1, double c2, const double *v_hat, double *v_hat_old,
-              const double *dinv, double *y, double *partials, int *nparts, const MinresDev *ds) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv ? (cst ? can_vec2(n, av, v_hat, v_hat_old, y) : can_vec2(n, av, v_hat, v_hat_old, dinv, y))
-                       : can_vec2(n, av, v_hat, v_hat_old);
-#define L(V, PRE)                                                                              \
-  hipLaunchKernelGGL((lanczos_kernel<V, PRE>), dim3(grid), dim3(kBlock), 0, stream(), n, av, c1, \
-                     c2, v_hat, v_hat_old, dinv, dc, y, partials, ds)
-  if (cst) { if (v2) L(2, 2); else L(1, 2); }
-  else if (dinv) { if (v2) L(2, 1); else L(1, 1); }
-  else { if (v2) L(2, 0); else L(1, 0); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+int k_lanczos(long n, const double *av, double c1, double c2, const double *v_hat, double *v_hat_old, const double *dinv,
+              double *y, double *partials, int *nparts, const MinresDev *ds) {
+  return launch_vec_pre(n, dinv, {av, v_hat, v_hat_old}, {y}, nparts, [&](int grid, double dc, auto V, auto PRE) {
+    hipLaunchKernelGGL((lanczos_kernel<decltype(V)::value, decltype(PRE)::value>), dim3(grid), dim3(kBlock), 0, stream(),
+                       n, av, c1, c2, v_hat, v_hat_old, dinv, dc, y, partials, ds);
+  });
 }
 
-int k_lanczos_plain(long n, const double *av, double c1, double c2, const double *v_hat,
-                    double *v_hat_old) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, av, v_hat, v_hat_old))
-    hipLaunchKernelGGL(lanczos_plain_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, av, c1,
-                       c2, v_hat, v_hat_old);
-  else
-    hipLaunchKernelGGL(lanczos_plain_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, av, c1,
-                       c2, v_hat, v_hat_old);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+int k_lanczos_plain(long n, const double *av, double c1, double c2, const double *v_hat, double *v_hat_old) {
+  return launch_vec(n, {av, v_hat, v_hat_old}, nullptr, [&](int grid, auto V) {
+    hipLaunchKernelGGL(lanczos_plain_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, av, c1, c2,
+                       v_hat, v_hat_old);
+  });
 }
 
 int k_lin2(long n, double a, const double *x, double b, const double *y, double *z) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, x, y, z))
-    hipLaunchKernelGGL(lin2_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, a, x, b, y, z);
-  else
-    hipLaunchKernelGGL(lin2_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, a, x, b, y, z);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+  return launch_vec(n, {x, y, z}, nullptr, [&](int grid, auto V) {
+    hipLaunchKernelGGL(lin2_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, a, x, b, y, z);
+  });
 }
 
 int k_bicg_p(long n, const double *r, const double *v, double *p, double *phat, const double *dinv, double beta,
              double omega, bool first, KryArg ka) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv ? (cst ? can_vec2(n, r, v, p, phat) : can_vec2(n, r, v, p, phat, dinv)) : can_vec2(n, r, v, p);
-#define L(V, PRE)                                                                                       \
-  hipLaunchKernelGGL((bicg_p_kernel<V, PRE>), dim3(grid), dim3(kBlock), 0, stream(), n, r, v, p, phat, \
-                     dinv, dc, beta, omega, first ? 1 : 0, ka)
-  if (cst) { if (v2) L(2, 2); else L(1, 2); }
-  else if (dinv) { if (v2) L(2, 1); else L(1, 1); }
-  else { if (v2) L(2, 0); else L(1, 0); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+  return launch_vec_pre(n, dinv, {r, v, p}, {phat}, nullptr, [&](int grid, double dc, auto V, auto PRE) {
+    hipLaunchKernelGGL((bicg_p_kernel<decltype(V)::value, decltype(PRE)::value>), dim3(grid), dim3(kBlock), 0, stream(),
+                       n, r, v, p, phat, dinv, dc, beta, omega, first ? 1 : 0, ka);
+  });
 }
 
-int k_bicg_s(long n, const double *r, const double *v, double *s, double *shat, const double *dinv, double alpha, KryArg ka) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv ? (cst ? can_vec2(n, r, v, s, shat) : can_vec2(n, r, v, s, shat, dinv)) : can_vec2(n, r, v, s);
-#define L(V, PRE)                                                                                    \
-  hipLaunchKernelGGL((bicg_s_kernel<V, PRE>), dim3(grid), dim3(kBlock), 0, stream(), n, r, v, s, shat, \
-                     dinv, dc, alpha, ka)
-  if (cst) { if (v2) L(2, 2); else L(1, 2); }
-  else if (dinv) { if (v2) L(2, 1); else L(1, 1); }
-  else { if (v2) L(2, 0); else L(1, 0); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+int k_bicg_s(long n, const double *r, const double *v, double *s, double *shat, const double *dinv, double alpha,
+             KryArg ka) {
+  return launch_vec_pre(n, dinv, {r, v, s}, {shat}, nullptr, [&](int grid, double dc, auto V, auto PRE) {
+    hipLaunchKernelGGL((bicg_s_kernel<decltype(V)::value, decltype(PRE)::value>), dim3(grid), dim3(kBlock), 0, stream(),
+                       n, r, v, s, shat, dinv, dc, alpha, ka);
+  });
 }
 
 int k_bicg_xr(long n, double *x, const double *phat, const double *shat, const double *s, const double *t, double *r,
               const double *rhat, double alpha, double omega, double *partials, int *nparts, KryArg ka) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, x, phat, shat, s, t, r, rhat))
-    hipLaunchKernelGGL(bicg_xr_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, x, phat, shat, s, t, r, rhat,
-                       alpha, omega, partials, ka);
-  else
-    hipLaunchKernelGGL(bicg_xr_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, x, phat, shat, s, t, r, rhat,
-                       alpha, omega, partials, ka);
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+  return launch_vec(n, {x, phat, shat, s, t, r, rhat}, nparts, [&](int grid, auto V) {
+    hipLaunchKernelGGL(bicg_xr_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, x, phat, shat, s, t,
+                       r, rhat, alpha, omega, partials, ka);
+  });
 }
 
 int k_cgs_q(long n, const double *u, const double *v, double *x, double *q, double *tmp2, const double *dinv,
             double alpha, KryArg ka) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv && !cst ? can_vec2(n, u, v, x, q, tmp2, dinv) : can_vec2(n, u, v, x, q, tmp2);
-#define L(V, PRE)                                                                                       \
-  hipLaunchKernelGGL((cgs_q_kernel<V, PRE>), dim3(grid), dim3(kBlock), 0, stream(), n, u, v, x, q, tmp2, \
-                     dinv, dc, alpha, ka)
-  if (cst) { if (v2) L(2, 2); else L(1, 2); }
-  else if (dinv) { if (v2) L(2, 1); else L(1, 1); }
-  else { if (v2) L(2, 0); else L(1, 0); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+  return launch_vec_pre(n, dinv, {u, v, x, q, tmp2}, {}, nullptr, [&](int grid, double dc, auto V, auto PRE) {
+    hipLaunchKernelGGL((cgs_q_kernel<decltype(V)::value, decltype(PRE)::value>), dim3(grid), dim3(kBlock), 0, stream(),
+                       n, u, v, x, q, tmp2, dinv, dc, alpha, ka);
+  });
 }
 
-int k_cgs_r(long n, double *r, const double *t, const double *r0, double alpha, double *partials, int *nparts, KryArg ka) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, r, t, r0))
-    hipLaunchKernelGGL(cgs_r_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, r, t, r0, alpha, partials, ka);
-  else
-    hipLaunchKernelGGL(cgs_r_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, r, t, r0, alpha, partials, ka);
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+int k_cgs_r(long n, double *r, const double *t, const double *r0, double alpha, double *partials, int *nparts,
+            KryArg ka) {
+  return launch_vec(n, {r, t, r0}, nparts, [&](int grid, auto V) {
+    hipLaunchKernelGGL(cgs_r_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, r, t, r0, alpha,
+                       partials, ka);
+  });
 }
 
-int k_cgs_p(long n, const double *r, const double *q, double *p, double *u, double *kp, const double *dinv,
-            double beta, KryArg ka) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv ? (cst ? can_vec2(n, r, q, p, u, kp) : can_vec2(n, r, q, p, u, kp, dinv)) : can_vec2(n, r, q, p, u);
-#define L(V, PRE)                                                                                    \
-  hipLaunchKernelGGL((cgs_p_kernel<V, PRE>), dim3(grid), dim3(kBlock), 0, stream(), n, r, q, p, u, kp, \
-                     dinv, dc, beta, ka)
-  if (cst) { if (v2) L(2, 2); else L(1, 2); }
-  else if (dinv) { if (v2) L(2, 1); else L(1, 1); }
-  else { if (v2) L(2, 0); else L(1, 0); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+int k_cgs_p(long n, const double *r, const double *q, double *p, double *u, double *kp, const double *dinv, double beta,
+            KryArg ka) {
+  return launch_vec_pre(n, dinv, {r, q, p, u}, {kp}, nullptr, [&](int grid, double dc, auto V, auto PRE) {
+    hipLaunchKernelGGL((cgs_p_kernel<decltype(V)::value, decltype(PRE)::value>), dim3(grid), dim3(kBlock), 0, stream(),
+                       n, r, q, p, u, kp, dinv, dc, beta, ka);
+  });
 }
 
 int k_qmrs_kv(long n, const double *v1, double *wrk1, const double *dinv, double *partials, int *nparts) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv ? (cst ? can_vec2(n, v1, wrk1) : can_vec2(n, v1, wrk1, dinv)) : can_vec2(n, v1);
-#define L(V, PRE)                                                                                      \
-  hipLaunchKernelGGL((qmrs_kv_kernel<V, PRE>), dim3(grid), dim3(kBlock), 0, stream(), n, v1, wrk1, dinv, \
-                     dc, partials)
-  if (cst) { if (v2) L(2, 2); else L(1, 2); }
-  else if (dinv) { if (v2) L(2, 1); else L(1, 1); }
-  else { if (v2) L(2, 0); else L(1, 0); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+  return launch_vec_pre(n, dinv, {v1}, {wrk1}, nparts, [&](int grid, double dc, auto V, auto PRE) {
+    hipLaunchKernelGGL((qmrs_kv_kernel<decltype(V)::value, decltype(PRE)::value>), dim3(grid), dim3(kBlock), 0, stream(),
+                       n, v1, wrk1, dinv, dc, partials);
+  });
 }
 
 int k_qmrs_pg(long n, const double *v1, const double *wrk1, double *p, double *g, double cc, KryArg ka) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, v1, wrk1, p, g))
-    hipLaunchKernelGGL(qmrs_pg_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, v1, wrk1, p, g, cc, ka);
-  else
-    hipLaunchKernelGGL(qmrs_pg_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, v1, wrk1, p, g, cc, ka);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+  return launch_vec(n, {v1, wrk1, p, g}, nullptr, [&](int grid, auto V) {
+    hipLaunchKernelGGL(qmrs_pg_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, v1, wrk1, p, g, cc,
+                       ka);
+  });
 }
 
 int k_qmrs_v(long n, const double *t, double *v1, double beta, double *partials, int *nparts, KryArg ka) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, t, v1))
-    hipLaunchKernelGGL(qmrs_v_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, t, v1, beta, partials, ka);
-  else
-    hipLaunchKernelGGL(qmrs_v_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, t, v1, beta, partials, ka);
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+  return launch_vec(n, {t, v1}, nparts, [&](int grid, auto V) {
+    hipLaunchKernelGGL(qmrs_v_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, t, v1, beta, partials,
+                       ka);
+  });
 }
 
 int k_qmrs_dx(long n, const double *p, double *d, double *x, double *v1, double *wrk1, const double *dinv, double eta,
               double cc, double rho1inv, double *partials, int *nparts, KryArg ka) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  double dc = 0.0;
-  const bool cst = dinv && dinv_constant(dinv, n, &dc);
-  const bool v2 = dinv ? (cst ? can_vec2(n, p, d, x, v1, wrk1) : can_vec2(n, p, d, x, v1, wrk1, dinv))
-                       : can_vec2(n, p, d, x, v1);
-#define L(V, PRE)                                                                                          \
-  hipLaunchKernelGGL((qmrs_dx_kernel<V, PRE>), dim3(grid), dim3(kBlock), 0, stream(), n, p, d, x, v1, wrk1, \
-                     dinv, dc, eta, cc, rho1inv, partials, ka)
-  if (cst) { if (v2) L(2, 2); else L(1, 2); }
-  else if (dinv) { if (v2) L(2, 1); else L(1, 1); }
-  else { if (v2) L(2, 0); else L(1, 0); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+  return launch_vec_pre(n, dinv, {p, d, x, v1}, {wrk1}, nparts, [&](int grid, double dc, auto V, auto PRE) {
+    hipLaunchKernelGGL((qmrs_dx_kernel<decltype(V)::value, decltype(PRE)::value>), dim3(grid), dim3(kBlock), 0, stream(),
+                       n, p, d, x, v1, wrk1, dinv, dc, eta, cc, rho1inv, partials, ka);
+  });
 }
 
+// z == nullptr: the SELF form (y.y), which reads no z
 int k_axpy_dot(long n, double a, const double *x, double *y, const double *z, double *partials, int *nparts,
                const double *neg_a_dev) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  const bool v2 = z ? can_vec2(n, x, y, z) : can_vec2(n, x, y);
-#define L(V, SELF)                                                                                      \
-  hipLaunchKernelGGL((axpy_dot_kernel<V, SELF>), dim3(grid), dim3(kBlock), 0, stream(), n, a, x, y, z, partials, neg_a_dev)
-  if (z) { if (v2) L(2, false); else L(1, false); }
-  else { if (v2) L(2, true); else L(1, true); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+  return launch_vec(n, {x, y, z}, nparts, [&](int grid, auto V) {
+    with_flag(z == nullptr, [&](auto SELF) {
+      hipLaunchKernelGGL((axpy_dot_kernel<decltype(V)::value, decltype(SELF)::value>), dim3(grid), dim3(kBlock), 0,
+                         stream(), n, a, x, y, z, partials, neg_a_dev);
+    });
+  });
 }
 
 int k_axpy_dot_chain(long n, const double *prev, int np_prev, double *h_out, const double *x, double *y, const double *z,
                      double *partials, int *nparts) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
   if (np_prev < 1 || np_prev > 4096) return fail(PSP_EINVAL, "k_axpy_dot_chain: %d partial sums", np_prev);
-  const int grid = vec_grid(*w, n);
-  const bool v2 = z ? can_vec2(n, x, y, z) : can_vec2(n, x, y);
-#define L(V, SELF)                                                                                                 \
-  hipLaunchKernelGGL((axpy_dot_chain_kernel<V, SELF>), dim3(grid), dim3(kBlock), 0, stream(), n, prev, np_prev, h_out, x, y, \
-                     z, partials)
-  if (z) { if (v2) L(2, false); else L(1, false); }
-  else { if (v2) L(2, true); else L(1, true); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  *nparts = grid;
-  return PSP_OK;
+  return launch_vec(n, {x, y, z}, nparts, [&](int grid, auto V) {
+    with_flag(z == nullptr, [&](auto SELF) {
+      hipLaunchKernelGGL((axpy_dot_chain_kernel<decltype(V)::value, decltype(SELF)::value>), dim3(grid), dim3(kBlock), 0,
+                         stream(), n, prev, np_prev, h_out, x, y, z, partials);
+    });
+  });
 }
 
 int k_scal(long n, double a, double *x) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, x))
-    hipLaunchKernelGGL(scal_kernel<2>, dim3(grid), dim3(kBlock), 0, stream(), n, a, x);
-  else
-    hipLaunchKernelGGL(scal_kernel<1>, dim3(grid), dim3(kBlock), 0, stream(), n, a, x);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+  return launch_vec(n, {x}, nullptr, [&](int grid, auto V) {
+    hipLaunchKernelGGL(scal_kernel<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, stream(), n, a, x);
+  });
 }
 
-int k_minres_wx(long n, const double *v, double r1, double r2, double r3, double c_eta, const double *w_,
-                double *w_old, double *x, bool scaled, double vdiv, const MinresDev *ds) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  const bool v2 = can_vec2(n, v, w_, w_old, x);
+int k_minres_wx(long n, const double *v, double r1, double r2, double r3, double c_eta, const double *w_, double *w_old,
+                double *x, bool scaled, double vdiv, const MinresDev *ds) {
   double *vm = const_cast<double *>(v);  // (only the VNEXT form writes v)
-#define L(V, S)                                                                                   \
-  hipLaunchKernelGGL((minres_wx_kernel<V, S>), dim3(grid), dim3(kBlock), 0, stream(), n, vm, vdiv, r1, \
-                     r2, r3, c_eta, w_, w_old, x, ds, (const double *)nullptr)
-  if (scaled) { if (v2) L(2, true); else L(1, true); }
-  else { if (v2) L(2, false); else L(1, false); }
-#undef L
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+  return launch_vec(n, {v, w_, w_old, x}, nullptr, [&](int grid, auto V) {
+    with_flag(scaled, [&](auto SCALED) {
+      hipLaunchKernelGGL((minres_wx_kernel<decltype(V)::value, decltype(SCALED)::value>), dim3(grid), dim3(kBlock), 0,
+                         stream(), n, vm, vdiv, r1, r2, r3, c_eta, w_, w_old, x, ds, (const double *)nullptr);
+    });
+  });
 }
 
 // the w / x update of the running iteration AND v = ynext / beta of the next one (device-resident scalars, unscaled products)
 int k_minres_wx_vnext(long n, double *v, const double *ynext, const double *w_, double *w_old, double *x,
                       const MinresDev *ds) {
-  Workspace *w;
-  PSP_TRY(workspace(&w));
-  const int grid = vec_grid(*w, n);
-  if (can_vec2(n, v, w_, w_old, x) && can_vec2(n, ynext, v))
-    hipLaunchKernelGGL((minres_wx_kernel<2, false, true>), dim3(grid), dim3(kBlock), 0, stream(), n, v, 1.0, 0.0, 0.0, 0.0,
-                       0.0, w_, w_old, x, ds, ynext);
-  else
-    hipLaunchKernelGGL((minres_wx_kernel<1, false, true>), dim3(grid), dim3(kBlock), 0, stream(), n, v, 1.0, 0.0, 0.0, 0.0,
-                       0.0, w_, w_old, x, ds, ynext);
-  PSP_LAUNCH_CHECK();
-  return PSP_OK;
+  return launch_vec(n, {v, w_, w_old, x, ynext}, nullptr, [&](int grid, auto V) {
+    hipLaunchKernelGGL((minres_wx_kernel<decltype(V)::value, false, true>), dim3(grid), dim3(kBlock), 0, stream(), n, v,
+                       1.0, 0.0, 0.0, 0.0, 0.0, w_, w_old, x, ds, ynext);
+  });
 }
 
 }  // namespace psp

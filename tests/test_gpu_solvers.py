@@ -752,3 +752,183 @@ def test_concurrent_solves_from_python_threads(oracle):
             t.join()
         for (r0, x0, y0), (r1, x1, y1) in zip(alone, got):
             assert r0 == r1 and np.array_equal(x0, x1) and np.array_equal(y0, y1)
+
+
+PHASE_ALPHA, PHASE_BETA, GUARD = 0.37, -1.3, 777.0
+
+
+def _phase_kernels(n, off, dh, hinted):
+    """Every phase entry point of the C ABI that ends in a vector-kernel wrapper, on vectors that start `off` doubles
+    into buffers of n + 2 (the two doubles around a vector hold GUARD and must come back untouched).
+    -> {name: vector or reduction results}"""
+    from pysparse_amd import device as dev
+    from pysparse_amd._capi import check, lib
+    L = lib()
+    rng = np.random.default_rng(n)
+    b, r, p, q, x = (rng.standard_normal(n) for _ in range(5))
+    keep = []
+
+    def put(a):
+        full = np.full(n + 2, GUARD)
+        full[off:off + n] = a
+        keep.append(dev.DeviceBuffer.from_host(full))
+        return keep[-1]
+
+    def at(buf):
+        return buf.ptr + 8 * off
+
+    def get(buf):
+        full = buf.download()
+        assert (np.delete(full, slice(off, off + n)) == GUARD).all()
+        return full[off:off + n].copy()
+
+    out = dev.DeviceBuffer(4)
+
+    def sums(k):
+        return out.download()[:k].copy()
+
+    db, dr, dp, dq, dx = put(b), put(r), put(p), put(q), put(x)
+    dptr = None if dh is None else at(put(dh))
+    res = {}
+    if hinted:
+        check(L.psp_k_hint_constant(dptr, n))
+    try:
+        t = put(r)
+        check(L.psp_k_residual(n, at(db), at(t), dptr, out.ptr))
+        res["residual.r"], res["residual.sums"] = get(t), sums(2)
+        for first in (1, 0):
+            t = put(p)
+            check(L.psp_k_pupdate(n, at(dr), dptr, PHASE_BETA, first, at(t)))
+            res["pupdate%d.p" % first] = get(t)
+        for first, xpend in ((0, 1), (1, 0)):
+            tp, tx = put(p), put(x)
+            check(L.psp_k_px_update(n, at(dr), dptr, PHASE_BETA, first, PHASE_ALPHA, xpend, at(tp), at(tx), out.ptr))
+            key = "px_update%d%d" % (first, xpend)
+            res[key + ".p"], res[key + ".x"], res[key + ".nonstag"] = get(tp), get(tx), sums(1)
+        t = put(x)
+        check(L.psp_k_x_update(n, PHASE_ALPHA, at(dp), at(t), out.ptr))
+        res["x_update.x"], res["x_update.nonstag"] = get(t), sums(1)
+        t = put(r)
+        check(L.psp_k_r_update(n, PHASE_ALPHA, at(dq), dptr, at(t), out.ptr))
+        res["r_update.r"], res["r_update.sums"] = get(t), sums(2)
+        tx, tr = put(x), put(r)
+        check(L.psp_k_xr_update(n, PHASE_ALPHA, at(dp), at(dq), dptr, at(tx), at(tr), out.ptr))
+        res["xr_update.x"], res["xr_update.r"], res["xr_update.sums"] = get(tx), get(tr), sums(3)
+        if dh is not None:
+            t = put(np.zeros(n))
+            check(L.psp_k_jacobi(n, at(dx), dptr, at(t)))
+            res["jacobi.y"] = get(t)
+    finally:
+        if hinted:
+            check(L.psp_k_unhint(dptr))
+    for buf in (db, dr, dp, dq, dx):  # the inputs are read only
+        get(buf)
+    return res, (b, r, p, q, x)
+
+
+@pytest.mark.parametrize("form", ["none", "array", "constant"])
+@pytest.mark.parametrize("n", [1000, 4097])
+def test_phase_kernels_at_both_alignments_and_every_preconditioner_form(n, form):
+    """The 16-byte-per-lane form of a vector kernel runs only when n is even and every pointer it dereferences that way is
+    16-byte aligned; the preconditioner is absent, an array, or a hinted constant.  n = 1000: two spans, the second ragged;
+    n = 4097: odd (8-byte accesses wherever the vectors sit), nine workgroups.  Every output vector and reduction result is
+    bit-identical between byte offsets 0 and 8 and between the hinted and the unhinted constant dinv, the vectors equal
+    the NumPy expression of the update (unfused per-element arithmetic), the sums agree with it to 1e-12."""
+    rng = np.random.default_rng(7)
+    dh = {"none": None, "array": 1.0 / (4.0 + rng.random(n)), "constant": np.full(n, 1.0 / 6.0)}[form]
+    runs = [_phase_kernels(n, off, dh, hinted) for hinted in ((False, True) if form == "constant" else (False,))
+            for off in (0, 1)]
+    res, (b, r, p, q, x) = runs[0]
+    for other, _ in runs[1:]:
+        assert other.keys() == res.keys()
+        for k in res:
+            assert np.array_equal(res[k], other[k]), k
+    al, be = PHASE_ALPHA, PHASE_BETA
+    K = (lambda v: v) if dh is None else (lambda v: v * dh)
+
+    def rr_rz(v):
+        return np.array([np.dot(v, v), np.dot(v, K(v))])
+
+    rn = r + (-al) * q
+    want = {"residual.r": b - r, "pupdate1.p": K(r), "pupdate0.p": K(r) + be * p,
+            "px_update01.p": K(r) + be * p, "px_update01.x": x + al * p, "px_update10.p": K(r), "px_update10.x": x,
+            "x_update.x": x + al * p, "r_update.r": rn, "xr_update.x": x + al * p, "xr_update.r": rn}
+    if dh is not None:
+        want["jacobi.y"] = x * dh
+    for k, v in want.items():
+        assert np.array_equal(res[k], v), k
+    for k, v in (("residual.sums", rr_rz(b - r)), ("r_update.sums", rr_rz(rn)), ("xr_update.sums", rr_rz(rn))):
+        assert (np.abs(res[k][:2] - v) <= 1e-12 * np.abs(v)).all(), (k, res[k], v)
+        if dh is None:
+            assert res[k][1] == res[k][0]
+    # |alpha p / x| is far above eps somewhere in every wave: not stagnated; no pending update, nothing scanned
+    assert res["x_update.nonstag"][0] != 0.0 and res["xr_update.sums"][2] != 0.0 and res["px_update01.nonstag"][0] != 0.0
+    assert res["px_update10.nonstag"][0] == 0.0
+
+
+def _odd_systems(O):
+    """poisson_csr(33, 31): n = 1023 is odd, so every vector kernel takes its 8-byte form; the constant diagonal makes
+    Jacobi the constant-dinv form, the same matrix with its diagonal perturbed row by row (still symmetric) the array form"""
+    A = O.poisson_csr(33, 31)
+    n = A.shape[0]
+    rows = np.repeat(np.arange(n), np.diff(A.ind))
+    val = A.val.copy()
+    val[A.col == rows] += 0.5 + 0.4 * np.sin(np.arange(n) * 0.01)
+    return {"constant": A, "variable": O.CSR(A.shape, val, A.col, A.ind)}
+
+
+def _check_odd_solve(O, solver, A, b, jacobi, got):
+    """got = (info, iter, x) of a device solve with tol = 0, maxit = 10 against the oracle's restatement: the bar
+    krylov_cases.check_against_golden applies to fixed-iteration cases"""
+    K = ("jacobi", O.jacobi_dinv(A.diagonal()), 1) if jacobi else None
+    xo = np.zeros(A.shape[0])
+    with np.errstate(all="ignore"):
+        info, it, _, _ = O.solve(solver, A, b, xo, 0.0, 10, K, dim=20)
+    assert (got[0], got[1]) == (info, it), (solver, jacobi, got[:2], (info, it))
+    assert np.abs(got[2] - xo).max() <= 1e-12 * np.abs(xo).max(), (solver, jacobi, relerr(got[2], xo))
+
+
+@pytest.mark.parametrize("solver", ["cgs", "bicgstab", "qmrs", "gmres"])
+def test_fused_krylov_passes_at_odd_n(oracle, solver):
+    """The fused passes of cgs / bicgstab / qmrs / gmres(20) have no entry point of their own: ten iterations on an odd-sized
+    system, where their 8-byte forms run, without a preconditioner and with Jacobi in both of its forms."""
+    from pysparse_amd import device as dev
+    for name, A in _odd_systems(oracle).items():
+        n = A.shape[0]
+        D = dev.DeviceCSR.from_arrays(A.shape, A.ind, A.col, A.val)
+        b = np.random.default_rng(11).standard_normal(n)
+        for jacobi in (False, True):
+            x = np.zeros(n)
+            kw = {"dim": 20} if solver == "gmres" else {}
+            r = getattr(dev, solver)(D, b, x, 0.0, 10, dev.DeviceJacobi(D) if jacobi else None, **kw)
+            _check_odd_solve(oracle, solver, A, b, jacobi, (r[0], r[1], x))
+
+
+def test_launch_per_phase_pcg_and_minres_at_odd_n(oracle):
+    """The same for pcg and minres.  A system of this size runs in the single-kernel loops by default, so the solves
+    run in a child process with those switched off: the launch-per-phase loops, and with them the vector kernels."""
+    import subprocess
+    import sys
+    systems = _odd_systems(oracle)
+    n = 1023
+    b = np.random.default_rng(11).standard_normal(n)
+    code = (
+        "import sys, json, numpy as np; sys.path.insert(0, %r); sys.path.insert(0, %r);"
+        "from pysparse_amd import device as dev; from oracle import oracle as O; import test_gpu_solvers as T;"
+        "out = [];\n"
+        "b = np.random.default_rng(11).standard_normal(%d)\n"
+        "for name, A in T._odd_systems(O).items():\n"
+        "    D = dev.DeviceCSR.from_arrays(A.shape, A.ind, A.col, A.val)\n"
+        "    for solver in ('pcg', 'minres'):\n"
+        "        for jacobi in (False, True):\n"
+        "            x = np.zeros(len(b)); r = getattr(dev, solver)(D, b, x, 0.0, 10, dev.DeviceJacobi(D) if jacobi else None)\n"
+        "            out.append([name, solver, jacobi, r[0], r[1], x.tobytes().hex(), dev.last_solve_info()[0]])\n"
+        "print(json.dumps(out))"
+    ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)), n)
+    e = dict(os.environ, PSP_TUNING="1", PSP_COOP="0")
+    out = subprocess.run([sys.executable, "-c", code], env=e, capture_output=True, text=True, check=True).stdout
+    got = json.loads(out.strip().splitlines()[-1])
+    assert len(got) == 8
+    for name, solver, jacobi, info, it, xhex, loop in got:
+        assert loop in ("pcg_eager", "pcg_lazy", "pcg_lazy_pf", "minres_async"), loop  # a launch-per-phase loop ran
+        _check_odd_solve(oracle, solver, systems[name], b, jacobi, (info, it, np.frombuffer(bytes.fromhex(xhex))))
