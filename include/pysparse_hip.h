@@ -469,6 +469,24 @@ int psp_mg_create_sss_line(psp_sss_t *A, int ndim, const int *grid, double omega
 /* the line axis of a handle created by psp_mg_create_*_line, -1 for every other handle */
 int psp_mg_line_axis(const psp_mg_t *K, int *axis);
 
+/* precon.multigrid(A, grid, omega, steps, galerkin=True, stencil='box'): the Galerkin cycle for symmetric operators with the
+ * full pattern {-1, 0, 1}^ndim -- 9 points in 2-D, 27 in 3-D (Q1 finite elements, the compact 9-point Laplacian, -div(kappa
+ * grad u) with kappa per cell); DESIGN.md 9i.  A flag of psp_mg_create_csr_ex / _sss_ex, valid only together with
+ * PSP_MG_GALERKIN (PSP_EINVAL without it); PSP_MG_SINGLE may be added.  Row r and column c are split into grid coordinates
+ * (r = r0 + n0 r1 + n0 n1 r2): an entry is accepted iff c_a - r_a lies in {-1, 0, 1} on every axis, so an entry that wraps
+ * across a line end is an offset violation and an axis of length 1 never carries a difference.  As for the axis pattern no
+ * entry may be stored twice, the diagonal is stored, finite and > 0, and A[r, c] has the bits of A[c, r] (a neighbour that
+ * is not stored counts as +0.0); PSP_EINVAL names the first kind in the order offset, duplicate, diagonal, symmetry.  Level 0
+ * is stored in the layout of every lower level: the diagonal, omega / diagonal and all (3^ndim - 1) / 2 lower arrays (15
+ * arrays per point in 3-D against 5 of an axis handle), and the cycle's kernels take it as they take the lower levels; the
+ * level grids, transfers, tail, dense coarsest solve, launches and determinism are PSP_MG_GALERKIN's.  The Galerkin products
+ * of a handle of 2 or 3 axes sum the same terms in the same order as PSP_MG_GALERKIN's but keep the rounding errors of the
+ * running sum and add them at the end (each entry is the exact sum rounded to within an ulp or two).  In 1-D the two
+ * patterns coincide and the handle has the bits of the axis one.  There is no line-smoothed form. */
+#define PSP_MG_BOX 8u /* bit 2 (4u) stays unassigned and is refused like every unknown bit */
+/* *box = 1 for a handle created with PSP_MG_BOX, 0 for every other handle */
+int psp_mg_stencil(const psp_mg_t *K, int *box);
+
 /* --------------------------------------------------------- operator protocol */
 
 /* Host callback operator: the C image of SpMatrix_Matvec / SpMatrix_Precon

@@ -30,6 +30,10 @@
 // thread per line, factorised at creation), and the last level, a single line, is solved exactly.  The schedule, the
 // restriction and the prolongation are the ones below; there is no tail launch and no dense inverse.
 //
+// stencil = 'box' (PSP_MG_BOX; psp_mg_galerkin.h) is the stored mode for symmetric operators with the full
+// pattern {-1, 0, 1}^ND, 9 points in 2-D and 27 in 3-D: a checking and extraction pass of its own, level 0 stored like every
+// lower level, the Galerkin chain summed without losing its rounding errors; the cycle kernels are the ones below.
+//
 // Blocks of k vectors (psp_mg_precon_block): block forms of the five cycle kernels, one thread per
 // point and up to KC columns, the row's coefficients loaded once per point (Op::load_row / ax_row); the same schedule, the
 // same launches whatever k is, column c with the bits of the single cycle on column c.
@@ -701,6 +705,8 @@ struct psp_mg {
   int line_axis = -1;
   std::vector<MgLine> lines;
   std::vector<const double *> line_lo;
+  // stencil='box' (section 9i): level 0 of a stored handle has the full pattern like every level below it
+  bool box = false;
 };
 
 namespace {
@@ -1111,6 +1117,14 @@ const char *g_why(int bits) {
   return "an unsymmetric pair, A[k, k+st] != A[k+st, k]";
 }
 
+// the same for a box handle (section 9i), whose pass knows the kinds offset, duplicate, diagonal and symmetry
+const char *g_why_box(int bits) {
+  if (bits & kGBadOffset) return "an entry at an offset outside the box: a column more than one point away along an axis of the grid";
+  if (bits & kGBadDup) return "an entry that is stored twice";
+  if (bits & kGBadDiag) return "a diagonal entry that is missing, or not finite and > 0";
+  return "an unsymmetric pair, A[r, c] != A[c, r]";
+}
+
 GOut g_out(const GLevel &G) {
   GOut o;
   o.diag = const_cast<double *>(G.diag);
@@ -1141,7 +1155,18 @@ int g_dispatch(const GLevelT<S> &G, F &&f) {
   return PSP_OK;
 }
 
-int launch_galerkin(const GLevel &S, long Nc, double omega, const GOut &o, int *flag) {
+// box: the chain of a box handle (section 9i), whose sums keep their rounding errors; in 1-D the patterns coincide and so do
+// the bits
+int launch_galerkin(const GLevel &S, long Nc, double omega, const GOut &o, int *flag, bool box) {
+  const dim3 grid((unsigned)((Nc + 255) / 256));
+  if (box && S.nd == 2 && S.noff == g_full_noff(2)) {
+    hipLaunchKernelGGL(mg_galerkin_box_kernel<2>, grid, dim3(256), 0, stream(), S, Nc, omega, o, flag);
+    return PSP_OK;
+  }
+  if (box && S.nd == 3 && S.noff == g_full_noff(3)) {
+    hipLaunchKernelGGL(mg_galerkin_box_kernel<3>, grid, dim3(256), 0, stream(), S, Nc, omega, o, flag);
+    return PSP_OK;
+  }
   return g_dispatch(S, [&](auto sh) {
     hipLaunchKernelGGL((mg_galerkin_kernel<sh.nd, sh.noff>), dim3((unsigned)((Nc + 255) / 256)), dim3(256), 0, stream(), S,
                        Nc, omega, o, flag);
@@ -1262,7 +1287,7 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
     G.a = L.a;
     if (single) L.af = mg_round_level(L.a);  // the prolongation's geometry
     G.nd = nd;
-    G.noff = l == 0 ? nd : g_full_noff(nd);
+    G.noff = l == 0 && !K->box ? nd : g_full_noff(nd);
     for (int k = 0; k < G.noff; ++k)
       for (int a = 0; a < 3; ++a) G.od[k][a] = g_d(nd, G.noff, k, a);
     if (!single || l == 0) {
@@ -1272,19 +1297,26 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
   }
   // level 0: the checking pass writes it
   PSP_HIP(hipMemsetAsync(flags, 0, 3 * sizeof(int), stream()));
-  PSP_HIP(hipMemsetAsync(K->coef[0], 0, sizeof(double) * (size_t)(2 + nd) * (size_t)K->lev[0].N, stream()));
-  hipLaunchKernelGGL(mg_extract_csr_kernel, dim3((A->nrows + 255) / 256), dim3(256), 0, stream(), A->nrows, n[0], n[1], n[2],
-                     omega, (const int *)A->ind, (const int *)A->col, (const double *)A->val, g_out(K->glev[0]), flags);
+  PSP_HIP(hipMemsetAsync(K->coef[0], 0, sizeof(double) * (size_t)(2 + K->glev[0].noff) * (size_t)K->lev[0].N, stream()));
+  if (K->box)
+    hipLaunchKernelGGL(mg_extract_box_kernel, dim3((A->nrows + 255) / 256), dim3(256), 0, stream(), A->nrows, n[0], n[1], n[2],
+                       omega, (const int *)A->ind, (const int *)A->col, (const double *)A->val, g_out(K->glev[0]), flags);
+  else
+    hipLaunchKernelGGL(mg_extract_csr_kernel, dim3((A->nrows + 255) / 256), dim3(256), 0, stream(), A->nrows, n[0], n[1], n[2],
+                       omega, (const int *)A->ind, (const int *)A->col, (const double *)A->val, g_out(K->glev[0]), flags);
   PSP_LAUNCH_CHECK();
   int bad = 0;
   PSP_TRY(read_flag(flags, &bad));
+  if (bad && K->box)
+    return fail(PSP_EINVAL, "multigrid(galerkin=True, stencil='box'): the matrix is not a symmetric 9- / 27-point stencil on this grid: it has %s",
+                g_why_box(bad));
   if (bad)
     return fail(PSP_EINVAL, "multigrid(galerkin=True): the matrix is not a symmetric 3- / 5- / 7-point stencil on this grid: it has %s",
                 g_why(bad));
   // A_{l+1} = R_l A_l P_l, level by level
   for (int l = 0; l + 1 < nl; ++l) {
     if (single) PSP_TRY(g_alloc_level(K, l + 1, &K->coef[l + 1], &K->glev[l + 1]));
-    PSP_TRY(launch_galerkin(K->glev[l], K->lev[l + 1].N, omega, g_out(K->glev[l + 1]), flags + 1));
+    PSP_TRY(launch_galerkin(K->glev[l], K->lev[l + 1].N, omega, g_out(K->glev[l + 1]), flags + 1, K->box));
     PSP_LAUNCH_CHECK();
     if (single) {
       PSP_TRY(g_round_level(K, l, flags + 2));
@@ -1311,11 +1343,13 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
   return mg_upload_tail(K, inv, [&](int l) { return K->glev[l]; });
 }
 
-// line: -1, or the axis of the line smoother (section 9h), which has no single-precision form
+// line: -1, or the axis of the line smoother (section 9h), which has no single-precision form; box: level 0 in the full
+// layout (section 9i), which has no line-smoothed form
 int mg_create_galerkin_line(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, int line,
-                            psp_mg **out) {
+                            psp_mg **out, bool box = false) {
   int n[3];
   PSP_TRY(mg_check_args(A, ndim, grid, omega, steps, out, n));
+  if (line != -1 && box) return fail(PSP_EINVAL, "multigrid(line=%d): stencil='box' with a line smoother is not supported", line);
   if (line != -1) {
     if (ndim < 2) return fail(PSP_EINVAL, "multigrid(line=%d): a grid of one axis has no axis left to coarsen", line);
     if (line < 0 || line >= ndim) return fail(PSP_EINVAL, "multigrid(line=%d): the grid has the axes 0 .. %d", line, ndim - 1);
@@ -1329,14 +1363,23 @@ int mg_create_galerkin_line(psp_csr *A, int ndim, const int *grid, double omega,
   PSP_HIP(hipMalloc((void **)&flags, 3 * sizeof(int)));
   const int rc = mg_make(A, ndim, omega, steps, true, single, out, [&](psp_mg *K) {
     K->line_axis = line;
+    K->box = box;
     return g_build(K, A, n, flags);
   });
   (void)hipFree(flags);
   return rc;
 }
 
-int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, psp_mg **out) {
-  return mg_create_galerkin_line(A, ndim, grid, omega, steps, single, -1, out);
+int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, bool box, psp_mg **out) {
+  return mg_create_galerkin_line(A, ndim, grid, omega, steps, single, -1, out, box);
+}
+
+// the flags of psp_mg_create_*_ex: known bits only, and PSP_MG_BOX selects the pattern of a stored level 0
+int mg_check_flags(const char *fn, unsigned flags) {
+  if (flags & ~(unsigned)(PSP_MG_GALERKIN | PSP_MG_SINGLE | PSP_MG_BOX)) return fail(PSP_EINVAL, "%s: unknown flags 0x%x", fn, flags);
+  if ((flags & PSP_MG_BOX) && !(flags & PSP_MG_GALERKIN))
+    return fail(PSP_EINVAL, "%s: PSP_MG_BOX (stencil='box') needs PSP_MG_GALERKIN (galerkin=True): the matrix-free mode stores no level 0", fn);
+  return PSP_OK;
 }
 
 // A vector of the cycle: the handle's scalar type, or (wide) the caller's doubles, which only the finest level of a
@@ -1356,8 +1399,9 @@ struct MVec {
 
 // f(b's element type *, the written vector's element type *): with S = double both are double -- the kernels of a double
 // handle exist in that one form; with S = float a wide b is the caller's (float vectors otherwise), and only next to a
-// wide b can the written vector be the caller's y.  FINEST = false: the level's shape (a stored level with the full
-// pattern) is never the finest level's, so the forms with wide vectors are not instantiated for it.
+// wide b can the written vector be the caller's y.  FINEST = false: the level is not the finest one (a stored level with
+// the full pattern below level 0), so the forms with wide vectors are not chosen for it; level 0 of a box handle
+// (section 9i) has that pattern too and takes them.
 template <class S, bool FINEST = true, class F>
 void mg_with_io(const MVec &b, const MVec &out, F &&f) {
   if constexpr (std::is_same_v<S, double>) {
@@ -1471,7 +1515,7 @@ struct CycleOps {
     const long N = K->lev[l].N;
     return with_op<true>(l, [&](auto tag, const auto &A) {
       using Op = typename decltype(tag)::type;
-      mg_with_io<S, Op::kFinest>(b, xout, [&](auto *bp, auto *op) {
+      auto launch = [&](auto *bp, auto *op) {
         using TB = Elem<decltype(bp)>;
         using TO = Elem<decltype(op)>;
         if (!k)
@@ -1482,7 +1526,12 @@ struct CycleOps {
             hipLaunchKernelGGL((mg_smooth_block_kernel<Op, FROMB, c.kc, TB, TO>), grid(N), dim3(256), 0, stream(), A, N, k,
                                xin.as<const S>(), xin.ld, bp, b.ld, op, xout.ld, frozen);
           });
-      });
+      };
+      // level 0 of a box handle (section 9i) has the full pattern and is the finest level all the same
+      if (l == 0)
+        mg_with_io<S, true>(b, xout, launch);
+      else
+        mg_with_io<S, Op::kFinest>(b, xout, launch);
     });
   }
   // line = a (section 9h): one line sweep of level l, xout = xin + omega T^-1 (b - A xin); FROM0: from xin = 0.  The line
@@ -1537,7 +1586,7 @@ struct CycleOps {
       long g[3];
       mg_restrict_grid(level_geo(A), tile, g);
       const unsigned tiles = (unsigned)(g[0] * g[1] * g[2]);
-      mg_with_b<S, Op::kFinest>(b, [&](auto *bp) {
+      auto launch = [&](auto *bp) {
         using TB = Elem<decltype(bp)>;
         if (!k)
           hipLaunchKernelGGL((mg_restrict_kernel<Op, TB>), dim3(tiles), dim3(kResThreads), 0, stream(), A, tile[0], tile[1],
@@ -1546,7 +1595,11 @@ struct CycleOps {
           hipLaunchKernelGGL((mg_restrict_block_kernel<Op, TB>), dim3(tiles, (unsigned)k), dim3(kResThreads), 0, stream(), A,
                              tile[0], tile[1], tile[2], (int)g[0], (int)g[1], k, x.as<const S>(), x.ld, bp, b.ld, bc.as<S>(),
                              bc.ld, frozen);
-      });
+      };
+      if (l == 0)  // as in smooth()
+        mg_with_b<S, true>(b, launch);
+      else
+        mg_with_b<S, Op::kFinest>(b, launch);
     });
   }
   // the tail's ends are both the caller's (the whole grid is the tail) or both the handle's; a block's columns are a
@@ -1749,18 +1802,18 @@ extern "C" {
 
 int psp_mg_create_csr_ex(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, unsigned flags, psp_mg_t **out) {
   PSP_API_GUARD_H(A);
-  if (flags & ~(unsigned)(PSP_MG_GALERKIN | PSP_MG_SINGLE)) return fail(PSP_EINVAL, "psp_mg_create_csr_ex: unknown flags 0x%x", flags);
-  const bool single = (flags & PSP_MG_SINGLE) != 0;
-  if (flags & PSP_MG_GALERKIN) return mg_create_galerkin(A, ndim, grid, omega, steps, single, out);
+  PSP_TRY(mg_check_flags("psp_mg_create_csr_ex", flags));
+  const bool single = (flags & PSP_MG_SINGLE) != 0, box = (flags & PSP_MG_BOX) != 0;
+  if (flags & PSP_MG_GALERKIN) return mg_create_galerkin(A, ndim, grid, omega, steps, single, box, out);
   return mg_create(A, ndim, grid, omega, steps, single, out);
 }
 
 int psp_mg_create_sss_ex(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, unsigned flags, psp_mg_t **out) {
-  if (flags & ~(unsigned)(PSP_MG_GALERKIN | PSP_MG_SINGLE)) return fail(PSP_EINVAL, "psp_mg_create_sss_ex: unknown flags 0x%x", flags);
-  const bool single = (flags & PSP_MG_SINGLE) != 0;
+  PSP_TRY(mg_check_flags("psp_mg_create_sss_ex", flags));
+  const bool single = (flags & PSP_MG_SINGLE) != 0, box = (flags & PSP_MG_BOX) != 0;
   if (flags & PSP_MG_GALERKIN)
     return mg_create_sss(A, "psp_mg_create_sss_galerkin",
-                         [&](psp_csr *F) { return mg_create_galerkin(F, ndim, grid, omega, steps, single, out); });
+                         [&](psp_csr *F) { return mg_create_galerkin(F, ndim, grid, omega, steps, single, box, out); });
   return mg_create_sss(A, "psp_mg_create_sss", [&](psp_csr *F) { return mg_create(F, ndim, grid, omega, steps, single, out); });
 }
 
@@ -1781,6 +1834,12 @@ int psp_mg_create_sss_line(psp_sss_t *A, int ndim, const int *grid, double omega
 int psp_mg_line_axis(const psp_mg_t *K, int *axis) {
   if (!K || !axis) return fail(PSP_EINVAL, "psp_mg_line_axis: NULL argument");
   *axis = K->line_axis;
+  return PSP_OK;
+}
+
+int psp_mg_stencil(const psp_mg_t *K, int *box) {
+  if (!K || !box) return fail(PSP_EINVAL, "psp_mg_stencil: NULL argument");
+  *box = K->box ? 1 : 0;
   return PSP_OK;
 }
 

@@ -53,7 +53,7 @@ def _matmat(fn, h, shape, X, Y):
         Y[...] = yb
 
 
-PSP_MG_GALERKIN, PSP_MG_SINGLE = 1, 2  # psp_mg_create_*_ex flags (pysparse_hip.h)
+PSP_MG_GALERKIN, PSP_MG_SINGLE, PSP_MG_BOX = 1, 2, 8  # psp_mg_create_*_ex flags (pysparse_hip.h)
 
 
 class DeviceBuffer:
@@ -568,10 +568,20 @@ class DeviceMultigrid:
     def __init__(self, A, grid, omega=0.8, steps=2, galerkin=False):
         self._create(A, grid, omega, steps, galerkin, None)
 
-    def _create(self, A, grid, omega, steps, galerkin, line):
-        """every check, then the handle; line: None, or the axis of DeviceMultigridLine"""
+    def _create(self, A, grid, omega, steps, galerkin, line, stencil="axis"):
+        """every check, then the handle; line: None, or the axis of DeviceMultigridLine; stencil: 'axis', or
+        DeviceMultigridBox's 'box'"""
         if not isinstance(galerkin, bool):
             raise TypeError("galerkin must be a bool")
+        if not isinstance(stencil, str):
+            raise TypeError("stencil must be a str, 'axis' or 'box'")
+        if stencil not in ("axis", "box"):
+            raise ValueError("stencil must be 'axis' or 'box'")
+        box = stencil == "box"
+        if box and not galerkin:
+            raise ValueError("stencil='box' needs galerkin=True: the matrix-free mode stores no level operators")
+        if box and line is not None:
+            raise ValueError("stencil='box' with line: the line smoother on 9- / 27-point operators is not supported")
         if line is not None and (isinstance(line, bool) or not isinstance(line, int)):
             raise TypeError("line must be None or an int, the axis of the line smoother")
         if not isinstance(A, (DeviceCSR, DeviceSSS)):
@@ -617,7 +627,7 @@ class DeviceMultigrid:
             _check_einval(create(A._h, len(dims), g, omega, steps, line, C.byref(h)))
         else:
             create = lib().psp_mg_create_csr_ex if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss_ex
-            flags = (PSP_MG_GALERKIN if galerkin else 0) | self._FLAGS
+            flags = (PSP_MG_GALERKIN if galerkin else 0) | (PSP_MG_BOX if box else 0) | self._FLAGS
             _check_einval(create(A._h, len(dims), g, omega, steps, flags, C.byref(h)))
         self._A = A
         self._h = h
@@ -625,12 +635,19 @@ class DeviceMultigrid:
         self.ndim = len(dims)
         self.levels = tuple(lv[:self.ndim] for lv in self.info()["dims"])
 
+    @property
+    def stencil(self):
+        """'axis' (3- / 5- / 7-point operators) or 'box' (9- / 27-point ones, DeviceMultigridBox); read-only"""
+        return self.info()["stencil"]
+
     def info(self):
         """levels, first level of the single-workgroup tail launch, kernel launches per application, level dimensions
         (three per level, 1 on absent axes), whether the handle stores Galerkin level operators, and the precision
         of the cycle ('double' or 'single'), and the axis of the line smoother (None without one; with one there is no
-        tail launch and tail_first_level == levels)"""
-        nl, tf, la, gk, bits, ax = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        tail launch and tail_first_level == levels), and the pattern of the accepted operators ('axis', or 'box' for
+        DeviceMultigridBox)"""
+        nl, tf, la, gk, bits, ax, bx = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(lib().psp_mg_stencil(self._h, C.byref(bx)))
         check(lib().psp_mg_is_galerkin(self._h, C.byref(gk)))
         check(lib().psp_mg_precision(self._h, C.byref(bits)))
         check(lib().psp_mg_line_axis(self._h, C.byref(ax)))
@@ -639,7 +656,8 @@ class DeviceMultigrid:
         check(lib().psp_mg_info(self._h, None, None, None, d))
         return {"levels": nl.value, "tail_first_level": tf.value, "launches_per_apply": la.value,
                 "dims": tuple(tuple(d[3 * l:3 * l + 3]) for l in range(nl.value)), "galerkin": bool(gk.value),
-                "precision": "single" if bits.value == 32 else "double", "line": ax.value if ax.value >= 0 else None}
+                "precision": "single" if bits.value == 32 else "double", "line": ax.value if ax.value >= 0 else None,
+                "stencil": "box" if bx.value else "axis"}
 
     def bytes(self):
         """{"operator", "vector"}: device bytes the handle holds at rest (psp_mg_bytes) -- the level operators with the
@@ -715,6 +733,21 @@ class DeviceMultigridLine(DeviceMultigrid):
 
     def __init__(self, A, grid, omega=0.8, steps=2, galerkin=True, line=None):
         self._create(A, grid, omega, steps, galerkin, line)
+
+
+class DeviceMultigridBox(DeviceMultigrid):
+    """precon.multigrid(..., galerkin=True, stencil='box'): the Galerkin cycle for symmetric operators with the full
+    pattern {-1, 0, 1}^ndim -- 9 points in 2-D, 27 in 3-D (PSP_MG_BOX).  Level 0 is stored like every lower
+    level.  stencil='axis' is DeviceMultigrid; precision='single' is the float32 cycle of DeviceMultigrid32.  Every
+    method is the parent's; info()["stencil"] and .stencil say which pattern the handle takes."""
+
+    def __init__(self, A, grid, omega=0.8, steps=2, galerkin=True, stencil="box", precision="double"):
+        if not isinstance(precision, str):
+            raise TypeError("precision must be a str, 'double' or 'single'")
+        if precision not in ("double", "single"):
+            raise ValueError("precision must be 'double' or 'single'")
+        self._FLAGS = PSP_MG_SINGLE if precision == "single" else 0
+        self._create(A, grid, omega, steps, galerkin, None, stencil)
 
 
 def _solve(fn, A, b, x, tol, maxit, K, hist):

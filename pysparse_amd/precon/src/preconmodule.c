@@ -254,7 +254,8 @@ static PyGetSetDef SSOR_getset[] = {{"shape", (getter)SSOR_get_shape, NULL, "(n,
  * constant-coefficient grid operators and, with the keyword galerkin=True (a real bool), for any symmetric 3- / 5- /
  * 7-point operator on the grid (psp_mg.hip); the keyword precision='single' (a str) selects the cycle evaluated in float32
  * (DESIGN.md 9g); the keyword line=a (an int, with galerkin=True) the line smoother along axis a for graded and
- * stretched grids; no reference analogue */
+ * stretched grids; the keyword stencil='box' (a str, with galerkin=True) the 9- / 27-point operators
+ * (DESIGN.md 9i); no reference analogue */
 #define MG_MAX_LEVELS 40
 
 typedef struct {
@@ -269,8 +270,9 @@ typedef struct {
 static PyTypeObject MGType;
 
 static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
-  static char *kwlist[] = {"A", "grid", "omega", "steps", "galerkin", "precision", "line", NULL};
+  static char *kwlist[] = {"A", "grid", "omega", "steps", "galerkin", "precision", "line", "stencil", NULL};
   PyObject *matrix, *grid, *seq, *cap, *galerkin_obj = Py_False, *precision_obj = NULL, *line_obj = Py_None;
+  PyObject *stencil_obj = NULL;
   int galerkin;
   long line = -1;
   unsigned flags = 0;
@@ -279,8 +281,8 @@ static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
   int is_csr, is_sss, is_ll;
   long long prod = 1;
   MGObject *op;
-  if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|di$OOO", kwlist, &matrix, &grid, &omega, &steps, &galerkin_obj,
-                                   &precision_obj, &line_obj))
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "OO|di$OOOO", kwlist, &matrix, &grid, &omega, &steps, &galerkin_obj,
+                                   &precision_obj, &line_obj, &stencil_obj))
     return NULL;
   if (!PyBool_Check(galerkin_obj)) {
     PyErr_SetString(PyExc_TypeError, "multigrid() argument 'galerkin' must be a bool");
@@ -297,6 +299,27 @@ static PyObject *multigrid_prec(PyObject *self, PyObject *args, PyObject *kw) {
       flags |= PSP_MG_SINGLE;
     else if (PyUnicode_CompareWithASCIIString(precision_obj, "double") != 0) {
       PyErr_SetString(PyExc_ValueError, "multigrid() argument 'precision' must be 'double' or 'single'");
+      return NULL;
+    }
+  }
+  if (stencil_obj != NULL) { /* exactly the str 'axis' or 'box'  */
+    if (!PyUnicode_Check(stencil_obj)) {
+      PyErr_SetString(PyExc_TypeError, "multigrid() argument 'stencil' must be a str, 'axis' or 'box'");
+      return NULL;
+    }
+    if (PyUnicode_CompareWithASCIIString(stencil_obj, "box") == 0) {
+      if (!galerkin) {
+        PyErr_SetString(PyExc_ValueError, "multigrid() argument 'stencil': 'box' needs galerkin=True: the matrix-free mode "
+                                          "stores no level operators");
+        return NULL;
+      }
+      if (line_obj != Py_None) {
+        PyErr_SetString(PyExc_ValueError, "multigrid() argument 'stencil': 'box' with line is not supported");
+        return NULL;
+      }
+      flags |= PSP_MG_BOX;
+    } else if (PyUnicode_CompareWithASCIIString(stencil_obj, "axis") != 0) {
+      PyErr_SetString(PyExc_ValueError, "multigrid() argument 'stencil' must be 'axis' or 'box'");
       return NULL;
     }
   }
@@ -536,6 +559,13 @@ static PyObject *MG_get_precision(MGObject *self, void *c) {
   return PyUnicode_FromString(bits == 32 ? "single" : "double");
 }
 
+/* 'axis', or 'box' for a handle that takes 9- / 27-point operators */
+static PyObject *MG_get_stencil(MGObject *self, void *c) {
+  int box = 0, rc = psp_mg_stencil(self->dev, &box);
+  if (rc != PSP_OK) return raise_psp(rc);
+  return PyUnicode_FromString(box ? "box" : "axis");
+}
+
 /* the axis of the line smoother, None without one */
 static PyObject *MG_get_line(MGObject *self, void *c) {
   int axis = -1, rc = psp_mg_line_axis(self->dev, &axis);
@@ -557,6 +587,7 @@ static PyGetSetDef MG_getset[] = {{"shape", (getter)MG_get_shape, NULL, "(n, n)"
                                   {"galerkin", (getter)MG_get_galerkin, NULL, "stored Galerkin level operators", NULL},
                                   {"precision", (getter)MG_get_precision, NULL, "'double' or 'single'", NULL},
                                   {"line", (getter)MG_get_line, NULL, "the axis of the line smoother, or None", NULL},
+                                  {"stencil", (getter)MG_get_stencil, NULL, "'axis' or 'box'", NULL},
                                   {"_psp_op", (getter)MG_get_psp_op, NULL, "device operator", NULL},
                                   {NULL, NULL, NULL, NULL, NULL}};
 
@@ -570,7 +601,8 @@ static PyMethodDef precon_methods[] = {
      "omega  relaxation parameter (default value: 1.0)\n"
      "steps  number of SSOR steps"},
     {"multigrid", (PyCFunction)multigrid_prec, METH_VARARGS | METH_KEYWORDS,
-     "multigrid(A, grid, omega=0.8, steps=2, galerkin=False, precision='double', line=None) -- return geometric multigrid\n"
+     "multigrid(A, grid, omega=0.8, steps=2, galerkin=False, precision='double', line=None, stencil='axis') -- return\n"
+     "geometric multigrid\n"
      "preconditioner object\n\n"
      "One V-cycle with damped-Jacobi smoothing for A = sum_a c_a T_a + s I on a grid (no reference analogue).\n\n"
      "A      'csr_mat', 'sss_mat' or 'll_mat': the constant-coefficient [-1 2 -1] stencil on the grid\n"
@@ -583,7 +615,9 @@ static PyMethodDef precon_methods[] = {
      "       double ones; x and y stay double arrays, the outer solver is unchanged (default value: 'double')\n"
      "line   keyword, None or an int: with galerkin=True, the grid axis along which the cells are graded or stretched;\n"
      "       that axis is never coarsened and the smoother solves the level operator's tridiagonal part along each of\n"
-     "       its grid lines exactly instead of point Jacobi; double precision only (default value: None)"},
+     "       its grid lines exactly instead of point Jacobi; double precision only (default value: None)\n"
+     "stencil  keyword, a str: 'box' (with galerkin=True, without line) takes any symmetric operator with the pattern\n"
+     "       {-1, 0, 1}^ndim, 9 points in 2-D and 27 in 3-D (default value: 'axis')"},
     {NULL, NULL, 0, NULL}};
 
 static struct PyModuleDef precon_module = {PyModuleDef_HEAD_INIT, "precon",
