@@ -732,6 +732,65 @@ int psp_k_jacobi(int n, const double *x_dev, const double *dinv_dev, double *y_d
 /* gather send_dev[i] = v[idx[i]] (halo packing) */
 int psp_k_gather(int count, const int *idx_dev, const double *v_dev, double *send_dev);
 
+/* Test hook (tests/test_gpu_vec_passes.py): ONE launch of a fused vector pass of the cgs / bicgstab / qmrs / gmres / minres
+ * loops or of the Jacobi preconditioner, which otherwise run only inside whole solves.  vec_dev[0 .. nvec) are the pass's
+ * device vectors in the order below, scal_host[0 .. nscal) its by-value scalars; dinv_dev is the Jacobi array of the
+ * passes marked [K] (NULL: no preconditioner; a vector registered with psp_k_hint_constant: the constant form) and of
+ * JACOBI_SWEEP, NULL for every other pass.  Vectors in (parentheses) are dereferenced only with dinv_dev and may be NULL
+ * without it.  sums_dev receives the finished reductions {in braces}; it is ignored for passes that reduce nothing.
+ *   LIN2            x y z                 a b                    z = a x + b y (z may be x or y)
+ *   SCAL            x                     a                      x = a x
+ *   BICG_P     [K]  r v p (phat)          beta omega             p = r + beta (p - omega v), FIRST: p = r; phat = K p
+ *   BICG_S     [K]  r v s (shat)          alpha                  s = r - alpha v; shat = K s
+ *   BICG_XR         x phat shat s t r rhat  alpha omega          x += alpha phat + omega shat; r = s - omega t  {r.r, rhat.r}
+ *   CGS_Q      [K]  u v x q tmp2          alpha                  q = u - alpha v; tmp2 = K (u + q); x += alpha tmp2
+ *   CGS_R           r t r0                alpha                  r -= alpha t  {r.r, r.r0}
+ *   CGS_P      [K]  r q p u (kp)          beta                   u = r + beta q; p = u + beta (q + beta p); kp = K p
+ *   QMRS_KV    [K]  v1 (wrk1)             -                      wrk1 = K v1  {wrk1.v1; without K: v1.v1}
+ *   QMRS_PG         v1 wrk1 p g           cc                     p = v1 - cc p; g = wrk1 - cc g
+ *   QMRS_V          t v1                  beta                   v1 = t - beta v1  {v1.v1}
+ *   QMRS_DX    [K]  p d x v1 (wrk1)       eta cc rho1inv         d = eta p + cc d; x += d; v1 *= rho1inv; wrk1 = K v1  {wrk1.v1}
+ *   AXPY_DOT        x y z                 a                      y += a x  {y.z; z NULL: y.y}.  COEF_DEV: a = -scal[0], read
+ *                                                                from the device
+ *   AXPY_DOT_CHAIN  prev h_out x y z      np_prev                h = sum of prev[0 .. np_prev), np_prev in 1 .. 4096; *h_out = h;
+ *                                                                y -= h x  {y.z; z NULL: y.y}.  PREV_WS: prev is NULL and
+ *                                                                stands for the partial sums the calling thread's last
+ *                                                                reducing call of this function left (np_prev must be their count)
+ *   JACOBI_SWEEP    x temp y              -                      y = (x - y) dinv + temp
+ *   DINV            diag dinv             omega                  dinv = omega / diag  {number of entries with 1 + d == 1}
+ *   SCALE_DIV       y v                   beta                   v = y / beta
+ *   LANCZOS    [K]  av v_hat v_hat_old (y)  c1 c2                v_hat_old = av - c1 v_hat - c2 v_hat_old; y = K v_hat_old
+ *                                                                {v_hat_old.y; without K: v_hat_old.v_hat_old}
+ *   LANCZOS_PLAIN   av v_hat v_hat_old    c1 c2                  the same without K and without the sum
+ *   MINRES_WX       v w w_old x           r1 r2 r3 c_eta vdiv    w_old = (v - r3 w_old - r2 w) / r1; x += c_eta w_old;
+ *                                                                SCALED: v / vdiv in place of v
+ *   MINRES_WX_VNEXT v ynext w w_old x     -                      the same with the scalars of a NULL device state
+ *                                                                (r1 = r2 = r3 = c_eta = 0) and v = ynext / 1
+ * (the two MINRES passes run without a device state; their device-state forms are psp_kd_minres_*.)
+ * PSP_VEC_DEVSCAL (the nine passes that take their scalars from a device state: BICG_*, CGS_*, QMRS_PG / _V / _DX): the
+ * scalars travel in registers i0, i1, i2 (distinct, 0 .. 31) of a KryDev whose other registers hold NaN and whose iteration
+ * counter is `iter` (BICG_P takes "first" from iter == 1, not from PSP_VEC_FIRST); the by-value arguments of the launch are
+ * NaN.  PSP_VEC_STATUS_SET (with DEVSCAL): the state says the loop has ended -- the pass must change nothing.
+ * PSP_EINVAL before anything is launched: an unknown pass, other counts than the table's, n < 1, a flag the pass does not
+ * take, a NULL vector the selected form dereferences, dinv_dev where the pass takes none.
+ * psp_debug_vec_form: the form the calling thread's last vector-kernel launch took -- *V = 2 (one 16-byte access per lane)
+ * or 1 (two 8-byte ones), *pre = 0 (no preconditioner), 1 (dinv array) or 2 (constant); both 0 before the first launch. */
+enum {
+  PSP_VEC_LIN2 = 0, PSP_VEC_SCAL, PSP_VEC_BICG_P, PSP_VEC_BICG_S, PSP_VEC_BICG_XR, PSP_VEC_CGS_Q, PSP_VEC_CGS_R,
+  PSP_VEC_CGS_P, PSP_VEC_QMRS_KV, PSP_VEC_QMRS_PG, PSP_VEC_QMRS_V, PSP_VEC_QMRS_DX, PSP_VEC_AXPY_DOT,
+  PSP_VEC_AXPY_DOT_CHAIN, PSP_VEC_JACOBI_SWEEP, PSP_VEC_DINV, PSP_VEC_SCALE_DIV, PSP_VEC_LANCZOS, PSP_VEC_LANCZOS_PLAIN,
+  PSP_VEC_MINRES_WX, PSP_VEC_MINRES_WX_VNEXT, PSP_VEC_NPASS
+};
+#define PSP_VEC_FIRST 1u
+#define PSP_VEC_SCALED 2u
+#define PSP_VEC_DEVSCAL 4u
+#define PSP_VEC_STATUS_SET 8u
+#define PSP_VEC_COEF_DEV 16u
+#define PSP_VEC_PREV_WS 32u
+int psp_debug_vec_pass(int pass, int n, double *const *vec_dev, int nvec, const double *dinv_dev, const double *scal_host,
+                       int nscal, unsigned flags, int i0, int i1, int i2, int iter, double *sums_dev);
+int psp_debug_vec_form(int *V, int *pre);
+
 /* ------------------------------------------ device-resident solver state for the multi-GPU driver
  * The same loops with NO host round trip per reduction: alpha / beta / the exit tests of pcg.c:100-162
  * (resp. the Lanczos / Givens recurrences of minres.c:129-192) live in a small device-side state; the

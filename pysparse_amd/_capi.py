@@ -47,7 +47,13 @@ psp_kd_minres_scale psp_kd_minres_matvec psp_kd_minres_lanczos psp_kd_minres_sca
 psp_bv_tdot psp_bv_gemv psp_bv_rotate psp_jdsym psp_op_apply_host psp_debug_ritz psp_debug_lu_factor psp_debug_lu_solve
 psp_csr_matmat psp_csr_matmat_dev psp_sss_matmat psp_sss_matmat_dev psp_op_apply_block_dev psp_pcg_batch psp_pcg_batch_dev
 psp_bv_gram psp_bv_resid psp_lobpcg psp_debug_gen_ritz
+psp_debug_vec_pass psp_debug_vec_form
 """.split()
+
+# psp_debug_vec_pass: the passes in the order of the header's enum, and the flags
+VEC_PASSES = ("lin2 scal bicg_p bicg_s bicg_xr cgs_q cgs_r cgs_p qmrs_kv qmrs_pg qmrs_v qmrs_dx axpy_dot axpy_dot_chain "
+              "jacobi_sweep dinv scale_div lanczos lanczos_plain minres_wx minres_wx_vnext").split()
+VEC_FIRST, VEC_SCALED, VEC_DEVSCAL, VEC_STATUS_SET, VEC_COEF_DEV, VEC_PREV_WS = 1, 2, 4, 8, 16, 32
 
 
 class PcgStatus(C.Structure):
@@ -217,6 +223,7 @@ def _declare(L):
         "psp_bv_resid": [i, i, vp, i64, vp, i64, vp, vp, vp, i64, vp],
         "psp_lobpcg": [vp, vp, vp, i, i, d, i, vp, i, C.c_long, vp, vp, C.c_long, vp, pi, pi],
         "psp_debug_gen_ritz": [i, vp, vp, i, vp, vp],
+        "psp_debug_vec_pass": [i, i, pvp, i, vp, pd, i, C.c_uint, i, i, i, i, vp], "psp_debug_vec_form": [pi, pi],
     }
     for name, argtypes in sig.items():
         f = getattr(L, name)

@@ -937,6 +937,9 @@ inline bool aligned16(Ptrs ptrs) {  // (a null pointer -- an operand the chosen 
 template <int N>
 using Int = std::integral_constant<int, N>;
 
+// the form the calling thread's last launch_vec / launch_vec_pre chose (psp_debug_vec_form; nothing else reads it)
+thread_local int t_last_v = 0, t_last_pre = 0;
+
 // f(std::true_type / std::false_type): a run-time flag as a template argument of the kernel
 template <typename F>
 inline void with_flag(bool flag, F &&f) {
@@ -949,7 +952,10 @@ int launch_vec(long n, Ptrs always, int *nparts, F &&launch) {
   Workspace *w;
   PSP_TRY(workspace(&w));
   const int grid = vec_grid(*w, n);
-  if (n % 2 == 0 && aligned16(always)) launch(grid, Int<2>{}); else launch(grid, Int<1>{});
+  const bool v2 = n % 2 == 0 && aligned16(always);
+  t_last_v = v2 ? 2 : 1;
+  t_last_pre = 0;
+  if (v2) launch(grid, Int<2>{}); else launch(grid, Int<1>{});
   PSP_LAUNCH_CHECK();
   if (nparts) *nparts = grid;
   return PSP_OK;
@@ -966,6 +972,8 @@ int launch_vec_pre(long n, const double *dinv, Ptrs always, Ptrs with_pre, int *
   double dc = 0.0;
   const int pre = !dinv ? 0 : dinv_constant(dinv, n, &dc) ? 2 : 1;
   const bool v2 = n % 2 == 0 && aligned16(always) && (pre == 0 || aligned16(with_pre)) && (pre != 1 || aligned16({dinv}));
+  t_last_v = v2 ? 2 : 1;
+  t_last_pre = pre;
   auto with_pre_form = [&](auto V) {
     if (pre == 2) launch(grid, dc, V, Int<2>{});
     else if (pre == 1) launch(grid, dc, V, Int<1>{});
@@ -1340,6 +1348,187 @@ int psp_k_gather(int count, const int *idx_dev, const double *v_dev, double *sen
   hipLaunchKernelGGL(gather_kernel, dim3(grid), dim3(256), 0, stream(), count, idx_dev, v_dev,
                      send_dev);
   PSP_LAUNCH_CHECK();
+  return PSP_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ C ABI: one vector pass at a time (tests)
+
+namespace {
+
+// What psp_debug_vec_pass checks before it launches: the counts of a pass, which of its vectors only the preconditioned
+// forms dereference (bit i: vec_dev[i]), which may be NULL in every form, and what it takes besides.
+struct VecPassInfo {
+  int nvec, nscal, nsums;
+  unsigned pre_only, optional;
+  bool has_pre;   // takes dinv_dev or NULL (launch_vec_pre)
+  bool kry;       // takes a KryArg: PSP_VEC_DEVSCAL is allowed
+  int nreg;       // ... and reads this many registers
+};
+const VecPassInfo kVecPass[PSP_VEC_NPASS] = {
+    /* LIN2            */ {3, 2, 0, 0, 0, false, false, 0},
+    /* SCAL            */ {1, 1, 0, 0, 0, false, false, 0},
+    /* BICG_P          */ {4, 2, 0, 1u << 3, 0, true, true, 2},
+    /* BICG_S          */ {4, 1, 0, 1u << 3, 0, true, true, 1},
+    /* BICG_XR         */ {7, 2, 2, 0, 0, false, true, 2},
+    /* CGS_Q           */ {5, 1, 0, 0, 0, true, true, 1},
+    /* CGS_R           */ {3, 1, 2, 0, 0, false, true, 1},
+    /* CGS_P           */ {5, 1, 0, 1u << 4, 0, true, true, 1},
+    /* QMRS_KV         */ {2, 0, 1, 1u << 1, 0, true, false, 0},
+    /* QMRS_PG         */ {4, 1, 0, 0, 0, false, true, 1},
+    /* QMRS_V          */ {2, 1, 1, 0, 0, false, true, 1},
+    /* QMRS_DX         */ {5, 3, 1, 1u << 4, 0, true, true, 3},
+    /* AXPY_DOT        */ {3, 1, 1, 0, 1u << 2, false, false, 0},
+    /* AXPY_DOT_CHAIN  */ {5, 1, 1, 0, (1u << 0) | (1u << 4), false, false, 0},
+    /* JACOBI_SWEEP    */ {3, 0, 0, 0, 0, false, false, 0},
+    /* DINV            */ {2, 1, 1, 0, 0, false, false, 0},
+    /* SCALE_DIV       */ {2, 1, 0, 0, 0, false, false, 0},
+    /* LANCZOS         */ {4, 2, 1, 1u << 3, 0, true, false, 0},
+    /* LANCZOS_PLAIN   */ {3, 2, 0, 0, 0, false, false, 0},
+    /* MINRES_WX       */ {4, 5, 0, 0, 0, false, false, 0},
+    /* MINRES_WX_VNEXT */ {5, 0, 0, 0, 0, false, false, 0},
+};
+
+thread_local int t_dbg_nparts = 0;  // partial sums the thread's last reducing psp_debug_vec_pass left in the workspace
+
+}  // namespace
+
+extern "C" {
+
+int psp_debug_vec_pass(int pass, int n, double *const *vec_dev, int nvec, const double *dinv_dev, const double *scal_host,
+                       int nscal, unsigned flags, int i0, int i1, int i2, int iter, double *sums_dev) {
+  PSP_API_GUARD;
+  if (pass < 0 || pass >= PSP_VEC_NPASS) return fail(PSP_EINVAL, "psp_debug_vec_pass: unknown pass %d", pass);
+  const VecPassInfo &I = kVecPass[pass];
+  if (n < 1) return fail(PSP_EINVAL, "psp_debug_vec_pass: n = %d", n);
+  if (nvec != I.nvec || nscal != I.nscal)
+    return fail(PSP_EINVAL, "psp_debug_vec_pass: pass %d takes %d vectors and %d scalars, not %d and %d", pass, I.nvec,
+                I.nscal, nvec, nscal);
+  if (!vec_dev || (I.nscal > 0 && !scal_host)) return fail(PSP_EINVAL, "psp_debug_vec_pass: NULL argument list");
+  unsigned allowed = 0;
+  if (pass == PSP_VEC_BICG_P) allowed |= PSP_VEC_FIRST;
+  if (pass == PSP_VEC_MINRES_WX) allowed |= PSP_VEC_SCALED;
+  if (I.kry) allowed |= PSP_VEC_DEVSCAL | PSP_VEC_STATUS_SET;
+  if (pass == PSP_VEC_AXPY_DOT) allowed |= PSP_VEC_COEF_DEV;
+  if (pass == PSP_VEC_AXPY_DOT_CHAIN) allowed |= PSP_VEC_PREV_WS;
+  if (flags & ~allowed) return fail(PSP_EINVAL, "psp_debug_vec_pass: flags 0x%x do not apply to pass %d", flags, pass);
+  const bool devscal = (flags & PSP_VEC_DEVSCAL) != 0;
+  if ((flags & PSP_VEC_STATUS_SET) && !devscal)
+    return fail(PSP_EINVAL, "psp_debug_vec_pass: PSP_VEC_STATUS_SET needs PSP_VEC_DEVSCAL");
+  if (devscal) {
+    const int reg[3] = {i0, i1, i2};
+    for (int k = 0; k < I.nreg; ++k) {
+      if (reg[k] < 0 || reg[k] >= 32) return fail(PSP_EINVAL, "psp_debug_vec_pass: register %d out of range", reg[k]);
+      for (int j = 0; j < k; ++j)
+        if (reg[j] == reg[k]) return fail(PSP_EINVAL, "psp_debug_vec_pass: register %d named twice", reg[k]);
+    }
+  }
+  const bool needs_dinv = pass == PSP_VEC_JACOBI_SWEEP;
+  if (needs_dinv && !dinv_dev) return fail(PSP_EINVAL, "psp_debug_vec_pass: this pass needs dinv_dev");
+  if (!needs_dinv && !I.has_pre && dinv_dev) return fail(PSP_EINVAL, "psp_debug_vec_pass: pass %d takes no dinv_dev", pass);
+  const bool prev_ws = (flags & PSP_VEC_PREV_WS) != 0;
+  for (int k = 0; k < I.nvec; ++k) {
+    bool needed = !((I.optional >> k) & 1u) && (dinv_dev != nullptr || !((I.pre_only >> k) & 1u));
+    if (pass == PSP_VEC_AXPY_DOT_CHAIN && k == 0 && !prev_ws) needed = true;  // prev, unless the workspace holds it
+    if (needed && !vec_dev[k]) return fail(PSP_EINVAL, "psp_debug_vec_pass: vector %d of pass %d is NULL", k, pass);
+  }
+  if (prev_ws && vec_dev[0]) return fail(PSP_EINVAL, "psp_debug_vec_pass: PSP_VEC_PREV_WS takes prev = NULL");
+  if (I.nsums > 0 && !sums_dev) return fail(PSP_EINVAL, "psp_debug_vec_pass: sums_dev is NULL");
+  int np_prev = 0;
+  if (pass == PSP_VEC_AXPY_DOT_CHAIN) {
+    const double c = scal_host[0];
+    if (!(c >= 1.0 && c <= 4096.0) || c != (double)(int)c)
+      return fail(PSP_EINVAL, "psp_debug_vec_pass: np_prev = %g is not a count in 1 .. 4096", c);
+    np_prev = (int)c;
+    if (prev_ws && np_prev != t_dbg_nparts)
+      return fail(PSP_EINVAL, "psp_debug_vec_pass: the last reducing pass left %d partial sums, not %d", t_dbg_nparts,
+                  np_prev);
+  }
+  Workspace *w;
+  PSP_TRY(workspace(&w));
+  // by-value scalars; under PSP_VEC_DEVSCAL they travel in a KryDev and the by-value arguments are NaN
+  const double qnan = __builtin_nan("");
+  double sv[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < I.nscal; ++k) sv[k] = devscal ? qnan : scal_host[k];
+  KryArg ka;
+  char *host_blk = static_cast<char *>(w->state_host), *dev_blk = static_cast<char *>(w->state_dev);
+  static_assert(sizeof(KryDev) + sizeof(double) <= kStateBytes, "KryDev and one coefficient fit the state block");
+  if (devscal) {
+    KryDev *H = reinterpret_cast<KryDev *>(host_blk);
+    *H = KryDev{};
+    for (double &r : H->r) r = qnan;
+    const int reg[3] = {i0, i1, i2};
+    for (int k = 0; k < I.nreg; ++k) H->r[reg[k]] = scal_host[k];
+    H->status = (flags & PSP_VEC_STATUS_SET) ? 1 : 0;
+    H->iter = iter;
+    PSP_HIP(hipMemcpyAsync(dev_blk, host_blk, sizeof(KryDev), hipMemcpyHostToDevice, stream()));
+    ka.S = reinterpret_cast<const KryDev *>(dev_blk);
+    ka.i0 = i0;
+    ka.i1 = i1;
+    ka.i2 = i2;
+  }
+  const double *coef_dev = nullptr;
+  if (flags & PSP_VEC_COEF_DEV) {  // axpy_dot takes a = -(this value) from the device
+    *reinterpret_cast<double *>(host_blk + sizeof(KryDev)) = scal_host[0];
+    PSP_HIP(hipMemcpyAsync(dev_blk + sizeof(KryDev), host_blk + sizeof(KryDev), sizeof(double), hipMemcpyHostToDevice,
+                           stream()));
+    coef_dev = reinterpret_cast<const double *>(dev_blk + sizeof(KryDev));
+    sv[0] = qnan;
+  }
+  double *const *v = vec_dev;
+  double *part = w->partials;
+  int np = 0, rc = PSP_OK;
+  switch (pass) {
+    case PSP_VEC_LIN2: rc = k_lin2(n, sv[0], v[0], sv[1], v[1], v[2]); break;
+    case PSP_VEC_SCAL: rc = k_scal(n, sv[0], v[0]); break;
+    case PSP_VEC_BICG_P:
+      rc = k_bicg_p(n, v[0], v[1], v[2], v[3], dinv_dev, sv[0], sv[1], (flags & PSP_VEC_FIRST) != 0, ka);
+      break;
+    case PSP_VEC_BICG_S: rc = k_bicg_s(n, v[0], v[1], v[2], v[3], dinv_dev, sv[0], ka); break;
+    case PSP_VEC_BICG_XR:
+      rc = k_bicg_xr(n, v[0], v[1], v[2], v[3], v[4], v[5], v[6], sv[0], sv[1], part, &np, ka);
+      break;
+    case PSP_VEC_CGS_Q: rc = k_cgs_q(n, v[0], v[1], v[2], v[3], v[4], dinv_dev, sv[0], ka); break;
+    case PSP_VEC_CGS_R: rc = k_cgs_r(n, v[0], v[1], v[2], sv[0], part, &np, ka); break;
+    case PSP_VEC_CGS_P: rc = k_cgs_p(n, v[0], v[1], v[2], v[3], v[4], dinv_dev, sv[0], ka); break;
+    case PSP_VEC_QMRS_KV: rc = k_qmrs_kv(n, v[0], v[1], dinv_dev, part, &np); break;
+    case PSP_VEC_QMRS_PG: rc = k_qmrs_pg(n, v[0], v[1], v[2], v[3], sv[0], ka); break;
+    case PSP_VEC_QMRS_V: rc = k_qmrs_v(n, v[0], v[1], sv[0], part, &np, ka); break;
+    case PSP_VEC_QMRS_DX:
+      rc = k_qmrs_dx(n, v[0], v[1], v[2], v[3], v[4], dinv_dev, sv[0], sv[1], sv[2], part, &np, ka);
+      break;
+    case PSP_VEC_AXPY_DOT: rc = k_axpy_dot(n, sv[0], v[0], v[1], v[2], part, &np, coef_dev); break;
+    case PSP_VEC_AXPY_DOT_CHAIN:
+      // (the partial sums ping-pong between two arrays, as in the Gram-Schmidt loop of gmres)
+      if (prev_ws) part = w->partials + kMaxParts;
+      rc = k_axpy_dot_chain(n, prev_ws ? w->partials : v[0], np_prev, v[1], v[2], v[3], v[4], part, &np);
+      break;
+    case PSP_VEC_JACOBI_SWEEP: rc = k_jacobi_sweep(n, v[0], dinv_dev, v[1], v[2]); break;
+    case PSP_VEC_DINV: rc = k_dinv(n, v[0], sv[0], v[1], part, &np); break;
+    case PSP_VEC_SCALE_DIV: rc = k_scale_div(n, v[0], sv[0], v[1], nullptr); break;
+    case PSP_VEC_LANCZOS: rc = k_lanczos(n, v[0], sv[0], sv[1], v[1], v[2], dinv_dev, v[3], part, &np, nullptr); break;
+    case PSP_VEC_LANCZOS_PLAIN: rc = k_lanczos_plain(n, v[0], sv[0], sv[1], v[1], v[2]); break;
+    case PSP_VEC_MINRES_WX:
+      rc = k_minres_wx(n, v[0], sv[0], sv[1], sv[2], sv[3], v[1], v[2], v[3], (flags & PSP_VEC_SCALED) != 0, sv[4],
+                       nullptr);
+      break;
+    case PSP_VEC_MINRES_WX_VNEXT: rc = k_minres_wx_vnext(n, v[0], v[1], v[2], v[3], v[4], nullptr); break;
+  }
+  if (rc != PSP_OK) return rc;
+  if (I.nsums > 0) {
+    // the finished sums first: when the chain wrote the second array, the first one is what PREV_WS hands on next
+    PSP_TRY(finish_partials(part, np, I.nsums, sums_dev));
+    t_dbg_nparts = part == w->partials ? np : 0;
+  }
+  PSP_HIP(hipStreamSynchronize(stream()));  // the pinned block above is free again
+  return PSP_OK;
+}
+
+int psp_debug_vec_form(int *V, int *pre) {
+  if (!V || !pre) return fail(PSP_EINVAL, "psp_debug_vec_form: NULL argument");
+  *V = t_last_v;
+  *pre = t_last_pre;
   return PSP_OK;
 }
 

@@ -890,8 +890,9 @@ def _check_odd_solve(O, solver, A, b, jacobi, got):
 
 @pytest.mark.parametrize("solver", ["cgs", "bicgstab", "qmrs", "gmres"])
 def test_fused_krylov_passes_at_odd_n(oracle, solver):
-    """The fused passes of cgs / bicgstab / qmrs / gmres(20) have no entry point of their own: ten iterations on an odd-sized
-    system, where their 8-byte forms run, without a preconditioner and with Jacobi in both of its forms."""
+    """The fused passes of cgs / bicgstab / qmrs / gmres(20) inside their solvers (each pass on its own:
+    tests/test_gpu_vec_passes.py): ten iterations on an odd-sized system, where their 8-byte forms run, without a
+    preconditioner and with Jacobi in both of its forms."""
     from pysparse_amd import device as dev
     for name, A in _odd_systems(oracle).items():
         n = A.shape[0]
