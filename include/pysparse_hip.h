@@ -487,6 +487,35 @@ int psp_mg_line_axis(const psp_mg_t *K, int *axis);
 /* *box = 1 for a handle created with PSP_MG_BOX, 0 for every other handle */
 int psp_mg_stencil(const psp_mg_t *K, int *box);
 
+/* precon.multigrid(A, grid, omega, steps, galerkin=True, interp='operator'): the Galerkin cycle with operator-dependent
+ * ("black box") interpolation, for coefficients that jump between regions a few cells wide; DESIGN.md 9j.  A flag of
+ * psp_mg_create_csr_ex / _sss_ex, valid only together with PSP_MG_GALERKIN; PSP_MG_BOX may be added, PSP_MG_SINGLE may not
+ * (PSP_EINVAL, "not supported", before any device call), and psp_mg_create_*_line has no such form.  The accepted
+ * operators, the checking pass, the level grids and the smoother are those of the handle without the flag.  The
+ * prolongation of level l is derived from the level's stored stencil S_p[d]: along a coarsened axis an odd fine index has
+ * the single parent (i - 1) / 2, an even one lies between its parents i / 2 - 1 and i / 2; with F the axes on which point p
+ * lies between, the stencil is collapsed onto F (T[delta] = sum of S_p[d] over the d that agree with delta on F) and
+ * w_p = -sum over delta != 0 of (T[delta] / T[0]) w_{p + delta}, neighbours inside the grid only, in rounds |F| = 1, 2, 3; a
+ * point whose T[0] is not finite and > 0 takes the linear weights and is counted.  R = P' / 2^(coarsened axes),
+ * A_{l+1} = R A_l P with the two-sum accumulation of PSP_MG_BOX.  Restriction and prolongation are gathers without atomics:
+ * the same bits from call to call, from csr and sss handles and from host and device entry points.  There is no tail
+ * kernel: every level above the last is launches, the dense product of the last level is one more; psp_mg_info reports
+ * tail_first_level == levels and launches_per_apply = (levels - 1)(max(steps - 1, 1) + steps + 2) + 1.  psp_mg_precon_block*
+ * applies the single cycle column by column (psp_mg_block_info reports 0 columns, psp_mg_block_reserve does nothing).
+ * psp_mg_bytes counts the weights as operator bytes. */
+#define PSP_MG_INTERP 16u
+/* *operator_dependent = 1 for a handle created with PSP_MG_INTERP, 0 for every other handle */
+int psp_mg_interp(const psp_mg_t *K, int *operator_dependent);
+/* the points of level `level` (0 .. levels - 2) that took the linear weights; PSP_EINVAL without PSP_MG_INTERP */
+int psp_mg_interp_fallbacks(psp_mg_t *K, int level, long long *points);
+/* Test hook: the weights of the prolongation from level `level` + 1 to `level` (0 .. levels - 2), slot-major over the
+ * level's fine points: slot s, point p at W_host[s * prod(level grid) + p].  There are 2^ndim slots, of which those with a
+ * bit on an axis that is not coarsened hold zeros.  Bit a of s names the parent along axis a: 0 the lower one -- coarse
+ * index i_a / 2 - 1 of an even fine index i_a, the only parent (i_a - 1) / 2 of an odd one, i_a itself on an axis that is
+ * not coarsened --, 1 the upper one, coarse index i_a / 2 of an even fine index.  A slot whose parent does not exist
+ * holds 0.  *nslots_inout: in, the room in slots; out, 2^ndim; with W_host NULL only the count is returned. */
+int psp_mg_transfer_weights(psp_mg_t *K, int level, int *nslots_inout, double *W_host);
+
 /* --------------------------------------------------------- operator protocol */
 
 /* Host callback operator: the C image of SpMatrix_Matvec / SpMatrix_Precon

@@ -36,6 +36,7 @@ psp_mg_create_csr_galerkin psp_mg_create_sss_galerkin psp_mg_is_galerkin psp_mg_
 psp_mg_precon_block psp_mg_precon_block_dev psp_mg_block_reserve psp_mg_block_info
 psp_mg_create_csr_ex psp_mg_create_sss_ex psp_mg_precision psp_mg_bytes
 psp_mg_create_csr_line psp_mg_create_sss_line psp_mg_line_axis psp_mg_stencil
+psp_mg_interp psp_mg_interp_fallbacks psp_mg_transfer_weights
 psp_op_from_csr psp_op_from_sss psp_op_from_jacobi psp_op_from_ssor psp_op_from_callback psp_op_destroy
 psp_pcg psp_pcg_dev psp_minres psp_minres_dev psp_cgs psp_bicgstab psp_qmrs psp_gmres
 psp_k_dot psp_k_residual psp_k_pupdate psp_k_csr_matvec_dot psp_k_xr_update psp_k_gather
@@ -175,6 +176,8 @@ def _declare(L):
         "psp_mg_precision": [vp, pi], "psp_mg_bytes": [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
         "psp_mg_create_csr_line": [vp, i, pi, d, i, i, pvp], "psp_mg_create_sss_line": [vp, i, pi, d, i, i, pvp],
         "psp_mg_line_axis": [vp, pi], "psp_mg_stencil": [vp, pi],
+        "psp_mg_interp": [vp, pi], "psp_mg_interp_fallbacks": [vp, i, C.POINTER(C.c_longlong)],
+        "psp_mg_transfer_weights": [vp, i, pi, vp],
         "psp_op_from_mg": [vp, pvp],
         "psp_op_from_csr": [vp, pvp], "psp_op_from_sss": [vp, pvp], "psp_op_from_jacobi": [vp, pvp],
         "psp_op_from_callback": [i, HOST_APPLY_FN, vp, pvp], "psp_op_destroy": [vp],

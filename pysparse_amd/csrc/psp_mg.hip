@@ -34,6 +34,11 @@
 // pattern {-1, 0, 1}^ND, 9 points in 2-D and 27 in 3-D: a checking and extraction pass of its own, level 0 stored like every
 // lower level, the Galerkin chain summed without losing its rounding errors; the cycle kernels are the ones below.
 //
+// interp = 'operator' (PSP_MG_INTERP; psp_mg_interp.h) is the stored mode with transfers derived from each
+// level's own stencil, for coefficients that jump between regions: weights per level, a weighted Galerkin product,
+// restriction and prolongation kernels of its own; the smoother kernels are the ones below.  Every level is launches, the
+// dense coarsest product one more: there is no tail launch.
+//
 // Blocks of k vectors (psp_mg_precon_block): block forms of the five cycle kernels, one thread per
 // point and up to KC columns, the row's coefficients loaded once per point (Op::load_row / ax_row); the same schedule, the
 // same launches whatever k is, column c with the bits of the single cycle on column c.
@@ -662,6 +667,7 @@ __global__ __launch_bounds__(256) void mg_check_w4_kernel(int n, MgStencil S, Mg
 
 #include "psp_mg_galerkin.h"
 #include "psp_mg_line.h"
+#include "psp_mg_interp.h"
 
 // ====================================================================== the handle
 
@@ -707,6 +713,12 @@ struct psp_mg {
   std::vector<const double *> line_lo;
   // stencil='box' (section 9i): level 0 of a stored handle has the full pattern like every level below it
   bool box = false;
+  // interp='operator' (psp_mg_interp.h; section 9j): per level above the last the 2^ndim weight arrays of its prolongation
+  // in one allocation, and the points of the level that took the linear weights.  No tail launch: `tail_first` is the last
+  // level, whose dense product the schedule's tail step launches on its own (`tail` stays null, `minv` is used).
+  bool interp = false;
+  std::vector<double *> wts;
+  std::vector<long long> fallbacks;
 };
 
 namespace {
@@ -940,7 +952,7 @@ int mg_check_args(const psp_csr *A, int ndim, const int *grid, double omega, int
 
 // the geometry of the cycle, the same in both modes: the level grids (n, co, nc, rs, N of every level; c, d, w are left
 // 0), the first level of the tail and the launches of one application
-int mg_level_grids(psp_mg *K, const int n[3], int steps, int line = -1) {
+int mg_level_grids(psp_mg *K, const int n[3], int steps, int line = -1, bool notail = false) {
   int cur[3] = {n[0], n[1], n[2]};
   for (;;) {
     psp_mg::Level L;
@@ -966,6 +978,12 @@ int mg_level_grids(psp_mg *K, const int n[3], int steps, int line = -1) {
     // no tail kernel: per level above the last `steps` sweeps, the restriction, the prolongation and `steps` sweeps; one
     // solve of the last level, which is a single line
     K->launches = (nl - 1) * (2 * steps + 2) + 1;
+    if (nl > kMaxLevels) return fail(PSP_EINVAL, "multigrid: too many levels");
+    return PSP_OK;
+  }
+  if (notail) {
+    // section 9j: the launches of every level above the last as below, and the dense product of the last one
+    K->launches = (nl - 1) * ((steps >= 2 ? steps - 1 : 1) + 1 + 1 + steps) + 1;
     if (nl > kMaxLevels) return fail(PSP_EINVAL, "multigrid: too many levels");
     return PSP_OK;
   }
@@ -1040,6 +1058,17 @@ int mg_upload_tail(psp_mg *K, const std::vector<double> &inv, LevelOf &&level) {
     return fail(PSP_ENOMEM, "multigrid: tail table allocation failed");
   }
   K->op_bytes += bytes + sizeof T;
+  return PSP_OK;
+}
+
+// interp='operator' (section 9j): the coarsest level's inverse alone -- there is no tail launch and no table of it
+int mg_upload_inverse(psp_mg *K, const std::vector<double> &inv) {
+  const size_t bytes = sizeof(double) * inv.size();
+  if (hipMalloc(&K->minv, bytes) != hipSuccess || hipMemcpy(K->minv, inv.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PSP_ENOMEM, "multigrid: coarsest inverse allocation failed");
+  }
+  K->op_bytes += bytes;
   return PSP_OK;
 }
 
@@ -1173,6 +1202,29 @@ int launch_galerkin(const GLevel &S, long Nc, double omega, const GOut &o, int *
   });
 }
 
+// interp='operator' (section 9j): the weights of level l's prolongation from its stored stencil -- round m computes the
+// points that lie between coarse points along m axes from the rounds before it --, then A_{l+1} = R A_l P with them.
+// counter: the level's count of points that took the linear weights, on the device
+int launch_weights_galerkin(psp_mg *K, int l, double omega, unsigned long long *counter, int *flag) {
+  const GLevel &S = K->glev[l];
+  const long N = K->lev[l].N, Nc = K->lev[l + 1].N;
+  const size_t bytes = sizeof(double) * ((size_t)N << S.nd);
+  if (hipMalloc((void **)&K->wts[l], bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PSP_ENOMEM, "multigrid(interp='operator'): weight allocation failed");
+  }
+  K->op_bytes += bytes;
+  double *W = K->wts[l];
+  const GOut o = g_out(K->glev[l + 1]);
+  return g_dispatch(S, [&](auto sh) {
+    for (int round = 0; round <= sh.nd; ++round)
+      hipLaunchKernelGGL((mg_weights_kernel<sh.nd, sh.noff>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream(), S, N,
+                         round, W, counter);
+    hipLaunchKernelGGL((mg_galerkin_w_kernel<sh.nd, sh.noff>), dim3((unsigned)((Nc + 255) / 256)), dim3(256), 0, stream(), S,
+                       (const double *)W, N, Nc, omega, o, flag);
+  });
+}
+
 // the dense matrix of a (small) level from its downloaded arrays: blk = diagonal, omega / diagonal, the lower arrays
 void g_dense(const GLevel &G, const std::vector<double> &blk, std::vector<double> *M) {
   const int n0 = G.a.n[0], n1 = G.a.n[1], n2 = G.a.n[2], m = n0 * n1 * n2;
@@ -1264,13 +1316,17 @@ int g_build_lines(psp_mg *K, int *flag) {
 }
 
 // mg_create_galerkin's part of mg_make; flags: three ints on the device (the extraction's, the Galerkin product's, the
-// rounding's)
-int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
+// rounding's); counters: with interp='operator' one zeroed counter per level on the device, else null
+int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags, unsigned long long *counters = nullptr) {
   const double omega = K->omega;
   const bool single = K->single;
   const int nd = n[2] > 1 ? 3 : n[1] > 1 ? 2 : 1;
-  PSP_TRY(mg_level_grids(K, n, K->steps, K->line_axis));  // section 9c's, or with a line axis section 9h's
+  PSP_TRY(mg_level_grids(K, n, K->steps, K->line_axis, K->interp));  // section 9c's, or with a line axis section 9h's
   const int nl = (int)K->lev.size();
+  if (K->interp) {
+    K->wts.assign(nl, nullptr);
+    K->fallbacks.assign(nl, 0);
+  }
   // the level vectors and the level operators' arrays (a single-precision handle allocates a level's double arrays only
   // when it builds the level)
   PSP_TRY(mg_alloc_own_vectors(K));
@@ -1316,7 +1372,10 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
   // A_{l+1} = R_l A_l P_l, level by level
   for (int l = 0; l + 1 < nl; ++l) {
     if (single) PSP_TRY(g_alloc_level(K, l + 1, &K->coef[l + 1], &K->glev[l + 1]));
-    PSP_TRY(launch_galerkin(K->glev[l], K->lev[l + 1].N, omega, g_out(K->glev[l + 1]), flags + 1, K->box));
+    if (K->interp)
+      PSP_TRY(launch_weights_galerkin(K, l, omega, counters + l, flags + 1));
+    else
+      PSP_TRY(launch_galerkin(K->glev[l], K->lev[l + 1].N, omega, g_out(K->glev[l + 1]), flags + 1, K->box));
     PSP_LAUNCH_CHECK();
     if (single) {
       PSP_TRY(g_round_level(K, l, flags + 2));
@@ -1333,12 +1392,15 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
   // the two flags of the chain, read once
   int chain[2] = {0, 0};
   PSP_HIP(hipMemcpyAsync(chain, flags + 1, 2 * sizeof(int), hipMemcpyDeviceToHost, stream()));
+  if (K->interp)
+    PSP_HIP(hipMemcpyAsync(K->fallbacks.data(), counters, nl * sizeof(long long), hipMemcpyDeviceToHost, stream()));
   PSP_HIP(hipStreamSynchronize(stream()));
   if (single) g_release_double(K, nl - 1);
   if (chain[0]) return fail(PSP_ESINGULAR, "multigrid(galerkin=True): a level operator's diagonal is not finite and > 0");
   if (chain[1]) return fail(PSP_EINVAL, "%s", kSingleRange);
   g_dense(C, blk, &M);
   PSP_TRY(dense_inverse(m, M, &inv));
+  if (K->interp) return mg_upload_inverse(K, inv);
   if (single) return mg_upload_tail(K, inv, [&](int l) { return K->glev32[l]; });
   return mg_upload_tail(K, inv, [&](int l) { return K->glev[l]; });
 }
@@ -1346,9 +1408,12 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags) {
 // line: -1, or the axis of the line smoother (section 9h), which has no single-precision form; box: level 0 in the full
 // layout (section 9i), which has no line-smoothed form
 int mg_create_galerkin_line(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, int line,
-                            psp_mg **out, bool box = false) {
+                            psp_mg **out, bool box = false, bool interp = false) {
   int n[3];
   PSP_TRY(mg_check_args(A, ndim, grid, omega, steps, out, n));
+  if (interp && (line != -1 || single))
+    return fail(PSP_EINVAL, "multigrid(interp='operator'): operator-dependent interpolation with %s is not supported",
+                line != -1 ? "a line smoother" : "precision='single'");
   if (line != -1 && box) return fail(PSP_EINVAL, "multigrid(line=%d): stencil='box' with a line smoother is not supported", line);
   if (line != -1) {
     if (ndim < 2) return fail(PSP_EINVAL, "multigrid(line=%d): a grid of one axis has no axis left to coarsen", line);
@@ -1361,22 +1426,38 @@ int mg_create_galerkin_line(psp_csr *A, int ndim, const int *grid, double omega,
   PSP_TRY(ensure_device());
   int *flags = nullptr;
   PSP_HIP(hipMalloc((void **)&flags, 3 * sizeof(int)));
+  unsigned long long *counters = nullptr;  // interp='operator': the fallback points of every level
+  if (interp && (hipMalloc((void **)&counters, kMaxLevels * sizeof(unsigned long long)) != hipSuccess ||
+                 hipMemsetAsync(counters, 0, kMaxLevels * sizeof(unsigned long long), stream()) != hipSuccess)) {
+    (void)hipGetLastError();
+    (void)hipFree(counters);
+    (void)hipFree(flags);
+    return fail(PSP_ENOMEM, "multigrid(interp='operator'): counter allocation failed");
+  }
   const int rc = mg_make(A, ndim, omega, steps, true, single, out, [&](psp_mg *K) {
     K->line_axis = line;
     K->box = box;
-    return g_build(K, A, n, flags);
+    K->interp = interp;
+    return g_build(K, A, n, flags, counters);
   });
+  (void)hipFree(counters);
   (void)hipFree(flags);
   return rc;
 }
 
-int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, bool box, psp_mg **out) {
-  return mg_create_galerkin_line(A, ndim, grid, omega, steps, single, -1, out, box);
+int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, bool box, psp_mg **out,
+                       bool interp = false) {
+  return mg_create_galerkin_line(A, ndim, grid, omega, steps, single, -1, out, box, interp);
 }
 
 // the flags of psp_mg_create_*_ex: known bits only, and PSP_MG_BOX selects the pattern of a stored level 0
 int mg_check_flags(const char *fn, unsigned flags) {
-  if (flags & ~(unsigned)(PSP_MG_GALERKIN | PSP_MG_SINGLE | PSP_MG_BOX)) return fail(PSP_EINVAL, "%s: unknown flags 0x%x", fn, flags);
+  if (flags & ~(unsigned)(PSP_MG_GALERKIN | PSP_MG_SINGLE | PSP_MG_BOX | PSP_MG_INTERP))
+    return fail(PSP_EINVAL, "%s: unknown flags 0x%x", fn, flags);
+  if ((flags & PSP_MG_INTERP) && !(flags & PSP_MG_GALERKIN))
+    return fail(PSP_EINVAL, "%s: PSP_MG_INTERP (interp='operator') needs PSP_MG_GALERKIN (galerkin=True): the weights come from stored level operators", fn);
+  if ((flags & PSP_MG_INTERP) && (flags & PSP_MG_SINGLE))
+    return fail(PSP_EINVAL, "%s: PSP_MG_INTERP (interp='operator') with PSP_MG_SINGLE (precision='single') is not supported", fn);
   if ((flags & PSP_MG_BOX) && !(flags & PSP_MG_GALERKIN))
     return fail(PSP_EINVAL, "%s: PSP_MG_BOX (stencil='box') needs PSP_MG_GALERKIN (galerkin=True): the matrix-free mode stores no level 0", fn);
   return PSP_OK;
@@ -1580,6 +1661,7 @@ struct CycleOps {
   }
   // a workgroup per tile of coarse points; a block's columns in gridDim.y, one each
   int restrict_to(int l, Vec x, Vec b, Vec bc) const {
+    if (K->interp) return restrict_w(l, x, b, bc);
     return with_op<false>(l, [&](auto tag, const auto &A) {
       using Op = typename decltype(tag)::type;
       int tile[3];
@@ -1602,6 +1684,39 @@ struct CycleOps {
         mg_with_b<S, Op::kFinest>(b, launch);
     });
   }
+  // interp='operator' (section 9j): the transfers with the level's weights and the coarsest level's dense product, each one
+  // launch on one vector in double -- such a handle has no single-precision form, and mg_apply_block_dev sends its columns
+  // through here one at a time
+  int not_weighted() const { return fail(PSP_EINVAL, "multigrid: internal error (weighted transfers on a single-precision handle or a block)"); }
+  int restrict_w(int l, Vec x, Vec b, Vec bc) const {
+    if constexpr (std::is_same_v<S, double>) {
+      if (k) return not_weighted();
+      const GLevel &G = K->glev[l];
+      int tile[3];
+      long g[3];
+      mg_restrict_grid(G.a, tile, g);
+      const unsigned tiles = (unsigned)(g[0] * g[1] * g[2]);
+      return g_dispatch(G, [&](auto sh) {
+        hipLaunchKernelGGL((mg_restrict_w_kernel<GOp<sh.nd, sh.noff, double>>), dim3(tiles), dim3(kResThreads), 0, stream(), G,
+                           tile[0], tile[1], tile[2], (int)g[0], (int)g[1], (const double *)K->wts[l], K->lev[l].N,
+                           x.as<const double>(), b.as<const double>(), bc.as<double>());
+      });
+    } else {
+      return not_weighted();
+    }
+  }
+  void prolong_w(int l, Vec e, Vec x) const {
+    if constexpr (std::is_same_v<S, double>) {
+      const long N = K->lev[l].N;
+      hipLaunchKernelGGL(mg_prolong_w_kernel, grid(N), dim3(256), 0, stream(), K->lev[l].a, N, (const double *)K->wts[l],
+                         e.as<const double>(), x.as<double>());
+    }
+  }
+  void dense(Vec b, Vec x) const {
+    if constexpr (std::is_same_v<S, double>)
+      hipLaunchKernelGGL(mg_dense_kernel, dim3(1), dim3(64), 0, stream(), (int)K->lev[K->tail_first].N, (const double *)K->minv,
+                         b.as<const double>(), x.as<double>());
+  }
   // the tail's ends are both the caller's (the whole grid is the tail) or both the handle's; a block's columns are a
   // workgroup each
   template <class Op>  // MfOp<3> or GTailOp: K->tail is that mode's table
@@ -1622,7 +1737,9 @@ struct CycleOps {
   }
   // with a line axis the step is the last level's x = T^-1 b: that level is one line and A = T there (section 9h)
   void tail(Vec b, Vec x) const {
-    if (K->line_axis >= 0)
+    if (K->interp)
+      dense(b, x);
+    else if (K->line_axis >= 0)
       (void)line_sweep<true>(K->tail_first, 1.0, Vec(), b, x);
     else if (K->galerkin)
       launch_tail<GTailOp<S>>(b, x);
@@ -1630,6 +1747,7 @@ struct CycleOps {
       launch_tail<MfOp<3, S>>(b, x);
   }
   void prolong(int l, Vec e, Vec x) const {
+    if (K->interp) return prolong_w(l, e, x);
     const long N = K->lev[l].N;
     const MgLevelArgT<S> &a = mf_level<S>(K, l);
     if (!k)
@@ -1717,7 +1835,8 @@ void mg_block_free(psp_mg *K) {
 
 // the block cycle's level vectors for at least k columns (k = 0: none)
 int mg_block_reserve(psp_mg *K, int k) {
-  if (k > 0 && (k <= K->blk_cols || K->line_axis >= 0)) return PSP_OK;  // a line handle has no block vectors to reserve
+  // a line handle has no block vectors to reserve, nor has one with operator-dependent interpolation
+  if (k > 0 && (k <= K->blk_cols || K->line_axis >= 0 || K->interp)) return PSP_OK;
   mg_block_free(K);
   if (k == 0) return PSP_OK;
   if (!mg_alloc_vectors(K, k, &K->blk, &K->blk_bytes)) {
@@ -1743,10 +1862,13 @@ int mg_apply_dev(psp_mg *K, const double *b_dev, double *y_dev) {
 // the bits of mg_apply_dev on the column, K's launches whatever k is.  Y must not overlap X.  The handle is locked by the
 // caller.
 int mg_apply_block_dev(psp_mg *K, int k, const double *X, long ldx, double *Y, long ldy, const int *frozen) {
-  if (K->line_axis >= 0) {
-    // the line kernels have no block form (section 9h): the single cycle column by column, no block vectors.  The frozen
-    // flags live on the device, so a caller that has some goes column by column itself (mg_block_routed is false).
-    if (frozen) return fail(PSP_EINVAL, "multigrid: internal error (a block cycle with frozen columns on a line handle)");
+  if (K->line_axis >= 0 || K->interp) {
+    // the line kernels have no block form (section 9h), nor have the weighted transfers (section 9j): the single cycle
+    // column by column, no block vectors.  The frozen flags live on the device, so a caller that has some goes column by
+    // column itself (mg_block_routed is false).
+    if (frozen)
+      return fail(PSP_EINVAL, "multigrid: internal error (a block cycle with frozen columns on %s)",
+                  K->interp ? "a handle with interp='operator'" : "a line handle");
     for (int c = 0; c < k; ++c) PSP_TRY(mg_apply_dev(K, X + (size_t)c * ldx, Y + (size_t)c * ldy));
     return PSP_OK;
   }
@@ -1761,7 +1883,7 @@ int mg_launches(const psp_mg *K) { return K->launches; }
 // Where op_apply_block and the batched PCG loop run the block cycle and where they keep the column-by-column path: by the
 // measurements of DESIGN.md section 9e (profiles/mg_block_timing.json).
 bool mg_block_routed(const psp_mg *K) {
-  if (K->line_axis >= 0) return false;
+  if (K->line_axis >= 0 || K->interp) return false;
   return K->galerkin ? kRouteBlockGalerkin : kRouteBlockMatrixFree;
 }
 
@@ -1803,17 +1925,17 @@ extern "C" {
 int psp_mg_create_csr_ex(psp_csr_t *A, int ndim, const int *grid, double omega, int steps, unsigned flags, psp_mg_t **out) {
   PSP_API_GUARD_H(A);
   PSP_TRY(mg_check_flags("psp_mg_create_csr_ex", flags));
-  const bool single = (flags & PSP_MG_SINGLE) != 0, box = (flags & PSP_MG_BOX) != 0;
-  if (flags & PSP_MG_GALERKIN) return mg_create_galerkin(A, ndim, grid, omega, steps, single, box, out);
+  const bool single = (flags & PSP_MG_SINGLE) != 0, box = (flags & PSP_MG_BOX) != 0, interp = (flags & PSP_MG_INTERP) != 0;
+  if (flags & PSP_MG_GALERKIN) return mg_create_galerkin(A, ndim, grid, omega, steps, single, box, out, interp);
   return mg_create(A, ndim, grid, omega, steps, single, out);
 }
 
 int psp_mg_create_sss_ex(psp_sss_t *A, int ndim, const int *grid, double omega, int steps, unsigned flags, psp_mg_t **out) {
   PSP_TRY(mg_check_flags("psp_mg_create_sss_ex", flags));
-  const bool single = (flags & PSP_MG_SINGLE) != 0, box = (flags & PSP_MG_BOX) != 0;
+  const bool single = (flags & PSP_MG_SINGLE) != 0, box = (flags & PSP_MG_BOX) != 0, interp = (flags & PSP_MG_INTERP) != 0;
   if (flags & PSP_MG_GALERKIN)
     return mg_create_sss(A, "psp_mg_create_sss_galerkin",
-                         [&](psp_csr *F) { return mg_create_galerkin(F, ndim, grid, omega, steps, single, box, out); });
+                         [&](psp_csr *F) { return mg_create_galerkin(F, ndim, grid, omega, steps, single, box, out, interp); });
   return mg_create_sss(A, "psp_mg_create_sss", [&](psp_csr *F) { return mg_create(F, ndim, grid, omega, steps, single, out); });
 }
 
@@ -1840,6 +1962,36 @@ int psp_mg_line_axis(const psp_mg_t *K, int *axis) {
 int psp_mg_stencil(const psp_mg_t *K, int *box) {
   if (!K || !box) return fail(PSP_EINVAL, "psp_mg_stencil: NULL argument");
   *box = K->box ? 1 : 0;
+  return PSP_OK;
+}
+
+int psp_mg_interp(const psp_mg_t *K, int *operator_dependent) {
+  if (!K || !operator_dependent) return fail(PSP_EINVAL, "psp_mg_interp: NULL argument");
+  *operator_dependent = K->interp ? 1 : 0;
+  return PSP_OK;
+}
+
+int psp_mg_interp_fallbacks(psp_mg_t *K, int level, long long *points) {
+  PSP_API_GUARD_H(K);
+  if (!K || !points) return fail(PSP_EINVAL, "psp_mg_interp_fallbacks: NULL argument");
+  if (!K->interp) return fail(PSP_EINVAL, "psp_mg_interp_fallbacks: the handle has no operator-dependent interpolation (interp='linear')");
+  if (level < 0 || level + 1 >= (int)K->lev.size()) return fail(PSP_EINVAL, "psp_mg_interp_fallbacks: no transfer from level %d", level);
+  *points = K->fallbacks[level];
+  return PSP_OK;
+}
+
+int psp_mg_transfer_weights(psp_mg_t *K, int level, int *nslots_inout, double *W_host) {
+  PSP_API_GUARD_H(K);
+  if (!K || !nslots_inout) return fail(PSP_EINVAL, "psp_mg_transfer_weights: NULL argument");
+  if (!K->interp) return fail(PSP_EINVAL, "psp_mg_transfer_weights: the handle stores no weights (interp='linear')");
+  if (level < 0 || level + 1 >= (int)K->lev.size()) return fail(PSP_EINVAL, "psp_mg_transfer_weights: no transfer from level %d", level);
+  const int cap = *nslots_inout, cnt = 1 << K->glev[level].nd;
+  *nslots_inout = cnt;
+  if (!W_host) return PSP_OK;
+  if (cap < cnt) return fail(PSP_EINVAL, "psp_mg_transfer_weights: room for %d slots, the level has %d", cap, cnt);
+  PSP_TRY(ensure_device());
+  PSP_HIP(hipMemcpyAsync(W_host, K->wts[level], sizeof(double) * (size_t)cnt * (size_t)K->lev[level].N, hipMemcpyDeviceToHost, stream()));
+  PSP_HIP(hipStreamSynchronize(stream()));
   return PSP_OK;
 }
 
@@ -1919,6 +2071,7 @@ int psp_mg_destroy(psp_mg_t *K) {
   mg_block_free(K);
   for (double *p : K->coef) (void)hipFree(p);
   for (float *p : K->coef32) (void)hipFree(p);
+  for (double *p : K->wts) (void)hipFree(p);
   mg_free_vectors(&K->vec);
   (void)hipFree(K->minv);
   (void)hipFree(K->tail);
@@ -1930,7 +2083,8 @@ int psp_mg_info(const psp_mg_t *K, int *levels, int *tail_first_level, int *laun
   if (!K) return fail(PSP_EINVAL, "psp_mg_info: NULL handle");
   if (levels) *levels = (int)K->lev.size();
   // a line handle has no tail launch: its last level is one more ordinary launch
-  if (tail_first_level) *tail_first_level = K->line_axis >= 0 ? (int)K->lev.size() : K->tail_first;
+  // nor has a handle with operator-dependent interpolation
+  if (tail_first_level) *tail_first_level = K->line_axis >= 0 || K->interp ? (int)K->lev.size() : K->tail_first;
   if (launches_per_apply) *launches_per_apply = K->launches;
   if (dims)
     for (size_t l = 0; l < K->lev.size(); ++l)

@@ -53,7 +53,7 @@ def _matmat(fn, h, shape, X, Y):
         Y[...] = yb
 
 
-PSP_MG_GALERKIN, PSP_MG_SINGLE, PSP_MG_BOX = 1, 2, 8  # psp_mg_create_*_ex flags (pysparse_hip.h)
+PSP_MG_GALERKIN, PSP_MG_SINGLE, PSP_MG_BOX, PSP_MG_INTERP = 1, 2, 8, 16  # psp_mg_create_*_ex flags (pysparse_hip.h)
 
 
 class DeviceBuffer:
@@ -568,11 +568,22 @@ class DeviceMultigrid:
     def __init__(self, A, grid, omega=0.8, steps=2, galerkin=False):
         self._create(A, grid, omega, steps, galerkin, None)
 
-    def _create(self, A, grid, omega, steps, galerkin, line, stencil="axis"):
+    def _create(self, A, grid, omega, steps, galerkin, line, stencil="axis", interp="linear"):
         """every check, then the handle; line: None, or the axis of DeviceMultigridLine; stencil: 'axis', or
-        DeviceMultigridBox's 'box'"""
+        DeviceMultigridBox's 'box'; interp: 'linear', or DeviceMultigridInterp's 'operator'"""
         if not isinstance(galerkin, bool):
             raise TypeError("galerkin must be a bool")
+        if not isinstance(interp, str):
+            raise TypeError("interp must be a str, 'linear' or 'operator'")
+        if interp not in ("linear", "operator"):
+            raise ValueError("interp must be 'linear' or 'operator'")
+        if interp == "operator":
+            if not galerkin:
+                raise ValueError("interp='operator' needs galerkin=True: the weights come from stored level operators")
+            if line is not None:
+                raise ValueError("interp='operator' with line is not supported")
+            if self._FLAGS & PSP_MG_SINGLE:
+                raise ValueError("interp='operator' with precision='single' is not supported")
         if not isinstance(stencil, str):
             raise TypeError("stencil must be a str, 'axis' or 'box'")
         if stencil not in ("axis", "box"):
@@ -628,6 +639,8 @@ class DeviceMultigrid:
         else:
             create = lib().psp_mg_create_csr_ex if isinstance(A, DeviceCSR) else lib().psp_mg_create_sss_ex
             flags = (PSP_MG_GALERKIN if galerkin else 0) | (PSP_MG_BOX if box else 0) | self._FLAGS
+            if interp == "operator":
+                flags |= PSP_MG_INTERP
             _check_einval(create(A._h, len(dims), g, omega, steps, flags, C.byref(h)))
         self._A = A
         self._h = h
@@ -658,6 +671,28 @@ class DeviceMultigrid:
                 "dims": tuple(tuple(d[3 * l:3 * l + 3]) for l in range(nl.value)), "galerkin": bool(gk.value),
                 "precision": "single" if bits.value == 32 else "double", "line": ax.value if ax.value >= 0 else None,
                 "stencil": "box" if bx.value else "axis"}
+
+    @property
+    def interp(self):
+        """'linear', or 'operator' for DeviceMultigridInterp's operator-dependent interpolation; read-only"""
+        op = C.c_int()
+        check(lib().psp_mg_interp(self._h, C.byref(op)))
+        return "operator" if op.value else "linear"
+
+    def interp_fallbacks(self, level):
+        """test hook (interp='operator'): the points of `level` that took the linear weights (psp_mg_interp_fallbacks)"""
+        pts = C.c_longlong()
+        _check_einval(lib().psp_mg_interp_fallbacks(self._h, int(level), C.byref(pts)))
+        return pts.value
+
+    def transfer_weights(self, level):
+        """test hook (interp='operator'): W[slot, point], the weights of the prolongation onto `level`; bit a of the slot
+        number names the parent along axis a, 0 the lower (or only) one, 1 the upper one (psp_mg_transfer_weights)"""
+        cnt = C.c_int(0)
+        _check_einval(lib().psp_mg_transfer_weights(self._h, int(level), C.byref(cnt), None))
+        W = np.empty((cnt.value, int(np.prod(self.info()["dims"][level]))))
+        check(lib().psp_mg_transfer_weights(self._h, int(level), C.byref(cnt), _ptr(W)))
+        return W
 
     def bytes(self):
         """{"operator", "vector"}: device bytes the handle holds at rest (psp_mg_bytes) -- the level operators with the
@@ -748,6 +783,16 @@ class DeviceMultigridBox(DeviceMultigrid):
             raise ValueError("precision must be 'double' or 'single'")
         self._FLAGS = PSP_MG_SINGLE if precision == "single" else 0
         self._create(A, grid, omega, steps, galerkin, None, stencil)
+
+
+class DeviceMultigridInterp(DeviceMultigrid):
+    """precon.multigrid(..., galerkin=True, interp='operator'): the Galerkin cycle with operator-dependent interpolation,
+    the weights of every level derived from the level operator's own stencil, for coefficients that jump between regions
+    (PSP_MG_INTERP).  stencil is 'axis' or 'box'; interp='linear' is DeviceMultigrid / DeviceMultigridBox.
+    Double precision, no line smoother.  Every method is the parent's; .interp says which transfer the handle has."""
+
+    def __init__(self, A, grid, omega=0.8, steps=2, galerkin=True, stencil="axis", interp="operator"):
+        self._create(A, grid, omega, steps, galerkin, None, stencil, interp)
 
 
 def _solve(fn, A, b, x, tol, maxit, K, hist):
