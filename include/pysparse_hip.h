@@ -85,6 +85,11 @@ int psp_debug_hold_handles(const void *h1, const void *h2, int milliseconds);
 int psp_debug_mid_count(long long *solves, long long *fallbacks);
 /* the same counters for the brick form of those loops (7-offset operators of 3-D grids; psp_mid.hip) */
 int psp_debug_brick_count(long long *solves, long long *fallbacks);
+/* the device memory the handles of this process own through their array type (psp_internal.h DevArray: precon.ssor and
+ * precon.multigrid handles with their set-up temporaries, the staging of csr_mat's host-pointer diagonal and transposed
+ * product): bytes held now, and allocations made so far.  A handle that is closed gives back what it took, whether or not
+ * psp_trim is called; the solvers' vector pool, the placement draws and the per-thread workspaces are not counted */
+int psp_debug_device_bytes(long long *live_bytes, long long *allocations);
 int psp_debug_shake(long long seed, int min_us, int max_us, unsigned point_mask, unsigned rank_mask, int revert_mask);
 int psp_debug_shake_count(long long *injected);
 int psp_debug_spin(int microseconds);

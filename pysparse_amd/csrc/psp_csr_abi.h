@@ -427,10 +427,10 @@ int psp_csr_diagonal(const psp_csr_t *A, double *diag_host) {
   if (!A || !diag_host) return fail(PSP_EINVAL, "psp_csr_diagonal: NULL argument");
   if (A->host) return psp::cpu::csr_diagonal(A, diag_host);
   if (A->multi) return psp::multi_diagonal_host(A->multi, diag_host);
-  DevBuf d;
+  DevArray<double> d;
   PSP_TRY(d.alloc(A->nrows));
-  PSP_TRY(psp_csr_diagonal_dev(A, d.p));
-  return download_strided(diag_host, d.p, A->nrows, 1);
+  PSP_TRY(psp_csr_diagonal_dev(A, d));
+  return download_strided(diag_host, d, A->nrows, 1);
 }
 
 int psp_csr_matvec_dev(psp_csr_t *A, const double *x_dev, double *y_dev) {
@@ -494,12 +494,12 @@ int psp_csr_matvec_transp_stride(psp_csr_t *A, const double *x_host, ptrdiff_t i
   if (!A || !x_host || !y_host) return fail(PSP_EINVAL, "psp_csr_matvec_transp: NULL argument");
   if (A->host) return psp::cpu::csr_matvec(A, x_host, incx, y_host, incy, true);
   PSP_TRY(ensure_device());
-  DevBuf x, y;
+  DevArray<double> x, y;
   PSP_TRY(x.alloc(A->nrows));
   PSP_TRY(y.alloc(A->ncols));
-  PSP_TRY(upload_strided(x.p, x_host, A->nrows, incx));
-  PSP_TRY(psp_csr_matvec_transp_dev(A, x.p, y.p));
-  return download_strided(y_host, y.p, A->ncols, incy);
+  PSP_TRY(upload_strided(x, x_host, A->nrows, incx));
+  PSP_TRY(psp_csr_matvec_transp_dev(A, x, y));
+  return download_strided(y_host, y, A->ncols, incy);
 }
 
 int psp_csr_matvec_transp(psp_csr_t *A, const double *x_host, double *y_host) {

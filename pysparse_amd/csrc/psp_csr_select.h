@@ -1047,17 +1047,6 @@ int csr_spmv_overlap(const psp_csr *A, const double *x, double *y, const double 
 
 namespace {
 
-struct DevBuf {
-  double *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t n) {
-    PSP_HIP(hipMalloc((void **)&p, sizeof(double) * (n ? n : 1)));
-    return PSP_OK;
-  }
-};
-
 int upload_strided(double *dev, const double *host, size_t n, ptrdiff_t inc) {
   if (inc == 1) {
     PSP_HIP(hipMemcpyAsync(dev, host, sizeof(double) * n, hipMemcpyHostToDevice, stream()));

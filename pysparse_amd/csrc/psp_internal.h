@@ -171,6 +171,79 @@ int current_thread_slot();  // 0 for the first thread that used the library, sma
 
 #define PSP_LAUNCH_CHECK() PSP_HIP(hipGetLastError())
 
+// Device memory with an owner: one hipMalloc of sizeof(T) * max(count, 1) bytes that reset() and the
+// destructor give back.  A handle's device arrays are DevArray members, the temporaries of its set-up DevArray locals, and
+// a hand-over is a move; nothing is freed through a list.  hipFree waits for the device, so nothing that still runs loses
+// its buffer.  The two counters cover DevArrays alone (psp_debug_device_bytes): the bytes they hold now and the
+// allocations they have made -- not the solvers' vector pool, the placement draws or the per-thread workspaces.
+inline std::atomic<long long> dev_live_bytes{0}, dev_allocations{0};
+template <typename T>
+class DevArray {
+ public:
+  DevArray() = default;
+  DevArray(DevArray &&o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.forget(); }
+  DevArray &operator=(DevArray &&o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_;
+      bytes_ = o.bytes_;
+      o.forget();
+    }
+    return *this;
+  }
+  DevArray(const DevArray &) = delete;
+  DevArray &operator=(const DevArray &) = delete;
+  ~DevArray() { reset(); }
+  int alloc(size_t count) {  // PSP_ENOMEM / PSP_ENODEV with the runtime's text
+    const hipError_t e = raw_alloc(count);
+    if (e == hipSuccess) return PSP_OK;
+    return fail(e == hipErrorOutOfMemory ? PSP_ENOMEM : PSP_ENODEV, "hipMalloc of %zu x %zu bytes: %s", count, sizeof(T),
+                hipGetErrorString(e));
+  }
+  bool try_alloc(size_t count) {  // for the paths that fall back instead of failing: no error text, no sticky error
+    if (raw_alloc(count) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+  }
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    dev_live_bytes.fetch_sub((long long)bytes_, std::memory_order_relaxed);
+    forget();
+  }
+  T *release() {  // the caller frees it; no longer counted
+    T *p = p_;
+    dev_live_bytes.fetch_sub((long long)bytes_, std::memory_order_relaxed);
+    forget();
+    return p;
+  }
+  void adopt(T *p) {  // a hipMalloc made elsewhere: freed here, not counted
+    reset();
+    p_ = p;
+  }
+  T *get() const { return p_; }
+  operator T *() const { return p_; }
+
+ private:
+  hipError_t raw_alloc(size_t count) {
+    reset();
+    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
+    void *p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) return e;
+    p_ = static_cast<T *>(p);
+    bytes_ = bytes;
+    dev_live_bytes.fetch_add((long long)bytes, std::memory_order_relaxed);
+    dev_allocations.fetch_add(1, std::memory_order_relaxed);
+    return e;
+  }
+  void forget() {
+    p_ = nullptr;
+    bytes_ = 0;
+  }
+  T *p_ = nullptr;
+  size_t bytes_ = 0;
+};
+
 // Reductions: every reducing kernel is launched with at most kMaxParts workgroups; workgroup b leaves its partial
 // sums in partials[slot*kMaxParts + b].  They are added in ONE canonical order, whichever kernel does the adding:
 //     R(v[0..m))        = wave_sum over the 64 lanes of ( v[l] + v[l+64] + v[l+128] + ... ), lane l, left to right

@@ -687,23 +687,23 @@ struct psp_mg {
   // cols columns of leading dimension N.  `vec`: the single cycle's, one column, allocated at creation.  `blk`: the block
   // cycle's (section 9e), blk_cols columns, allocated by the first block call and grown on demand.
   struct Vecs {
-    void *x = nullptr, *b = nullptr, *t = nullptr;
+    DevArray<char> x, b, t;
   };
   std::vector<Vecs> vec, blk;
   int blk_cols = 0;
   size_t blk_bytes = 0;
   int tail_first = 0;  // first level of the tail launch
   int launches = 0;    // kernel launches of one application
-  void *minv = nullptr;  // the coarsest level's inverse, in the handle's scalar type
-  void *tail = nullptr;  // the mode's TailArg on the device
+  DevArray<char> minv;   // the coarsest level's inverse, in the handle's scalar type
+  DevArray<char> tail;   // the mode's TailArg on the device
   // galerkin = True (psp_mg_galerkin.h): the stored level operators; `coef` owns each level's arrays in one allocation
   // (diagonal, omega / diagonal, the lower arrays).  A single-precision handle keeps the rounded arrays in `coef32`; its
   // `coef[l]` lives only until level l + 1 is built and level l is rounded.
   bool galerkin = false;
   std::vector<GLevel> glev;
   std::vector<GLevelT<float>> glev32;
-  std::vector<double *> coef;
-  std::vector<float *> coef32;
+  std::vector<DevArray<double>> coef;
+  std::vector<DevArray<float>> coef32;
   size_t op_bytes = 0, vec_bytes = 0;  // what the handle holds at rest (psp_mg_bytes)
   // line = a (psp_mg_line.h; section 9h): the axis that is solved exactly and never coarsened, -1 without.  Per level the
   // geometry of its grid lines and the lower array of offset -st_a; the level's second array holds q, not omega / diagonal.
@@ -717,7 +717,7 @@ struct psp_mg {
   // in one allocation, and the points of the level that took the linear weights.  No tail launch: `tail_first` is the last
   // level, whose dense product the schedule's tail step launches on its own (`tail` stays null, `minv` is used).
   bool interp = false;
-  std::vector<double *> wts;
+  std::vector<DevArray<double>> wts;
   std::vector<long long> fallbacks;
 };
 
@@ -833,16 +833,14 @@ int read_flag(int *bad_dev, int *bad) {
 // one checking pass: launch(flag) with a zeroed device flag, then the flag read back into *bad
 template <class Launch>
 int run_check(int *bad, Launch &&launch) {
-  int *bad_dev = nullptr;
-  PSP_HIP(hipMalloc((void **)&bad_dev, sizeof(int)));
+  DevArray<int> bad_dev;
+  PSP_TRY(bad_dev.alloc(1));
   hipError_t e = hipMemsetAsync(bad_dev, 0, sizeof(int), stream());
   if (e == hipSuccess) {
     launch(bad_dev);
     e = hipGetLastError();
   }
-  const int rc = e == hipSuccess ? read_flag(bad_dev, bad) : fail(PSP_ENODEV, "multigrid: %s", hipGetErrorString(e));
-  (void)hipFree(bad_dev);
-  return rc;
+  return e == hipSuccess ? read_flag(bad_dev, bad) : fail(PSP_ENODEV, "multigrid: %s", hipGetErrorString(e));
 }
 
 // c_a, d0 of A and the exact check that A is that stencil on that grid -- from the CSR arrays, or, for a handle that only
@@ -996,31 +994,21 @@ int mg_level_grids(psp_mg *K, const int n[3], int steps, int line = -1, bool not
   return PSP_OK;
 }
 
-// hipFree waits for the device, so nothing that still runs loses its buffers
-void mg_free_vectors(std::vector<psp_mg::Vecs> *set) {
-  for (psp_mg::Vecs &V : *set)
-    for (void *p : {V.x, V.b, V.t}) (void)hipFree(p);
-  set->clear();
-}
-
 // The level vectors of the handle, `cols` columns wide, into *set; *total grows by the bytes allocated.  The finest level
 // works in the caller's vectors and one spare; a level that heads the tail needs its b and x in memory (the restriction
 // above it writes b, the prolongation reads x); the levels inside the tail have none.  A single-precision handle holds
 // floats, and an x of its own for the finest level too when that level is not the tail: the caller's y is double and takes
-// only the last sweep (mg_schedule).  false: an allocation failed; what was allocated is in *set for the caller to free.
+// only the last sweep (mg_schedule).  false: an allocation failed; what was allocated is in *set for the caller to drop.
 bool mg_alloc_vectors(const psp_mg *K, int cols, std::vector<psp_mg::Vecs> *set, size_t *total) {
-  set->assign(K->lev.size(), psp_mg::Vecs());
+  *set = std::vector<psp_mg::Vecs>(K->lev.size());
   for (int l = 0; l <= K->tail_first; ++l) {
     psp_mg::Vecs &V = (*set)[l];
     const size_t bytes = (K->single ? sizeof(float) : sizeof(double)) * (size_t)K->lev[l].N * (size_t)cols;
     const bool own_x = l > 0 || (K->single && K->tail_first > 0);
-    void **const want[3] = {l < K->tail_first ? &V.t : nullptr, own_x ? &V.x : nullptr, l > 0 ? &V.b : nullptr};
-    for (void **p : want) {
+    DevArray<char> *const want[3] = {l < K->tail_first ? &V.t : nullptr, own_x ? &V.x : nullptr, l > 0 ? &V.b : nullptr};
+    for (DevArray<char> *p : want) {
       if (!p) continue;
-      if (hipMalloc(p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-      }
+      if (!p->try_alloc(bytes)) return false;
       *total += bytes;
     }
   }
@@ -1051,7 +1039,7 @@ int mg_upload_tail(psp_mg *K, const std::vector<double> &inv, LevelOf &&level) {
   const std::vector<float> inv32(K->single ? inv.begin() : inv.end(), inv.end());
   const void *src = K->single ? (const void *)inv32.data() : (const void *)inv.data();
   const size_t bytes = (K->single ? sizeof(float) : sizeof(double)) * inv.size();
-  if (hipMalloc(&K->minv, bytes) != hipSuccess || hipMalloc(&K->tail, sizeof T) != hipSuccess ||
+  if (!K->minv.try_alloc(bytes) || !K->tail.try_alloc(sizeof T) ||
       hipMemcpy(K->minv, src, bytes, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(K->tail, &T, sizeof T, hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipGetLastError();
@@ -1064,7 +1052,7 @@ int mg_upload_tail(psp_mg *K, const std::vector<double> &inv, LevelOf &&level) {
 // interp='operator' (section 9j): the coarsest level's inverse alone -- there is no tail launch and no table of it
 int mg_upload_inverse(psp_mg *K, const std::vector<double> &inv) {
   const size_t bytes = sizeof(double) * inv.size();
-  if (hipMalloc(&K->minv, bytes) != hipSuccess || hipMemcpy(K->minv, inv.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+  if (!K->minv.try_alloc(bytes) || hipMemcpy(K->minv, inv.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipGetLastError();
     return fail(PSP_ENOMEM, "multigrid: coarsest inverse allocation failed");
   }
@@ -1209,10 +1197,8 @@ int launch_weights_galerkin(psp_mg *K, int l, double omega, unsigned long long *
   const GLevel &S = K->glev[l];
   const long N = K->lev[l].N, Nc = K->lev[l + 1].N;
   const size_t bytes = sizeof(double) * ((size_t)N << S.nd);
-  if (hipMalloc((void **)&K->wts[l], bytes) != hipSuccess) {
-    (void)hipGetLastError();
+  if (!K->wts[l].try_alloc((size_t)N << S.nd))
     return fail(PSP_ENOMEM, "multigrid(interp='operator'): weight allocation failed");
-  }
   K->op_bytes += bytes;
   double *W = K->wts[l];
   const GOut o = g_out(K->glev[l + 1]);
@@ -1247,12 +1233,9 @@ void g_dense(const GLevel &G, const std::vector<double> &blk, std::vector<double
 // the arrays of level l in one allocation of scalar type S (diagonal, omega / diagonal, the lower arrays), and the
 // level's pointers into it
 template <class S>
-int g_alloc_level(psp_mg *K, int l, S **owner, GLevelT<S> *G) {
+int g_alloc_level(psp_mg *K, int l, DevArray<S> *owner, GLevelT<S> *G) {
   const size_t N = (size_t)K->lev[l].N;
-  if (hipMalloc((void **)owner, sizeof(S) * (size_t)(2 + G->noff) * N) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(PSP_ENOMEM, "multigrid: level operator allocation failed");
-  }
+  if (!owner->try_alloc((size_t)(2 + G->noff) * N)) return fail(PSP_ENOMEM, "multigrid: level operator allocation failed");
   G->diag = *owner;
   G->w = *owner + N;
   for (int k = 0; k < G->noff; ++k) G->lo[k] = *owner + (size_t)(2 + k) * N;
@@ -1278,8 +1261,7 @@ int g_round_level(psp_mg *K, int l, int *flag) {
   return PSP_OK;
 }
 void g_release_double(psp_mg *K, int l) {
-  (void)hipFree(K->coef[l]);
-  K->coef[l] = nullptr;
+  K->coef[l].reset();
   GLevel &G = K->glev[l];
   G.diag = G.w = nullptr;
   for (int k = 0; k < kGMaxOff; ++k) G.lo[k] = nullptr;
@@ -1324,17 +1306,17 @@ int g_build(psp_mg *K, const psp_csr *A, const int n[3], int *flags, unsigned lo
   PSP_TRY(mg_level_grids(K, n, K->steps, K->line_axis, K->interp));  // section 9c's, or with a line axis section 9h's
   const int nl = (int)K->lev.size();
   if (K->interp) {
-    K->wts.assign(nl, nullptr);
+    K->wts.resize(nl);
     K->fallbacks.assign(nl, 0);
   }
   // the level vectors and the level operators' arrays (a single-precision handle allocates a level's double arrays only
   // when it builds the level)
   PSP_TRY(mg_alloc_own_vectors(K));
   K->glev.resize(nl);
-  K->coef.assign(nl, nullptr);
+  K->coef.resize(nl);
   if (single) {
     K->glev32.resize(nl);
-    K->coef32.assign(nl, nullptr);
+    K->coef32.resize(nl);
   }
   for (int l = 0; l < nl; ++l) {
     psp_mg::Level &L = K->lev[l];
@@ -1424,25 +1406,20 @@ int mg_create_galerkin_line(psp_csr *A, int ndim, const int *grid, double omega,
   if (!(A->ind && A->col && A->val) || A->w4_only)
     return fail(PSP_EINVAL, "multigrid(galerkin=True): the handle no longer holds its index arrays on the device");
   PSP_TRY(ensure_device());
-  int *flags = nullptr;
-  PSP_HIP(hipMalloc((void **)&flags, 3 * sizeof(int)));
-  unsigned long long *counters = nullptr;  // interp='operator': the fallback points of every level
-  if (interp && (hipMalloc((void **)&counters, kMaxLevels * sizeof(unsigned long long)) != hipSuccess ||
+  DevArray<int> flags;
+  PSP_TRY(flags.alloc(3));
+  DevArray<unsigned long long> counters;  // interp='operator': the fallback points of every level
+  if (interp && (!counters.try_alloc(kMaxLevels) ||
                  hipMemsetAsync(counters, 0, kMaxLevels * sizeof(unsigned long long), stream()) != hipSuccess)) {
     (void)hipGetLastError();
-    (void)hipFree(counters);
-    (void)hipFree(flags);
     return fail(PSP_ENOMEM, "multigrid(interp='operator'): counter allocation failed");
   }
-  const int rc = mg_make(A, ndim, omega, steps, true, single, out, [&](psp_mg *K) {
+  return mg_make(A, ndim, omega, steps, true, single, out, [&](psp_mg *K) {
     K->line_axis = line;
     K->box = box;
     K->interp = interp;
     return g_build(K, A, n, flags, counters);
   });
-  (void)hipFree(counters);
-  (void)hipFree(flags);
-  return rc;
 }
 
 int mg_create_galerkin(psp_csr *A, int ndim, const int *grid, double omega, int steps, bool single, bool box, psp_mg **out,
@@ -1714,15 +1691,15 @@ struct CycleOps {
   }
   void dense(Vec b, Vec x) const {
     if constexpr (std::is_same_v<S, double>)
-      hipLaunchKernelGGL(mg_dense_kernel, dim3(1), dim3(64), 0, stream(), (int)K->lev[K->tail_first].N, (const double *)K->minv,
+      hipLaunchKernelGGL(mg_dense_kernel, dim3(1), dim3(64), 0, stream(), (int)K->lev[K->tail_first].N, (const double *)K->minv.get(),
                          b.as<const double>(), x.as<double>());
   }
   // the tail's ends are both the caller's (the whole grid is the tail) or both the handle's; a block's columns are a
   // workgroup each
   template <class Op>  // MfOp<3> or GTailOp: K->tail is that mode's table
   void launch_tail(Vec b, Vec x) const {
-    const auto *T = (const TailArg<typename Op::Level> *)K->tail;
-    const S *minv = (const S *)K->minv;
+    const auto *T = (const TailArg<typename Op::Level> *)K->tail.get();
+    const S *minv = (const S *)K->minv.get();
     mg_with_io<S>(b, x, [&](auto *bp, auto *xp) {
       using TB = Elem<decltype(bp)>;
       using TX = Elem<decltype(xp)>;
@@ -1828,7 +1805,7 @@ int mg_schedule(psp_mg *K, typename Ops::Vec b_dev, typename Ops::Vec y_dev, con
 }
 
 void mg_block_free(psp_mg *K) {
-  mg_free_vectors(&K->blk);
+  K->blk.clear();
   K->blk_cols = 0;
   K->blk_bytes = 0;
 }
@@ -2069,12 +2046,6 @@ int psp_mg_level_operator(psp_mg_t *K, int level, int *offsets_out, int *noff_in
 int psp_mg_destroy(psp_mg_t *K) {
   if (!K) return PSP_OK;
   mg_block_free(K);
-  for (double *p : K->coef) (void)hipFree(p);
-  for (float *p : K->coef32) (void)hipFree(p);
-  for (double *p : K->wts) (void)hipFree(p);
-  mg_free_vectors(&K->vec);
-  (void)hipFree(K->minv);
-  (void)hipFree(K->tail);
   delete K;
   return PSP_OK;
 }

@@ -696,6 +696,12 @@ int psp_debug_hold_handles(const void *h1, const void *h2, int milliseconds) {
   return PSP_OK;
 }
 
+int psp_debug_device_bytes(long long *live_bytes, long long *allocations) {
+  if (live_bytes) *live_bytes = psp::dev_live_bytes.load();
+  if (allocations) *allocations = psp::dev_allocations.load();
+  return PSP_OK;
+}
+
 int psp_debug_shake(long long seed, int min_us, int max_us, unsigned point_mask, unsigned rank_mask, int revert_mask) {
   if (!psp::tuning_env("PSP_TUNING"))  // (PSP_TUNING itself is set whenever the tuning switches are honoured)
     return fail(PSP_EINVAL, "psp_debug_shake: delay injection needs a process started with PSP_TUNING=1");

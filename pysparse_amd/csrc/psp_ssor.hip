@@ -50,23 +50,23 @@ struct psp_ssor {
   //   backward: rows in (backward level, row) order; b_row[u] = position of the u-th row, b_ptr / b_val /
   //             b_pos = its mirrored upper entries from the LAST to the first (the order in which the CPU's
   //             descending sweep scatters into it, preconmodule.c:186-193).
-  int *pos2row = nullptr, *row2pos = nullptr;
+  DevArray<int> pos2row, row2pos;
   std::vector<int> ptr_f, ptr_b;  // level l = positions / backward slots [ptr[l], ptr[l+1])
-  int *dptr_f = nullptr, *dptr_b = nullptr;
-  int *f_ptr = nullptr, *f_pos = nullptr;
-  double *f_val = nullptr;
-  int *b_row = nullptr, *b_ptr = nullptr, *b_pos = nullptr;
-  double *b_val = nullptr;
+  DevArray<int> dptr_f, dptr_b;
+  DevArray<int> f_ptr, f_pos;
+  DevArray<double> f_val;
+  DevArray<int> b_row, b_ptr, b_pos;
+  DevArray<double> b_val;
   // Rows with at most 8 entries per sweep (every stencil) use a padded slot-major (ELL) form instead of the
   // ptr / val / pos triple: entry s of slot u at [s*n + u], counts in one byte per slot.  A level kernel is
   // bound by its chain of dependent loads, not by bytes (a level of the 512^3 operator is ~1 us of streaming):
   // with the entries at computable addresses the chain is two loads deep (entries -> x) instead of three
   // (ptr -> entries -> x; four in the backward sweep, whose slots are rows by indirection).
   int ell_f = 0, ell_b = 0;  // width (0: CSR form)
-  unsigned char *fc8 = nullptr, *bc8 = nullptr;
-  double *da = nullptr;                 // diagonal by position
-  double *bp = nullptr, *xp = nullptr;  // right-hand side and iterate by position
-  double *temp = nullptr;               // y (symgs) / h (ssor) by position
+  DevArray<unsigned char> fc8, bc8;
+  DevArray<double> da;      // diagonal by position
+  DevArray<double> bp, xp;  // right-hand side and iterate by position
+  DevArray<double> temp;    // y (symgs) / h (ssor) by position
   // the level launches of one application, captured once (they only touch the buffers above)
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
@@ -84,30 +84,30 @@ struct psp_ssor {
   struct RunSet {
     std::vector<Run> runs;
     int m = 0;                 // slots in all runs = stride of dpk
-    unsigned *dpk = nullptr;   // distances to the dependencies' slots, two 16-bit fields per word, word-major
-    double2 *vp = nullptr;     // the row's values in pairs (entries 2k, 2k+1), pair-major: one 16-byte load per pair
-    double *dar = nullptr;     // diagonal by compact index
-    double2 *gd = nullptr;     // per application: (G, diagonal); G = everything of the row's formula that does not
+    DevArray<unsigned> dpk;    // distances to the dependencies' slots, two 16-bit fields per word, word-major
+    DevArray<double2> vp;      // the row's values in pairs (entries 2k, 2k+1), pair-major: one 16-byte load per pair
+    DevArray<double> dar;      // diagonal by compact index
+    DevArray<double2> gd;      // per application: (G, diagonal); G = everything of the row's formula that does not
                                // depend on this sweep
-    int2 *ticks = nullptr;     // (first slot, count <= kRunTick), never across a level boundary; zero-padded per run
+    DevArray<int2> ticks;      // (first slot, count <= kRunTick), never across a level boundary; zero-padded per run
   } run_f, run_b;
-  int *run_progress = nullptr;  // [0]: tick the walking workgroup has finished (throttles the L2 helpers), [1]: sink
+  DevArray<int> run_progress;  // [0]: tick the walking workgroup has finished (throttles the L2 helpers), [1]: sink
   // Round 3: BRICKS for 3-D grid operators whose levels are too wide for the runs (ssor_brick_kernel below).  The
   // positions are then ordered (brick, level, row) instead of (level, row): a brick of 32^3 grid points is one run for
   // one workgroup, the bricks themselves are a coarse wavefront handed out in dependency order.
   struct BrickSet {
     int nbricks = 0;
-    int2 *ticks = nullptr;     // every brick's ticks, each brick's followed by kRunPad empty ones
-    int4 *info = nullptr;      // per brick in processing order: first tick, ticks, first halo entry, halo entries
-    int4 *pred = nullptr;      // per brick: up to three bricks it waits for (processing-order indices, -1: none)
-    int *halo_pos = nullptr;   // positions of the dependencies outside the brick, brick-major
-    unsigned *dpk = nullptr;   // per entry 16 bits: 0 none, 1..0x7fff distance back in slots, 0x8000 | i: halo entry i
-    double2 *vp = nullptr;
-    double *dar = nullptr;
-    double2 *gd = nullptr;
-    int4 *tick_ext = nullptr;  // pipelined sweeps: per tick its range of the brick's halo (first, count) and, 10 bits per
+    DevArray<int2> ticks;      // every brick's ticks, each brick's followed by kRunPad empty ones
+    DevArray<int4> info;       // per brick in processing order: first tick, ticks, first halo entry, halo entries
+    DevArray<int4> pred;       // per brick: up to three bricks it waits for (processing-order indices, -1: none)
+    DevArray<int> halo_pos;    // positions of the dependencies outside the brick, brick-major
+    DevArray<unsigned> dpk;    // per entry 16 bits: 0 none, 1..0x7fff distance back in slots, 0x8000 | i: halo entry i
+    DevArray<double2> vp;
+    DevArray<double> dar;
+    DevArray<double2> gd;
+    DevArray<int4> tick_ext;   // pipelined sweeps: per tick its range of the brick's halo (first, count) and, 10 bits per
                                // predecessor, how many ticks of that predecessor must be complete before it is gathered
-    int *flags = nullptr;      // [0 .. nbricks): done; [nbricks]: next brick to hand out; [nbricks + 1]: error;
+    DevArray<int> flags;       // [0 .. nbricks): done; [nbricks]: next brick to hand out; [nbricks + 1]: error;
                                // [nbricks + 2]: scratch word of run_pre_kernel
   } brick_f, brick_b;
   bool brick_mode = false;
@@ -1292,42 +1292,45 @@ __global__ void ssor_fill_backward_kernel(int n, const int *__restrict__ rows, c
   }
 }
 
+// hipcub's two calls, once: call(nullptr, bytes) asks for the size of the temporary storage, call(tmp, bytes) works in it.
+// The caller owns tmp and with it the moment it is given back.
+template <class Call>
+hipError_t cub_two_calls(DevArray<char> &tmp, Call &&call) {
+  size_t bytes = 0;
+  hipError_t e = call((void *)nullptr, bytes);
+  if (e == hipSuccess && !tmp.try_alloc(bytes)) e = hipErrorOutOfMemory;
+  if (e == hipSuccess) e = call((void *)tmp.get(), bytes);
+  return e;
+}
+
 // longest-path levels of the lower (dir 0) / upper (dir 1) dependency graph, rows sorted by level
-int build_schedule(const psp_csr *F, int dir, int **rows_out, std::vector<int> *ptr_out, int **level_out = nullptr) {
+int build_schedule(const psp_csr *F, int dir, DevArray<int> *rows_out, std::vector<int> *ptr_out,
+                   DevArray<int> *level_out = nullptr) {
   const int n = F->nrows;
-  int *level = nullptr, *changed = nullptr, *keys = nullptr, *vals = nullptr, *rows = nullptr, *dptr = nullptr;
-  void *tmp = nullptr;
-  int rc = PSP_OK;
+  // (declared in reverse: locals go in reverse order of declaration, and the order in which memory is given back decides
+  // the addresses of what is allocated next -- level is freed first, tmp last)
+  DevArray<char> tmp;
+  DevArray<int> dptr, rows, vals, keys, changed, level;
   const int grid = std::min((n + 255) / 256, 16384);
-#define SS_HIP(call)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (call);                                                             \
-    if (e_ != hipSuccess) {                                                             \
-      rc = fail(e_ == hipErrorOutOfMemory ? PSP_ENOMEM : PSP_ENODEV, "%s: %s", #call,    \
-                hipGetErrorString(e_));                                                 \
-      goto done;                                                                        \
-    }                                                                                   \
-  } while (0)
-  {
-    SS_HIP(hipMalloc((void **)&level, sizeof(int) * (size_t)n));
-    SS_HIP(hipMalloc((void **)&changed, sizeof(int)));
-    SS_HIP(hipMemsetAsync(level, 0, sizeof(int) * (size_t)n, stream()));
-    // Kahn's algorithm, one launch per level, kLevBatch levels between two looks at the counters
-    // (PSP_SSOR_KAHN=0: the relaxation sweeps below, the round-1 method -- same levels)
-    static const bool kahn = [] {
-      const char *e = psp::tuning_env("PSP_SSOR_KAHN");
-      return e ? atoi(e) != 0 : true;
-    }();
-    bool have_levels = false;
-    if (kahn && n > 0) {
-      constexpr int kLevBatch = 64;
-      const long maxlev = std::min<long>(n, 1L << 22);
-      int *deps = nullptr, *fr[2] = {nullptr, nullptr}, *cnt = nullptr;
-      bool ok = hipMalloc((void **)&deps, sizeof(int) * (size_t)n) == hipSuccess &&
-                hipMalloc((void **)&fr[0], sizeof(int) * (size_t)n) == hipSuccess &&
-                hipMalloc((void **)&fr[1], sizeof(int) * (size_t)n) == hipSuccess &&
-                hipMalloc((void **)&cnt, sizeof(int) * (size_t)(maxlev + kLevBatch + 2)) == hipSuccess &&
+  PSP_TRY(level.alloc((size_t)n));
+  PSP_TRY(changed.alloc(1));
+  PSP_HIP(hipMemsetAsync(level, 0, sizeof(int) * (size_t)n, stream()));
+  // Kahn's algorithm, one launch per level, kLevBatch levels between two looks at the counters
+  // (PSP_SSOR_KAHN=0: the relaxation sweeps below, the round-1 method -- same levels)
+  static const bool kahn = [] {
+    const char *e = psp::tuning_env("PSP_SSOR_KAHN");
+    return e ? atoi(e) != 0 : true;
+  }();
+  bool have_levels = false;
+  if (kahn && n > 0) {
+    constexpr int kLevBatch = 64;
+    const long maxlev = std::min<long>(n, 1L << 22);
+    {
+      DevArray<int> cnt, fr1, fr0, deps;  // (freed in the order deps, fr0, fr1, cnt)
+      bool ok = deps.try_alloc((size_t)n) && fr0.try_alloc((size_t)n) && fr1.try_alloc((size_t)n) &&
+                cnt.try_alloc((size_t)(maxlev + kLevBatch + 2)) &&
                 hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)(maxlev + kLevBatch + 2), stream()) == hipSuccess;
+      int *const fr[2] = {fr0, fr1};
       if (ok) {
         hipLaunchKernelGGL(kahn_init_kernel, dim3((n + 255) / 256), dim3(256), 0, stream(), n, F->ind, F->col, dir, deps,
                            level, fr[0], cnt);
@@ -1355,65 +1358,44 @@ int build_schedule(const psp_csr *F, int dir, int **rows_out, std::vector<int> *
         have_levels = ok && done_rows == n;  // a cycle (not a triangle) or a failure: fall through
       }
       (void)hipGetLastError();
-      if (deps) (void)hipFree(deps);
-      if (fr[0]) (void)hipFree(fr[0]);
-      if (fr[1]) (void)hipFree(fr[1]);
-      if (cnt) (void)hipFree(cnt);
-      if (!have_levels) SS_HIP(hipMemsetAsync(level, 0, sizeof(int) * (size_t)n, stream()));
     }
-    int passes = 0;
-    for (; !have_levels;) {
-      SS_HIP(hipMemsetAsync(changed, 0, sizeof(int), stream()));
-      for (int p = 0; p < 8; ++p)
-        hipLaunchKernelGGL(level_pass_kernel, dim3(grid), dim3(256), 0, stream(), n, F->ind, F->col, dir, level,
-                           changed);
-      SS_HIP(hipGetLastError());
-      int h = 0;
-      SS_HIP(hipMemcpyAsync(&h, changed, sizeof(int), hipMemcpyDeviceToHost, stream()));
-      SS_HIP(hipStreamSynchronize(stream()));
-      passes += 8;
-      if (!h) break;
-      if (passes > 8 * (n / 8 + 2)) {
-        rc = fail(PSP_EINVAL, "ssor: level computation did not converge");
-        goto done;
-      }
-    }
-    SS_HIP(hipMalloc((void **)&keys, sizeof(int) * (size_t)n));
-    SS_HIP(hipMalloc((void **)&vals, sizeof(int) * (size_t)n));
-    SS_HIP(hipMalloc((void **)&rows, sizeof(int) * (size_t)n));
-    hipLaunchKernelGGL(iota_kernel, dim3(grid), dim3(256), 0, stream(), n, vals);
-    size_t bytes = 0;
-    SS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, level, keys, vals, rows, n, 0, 32, stream()));
-    SS_HIP(hipMalloc(&tmp, bytes ? bytes : 1));
-    SS_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, level, keys, vals, rows, n, 0, 32, stream()));  // stable
-    int maxlev = 0;
-    SS_HIP(hipMemcpyAsync(&maxlev, keys + (n - 1), sizeof(int), hipMemcpyDeviceToHost, stream()));
-    SS_HIP(hipStreamSynchronize(stream()));
-    const int nlev = maxlev + 1;
-    SS_HIP(hipMalloc((void **)&dptr, sizeof(int) * ((size_t)nlev + 1)));
-    hipLaunchKernelGGL(level_ptr_kernel, dim3(grid), dim3(256), 0, stream(), n, keys, dptr);
-    SS_HIP(hipGetLastError());
-    ptr_out->assign((size_t)nlev + 1, 0);
-    SS_HIP(hipMemcpyAsync(ptr_out->data(), dptr, sizeof(int) * (size_t)nlev, hipMemcpyDeviceToHost, stream()));
-    SS_HIP(hipStreamSynchronize(stream()));
-    (*ptr_out)[(size_t)nlev] = n;
-    *rows_out = rows;
-    rows = nullptr;
-    if (level_out) {  // the caller keeps the level of every row (brick ordering)
-      *level_out = level;
-      level = nullptr;
-    }
+    if (!have_levels) PSP_HIP(hipMemsetAsync(level, 0, sizeof(int) * (size_t)n, stream()));
   }
-done:
-#undef SS_HIP
-  (void)hipFree(level);
-  (void)hipFree(changed);
-  (void)hipFree(keys);
-  (void)hipFree(vals);
-  (void)hipFree(rows);
-  (void)hipFree(dptr);
-  (void)hipFree(tmp);
-  return rc;
+  int passes = 0;
+  for (; !have_levels;) {
+    PSP_HIP(hipMemsetAsync(changed, 0, sizeof(int), stream()));
+    for (int p = 0; p < 8; ++p)
+      hipLaunchKernelGGL(level_pass_kernel, dim3(grid), dim3(256), 0, stream(), n, F->ind, F->col, dir, level,
+                         changed);
+    PSP_HIP(hipGetLastError());
+    int h = 0;
+    PSP_HIP(hipMemcpyAsync(&h, changed, sizeof(int), hipMemcpyDeviceToHost, stream()));
+    PSP_HIP(hipStreamSynchronize(stream()));
+    passes += 8;
+    if (!h) break;
+    if (passes > 8 * (n / 8 + 2)) return fail(PSP_EINVAL, "ssor: level computation did not converge");
+  }
+  PSP_TRY(keys.alloc((size_t)n));
+  PSP_TRY(vals.alloc((size_t)n));
+  PSP_TRY(rows.alloc((size_t)n));
+  hipLaunchKernelGGL(iota_kernel, dim3(grid), dim3(256), 0, stream(), n, vals);
+  PSP_HIP(cub_two_calls(tmp, [&](void *t, size_t &bytes) {  // stable
+    return hipcub::DeviceRadixSort::SortPairs(t, bytes, level.get(), keys.get(), vals.get(), rows.get(), n, 0, 32, stream());
+  }));
+  int maxlev = 0;
+  PSP_HIP(hipMemcpyAsync(&maxlev, keys + (n - 1), sizeof(int), hipMemcpyDeviceToHost, stream()));
+  PSP_HIP(hipStreamSynchronize(stream()));
+  const int nlev = maxlev + 1;
+  PSP_TRY(dptr.alloc((size_t)nlev + 1));
+  hipLaunchKernelGGL(level_ptr_kernel, dim3(grid), dim3(256), 0, stream(), n, keys, dptr);
+  PSP_HIP(hipGetLastError());
+  ptr_out->assign((size_t)nlev + 1, 0);
+  PSP_HIP(hipMemcpyAsync(ptr_out->data(), dptr, sizeof(int) * (size_t)nlev, hipMemcpyDeviceToHost, stream()));
+  PSP_HIP(hipStreamSynchronize(stream()));
+  (*ptr_out)[(size_t)nlev] = n;
+  *rows_out = std::move(rows);
+  if (level_out) *level_out = std::move(level);  // the caller keeps the level of every row (brick ordering)
+  return PSP_OK;
 }
 
 }  // namespace
@@ -1436,7 +1418,7 @@ template <int KIND, int W>
 static void sweep_w(const psp_ssor *K, hipStream_t st, bool forward, int first) {
   const std::vector<int> &lp = forward ? K->ptr_f : K->ptr_b;
   const int *dlp = forward ? K->dptr_f : K->dptr_b;
-  const int *rowmap = forward ? nullptr : K->b_row;
+  const int *rowmap = forward ? nullptr : K->b_row.get();
   const int *ptr = forward ? K->f_ptr : K->b_ptr;
   const int *pos = forward ? K->f_pos : K->b_pos;
   const double *val = forward ? K->f_val : K->b_val;
@@ -1636,128 +1618,108 @@ int ssor_error_check(psp_ssor *K) { return brick_error_check(K, true); }
 
 namespace {
 
-template <typename T>
-int dev_alloc(T **p, size_t count) {
-  PSP_HIP(hipMalloc((void **)p, sizeof(T) * (count ? count : 1)));
-  return PSP_OK;
-}
-
 // exclusive prefix sum of cnt[0..n) into ptr[0..n]
 int exclusive_scan(int n, const int *cnt, int *ptr, long *total) {
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  PSP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, ptr, n, stream()));
-  PSP_HIP(hipMalloc(&tmp, bytes ? bytes : 1));
-  hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cnt, ptr, n, stream());
   int last_ptr = 0, last_cnt = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&last_ptr, ptr + (n - 1), sizeof(int), hipMemcpyDeviceToHost, stream());
-  if (e == hipSuccess) e = hipMemcpyAsync(&last_cnt, cnt + (n - 1), sizeof(int), hipMemcpyDeviceToHost, stream());
-  if (e == hipSuccess) e = hipStreamSynchronize(stream());
-  (void)hipFree(tmp);
-  if (e != hipSuccess) return fail(PSP_ENODEV, "ssor: scan failed: %s", hipGetErrorString(e));
+  hipError_t e;
+  {
+    DevArray<char> tmp;
+    e = cub_two_calls(tmp, [&](void *t, size_t &bytes) {
+      return hipcub::DeviceScan::ExclusiveSum(t, bytes, cnt, ptr, n, stream());
+    });
+    if (e == hipSuccess) e = hipMemcpyAsync(&last_ptr, ptr + (n - 1), sizeof(int), hipMemcpyDeviceToHost, stream());
+    if (e == hipSuccess) e = hipMemcpyAsync(&last_cnt, cnt + (n - 1), sizeof(int), hipMemcpyDeviceToHost, stream());
+    if (e == hipSuccess) e = hipStreamSynchronize(stream());
+  }
+  if (e != hipSuccess)
+    return fail(e == hipErrorOutOfMemory ? PSP_ENOMEM : PSP_ENODEV, "ssor: scan failed: %s", hipGetErrorString(e));
   *total = (long)last_ptr + last_cnt;
   const int tot = (int)*total;
   PSP_HIP(hipMemcpy(ptr + n, &tot, sizeof(int), hipMemcpyHostToDevice));
   return PSP_OK;
 }
 
-// the level-ordered copies of the triangle (see struct psp_ssor)
-int build_level_ordered(psp_ssor *K, int *rows_f, int *rows_b) {
+// the level-ordered copies of the triangle (see struct psp_ssor); rows_f becomes K->pos2row
+int build_level_ordered(psp_ssor *K, DevArray<int> &&rows_f, const int *rows_b) {
   const psp_sss *S = K->S;
   const psp_csr *F = S->full;
   const int n = K->n;
   const int grid = std::min((n + 255) / 256, 65536);
-  K->pos2row = rows_f;  // takes ownership
-  PSP_TRY(dev_alloc(&K->row2pos, n));
+  K->pos2row = std::move(rows_f);
+  PSP_TRY(K->row2pos.alloc((size_t)n));
   hipLaunchKernelGGL(invert_perm_kernel, dim3(grid), dim3(256), 0, stream(), n, K->pos2row, K->row2pos);
   PSP_LAUNCH_CHECK();
-  int *cnt = nullptr;
-  PSP_TRY(dev_alloc(&cnt, n));
-  int rc = PSP_OK;
+  DevArray<int> cnt;
+  PSP_TRY(cnt.alloc((size_t)n));
   long tot = 0;
   // forward
   hipLaunchKernelGGL(ssor_fill_forward_kernel, dim3(grid), dim3(256), 0, stream(), n, K->pos2row, S->ind, S->col, S->val,
                      K->row2pos, cnt, (const int *)nullptr, (int *)nullptr, (double *)nullptr);
-  if (rc == PSP_OK) rc = dev_alloc(&K->f_ptr, (size_t)n + 1);
-  if (rc == PSP_OK) rc = exclusive_scan(n, cnt, K->f_ptr, &tot);
-  if (rc == PSP_OK) rc = dev_alloc(&K->f_pos, (size_t)tot);
-  if (rc == PSP_OK) rc = dev_alloc(&K->f_val, (size_t)tot);
-  if (rc == PSP_OK)
-    hipLaunchKernelGGL(ssor_fill_forward_kernel, dim3(grid), dim3(256), 0, stream(), n, K->pos2row, S->ind, S->col,
-                       S->val, K->row2pos, (int *)nullptr, K->f_ptr, K->f_pos, K->f_val);
+  PSP_TRY(K->f_ptr.alloc((size_t)n + 1));
+  PSP_TRY(exclusive_scan(n, cnt, K->f_ptr, &tot));
+  PSP_TRY(K->f_pos.alloc((size_t)tot));
+  PSP_TRY(K->f_val.alloc((size_t)tot));
+  hipLaunchKernelGGL(ssor_fill_forward_kernel, dim3(grid), dim3(256), 0, stream(), n, K->pos2row, S->ind, S->col,
+                     S->val, K->row2pos, (int *)nullptr, K->f_ptr, K->f_pos, K->f_val);
   // backward
-  if (rc == PSP_OK) rc = dev_alloc(&K->b_row, n);
-  if (rc == PSP_OK)
-    hipLaunchKernelGGL(ssor_fill_backward_kernel, dim3(grid), dim3(256), 0, stream(), n, rows_b, F->ind, F->col, F->val,
-                       K->row2pos, cnt, (const int *)nullptr, (int *)nullptr, (double *)nullptr, K->b_row);
-  if (rc == PSP_OK) rc = dev_alloc(&K->b_ptr, (size_t)n + 1);
-  if (rc == PSP_OK) rc = exclusive_scan(n, cnt, K->b_ptr, &tot);
-  if (rc == PSP_OK) rc = dev_alloc(&K->b_pos, (size_t)tot);
-  if (rc == PSP_OK) rc = dev_alloc(&K->b_val, (size_t)tot);
-  if (rc == PSP_OK)
-    hipLaunchKernelGGL(ssor_fill_backward_kernel, dim3(grid), dim3(256), 0, stream(), n, rows_b, F->ind, F->col, F->val,
-                       K->row2pos, (int *)nullptr, K->b_ptr, K->b_pos, K->b_val, (int *)nullptr);
+  PSP_TRY(K->b_row.alloc((size_t)n));
+  hipLaunchKernelGGL(ssor_fill_backward_kernel, dim3(grid), dim3(256), 0, stream(), n, rows_b, F->ind, F->col, F->val,
+                     K->row2pos, cnt, (const int *)nullptr, (int *)nullptr, (double *)nullptr, K->b_row);
+  PSP_TRY(K->b_ptr.alloc((size_t)n + 1));
+  PSP_TRY(exclusive_scan(n, cnt, K->b_ptr, &tot));
+  PSP_TRY(K->b_pos.alloc((size_t)tot));
+  PSP_TRY(K->b_val.alloc((size_t)tot));
+  hipLaunchKernelGGL(ssor_fill_backward_kernel, dim3(grid), dim3(256), 0, stream(), n, rows_b, F->ind, F->col, F->val,
+                     K->row2pos, (int *)nullptr, K->b_ptr, K->b_pos, K->b_val, (int *)nullptr);
   // narrow rows: padded slot-major form, the ptr / pos / val triple is dropped
-  if (rc == PSP_OK) {
-    for (int dir = 0; dir < 2 && rc == PSP_OK; ++dir) {
-      int **ptr = dir ? &K->b_ptr : &K->f_ptr, **pos = dir ? &K->b_pos : &K->f_pos;
-      double **val = dir ? &K->b_val : &K->f_val;
-      int *dmax = nullptr, maxc = 0;
-      rc = dev_alloc(&dmax, 1);
-      if (rc != PSP_OK) break;
+  for (int dir = 0; dir < 2; ++dir) {
+    DevArray<int> &ptr = dir ? K->b_ptr : K->f_ptr, &pos = dir ? K->b_pos : K->f_pos;
+    DevArray<double> &val = dir ? K->b_val : K->f_val;
+    int maxc = 0;
+    {
+      DevArray<int> dmax;
+      PSP_TRY(dmax.alloc(1));
       (void)hipMemsetAsync(dmax, 0, sizeof(int), stream());
       // widest row = largest difference of consecutive offsets
-      hipLaunchKernelGGL(row_len_kernel, dim3(grid), dim3(256), 0, stream(), n, *ptr, cnt);
+      hipLaunchKernelGGL(row_len_kernel, dim3(grid), dim3(256), 0, stream(), n, ptr, cnt);
       hipLaunchKernelGGL(max_int_kernel, dim3(std::min(grid, 2048)), dim3(256), 0, stream(), n, cnt, dmax);
-      if (hipMemcpy(&maxc, dmax, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PSP_ENODEV, "ssor: max");
-      (void)hipFree(dmax);
-      if (rc != PSP_OK) break;
-      static const bool ell_off = [] {
-        const char *e = psp::tuning_env("PSP_SSOR_ELL");
-        return e && atoi(e) == 0;
-      }();
-      int W = 0;
-      for (int w : {1, 2, 3, 4, 6, 8})
-        if (maxc <= w) {
-          W = w;
-          break;
-        }
-      if (maxc == 0 || ell_off) W = 0;
-      if (W == 0) continue;
-      int *epos = nullptr;
-      double *eval = nullptr;
-      unsigned char *c8 = nullptr;
-      if (hipMalloc((void **)&epos, sizeof(int) * (size_t)W * n) != hipSuccess ||
-          hipMalloc((void **)&eval, sizeof(double) * (size_t)W * n) != hipSuccess ||
-          hipMalloc((void **)&c8, (size_t)n) != hipSuccess) {  // no room: keep the CSR form
-        (void)hipGetLastError();
-        (void)hipFree(epos);
-        (void)hipFree(eval);
-        (void)hipFree(c8);
-        continue;
-      }
-      hipLaunchKernelGGL(ssor_to_ell_kernel, dim3(grid), dim3(256), 0, stream(), n, W, *ptr, *pos, *val, c8, epos, eval);
-      if (hipStreamSynchronize(stream()) != hipSuccess) rc = fail(PSP_ENODEV, "ssor: ell build failed");
-      (void)hipFree(*ptr);
-      (void)hipFree(*pos);
-      (void)hipFree(*val);
-      *ptr = nullptr;
-      *pos = epos;
-      *val = eval;
-      (dir ? K->bc8 : K->fc8) = c8;
-      (dir ? K->ell_b : K->ell_f) = W;
+      if (hipMemcpy(&maxc, dmax, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(PSP_ENODEV, "ssor: max");
     }
+    static const bool ell_off = [] {
+      const char *e = psp::tuning_env("PSP_SSOR_ELL");
+      return e && atoi(e) == 0;
+    }();
+    int W = 0;
+    for (int w : {1, 2, 3, 4, 6, 8})
+      if (maxc <= w) {
+        W = w;
+        break;
+      }
+    if (maxc == 0 || ell_off) W = 0;
+    if (W == 0) continue;
+    DevArray<unsigned char> c8;  // (in reverse: with no room epos is given back first)
+    DevArray<double> eval;
+    DevArray<int> epos;
+    if (!epos.try_alloc((size_t)W * n) || !eval.try_alloc((size_t)W * n) || !c8.try_alloc((size_t)n))
+      continue;  // no room: keep the CSR form
+    hipLaunchKernelGGL(ssor_to_ell_kernel, dim3(grid), dim3(256), 0, stream(), n, W, ptr, pos, val, c8, epos, eval);
+    const bool built = hipStreamSynchronize(stream()) == hipSuccess;
+    ptr.reset();
+    pos = std::move(epos);
+    val = std::move(eval);
+    (dir ? K->bc8 : K->fc8) = std::move(c8);
+    (dir ? K->ell_b : K->ell_f) = W;
+    if (!built) return fail(PSP_ENODEV, "ssor: ell build failed");
   }
   // vectors by position
-  if (rc == PSP_OK) rc = dev_alloc(&K->da, n);
-  if (rc == PSP_OK) rc = dev_alloc(&K->bp, n);
-  if (rc == PSP_OK) rc = dev_alloc(&K->xp, n);
-  if (rc == PSP_OK) rc = dev_alloc(&K->temp, n);
-  if (rc == PSP_OK) rc = reorder_gather(n, K->pos2row, S->diag, K->da, nullptr);
-  if (rc == PSP_OK && hipStreamSynchronize(stream()) != hipSuccess) rc = fail(PSP_ENODEV, "ssor: build failed");
-  if (rc == PSP_OK && hipGetLastError() != hipSuccess) rc = fail(PSP_ENODEV, "ssor: build kernels failed");
-  (void)hipFree(cnt);
-  return rc;
+  PSP_TRY(K->da.alloc((size_t)n));
+  PSP_TRY(K->bp.alloc((size_t)n));
+  PSP_TRY(K->xp.alloc((size_t)n));
+  PSP_TRY(K->temp.alloc((size_t)n));
+  PSP_TRY(reorder_gather(n, K->pos2row, S->diag, K->da, nullptr));
+  if (hipStreamSynchronize(stream()) != hipSuccess) return fail(PSP_ENODEV, "ssor: build failed");
+  if (hipGetLastError() != hipSuccess) return fail(PSP_ENODEV, "ssor: build kernels failed");
+  return PSP_OK;
 }
 
 // runs of narrow levels for ssor_run_kernel (see there).  Never fails the handle: whatever goes wrong here leaves
@@ -1768,7 +1730,7 @@ void build_runs_w(psp_ssor *K, int dir) {
   const int *dlp = dir ? K->dptr_b : K->dptr_f;
   const int *pos = dir ? K->b_pos : K->f_pos;
   const unsigned char *c8 = dir ? K->bc8 : K->fc8;
-  const int *rowmap = dir ? K->b_row : nullptr;
+  const int *rowmap = dir ? K->b_row.get() : nullptr;
   psp_ssor::RunSet &rs = dir ? K->run_b : K->run_f;
   const int nl = (int)lp.size() - 1, n = K->n;
   // candidates: maximal stretches of levels of at most kRunWide rows
@@ -1784,15 +1746,15 @@ void build_runs_w(psp_ssor *K, int dir) {
     l = e;
   }
   if (cand.empty()) return;
-  int *slot_of = nullptr, *lev_maxd = nullptr;
+  DevArray<int> slot_of, lev_maxd;
   std::vector<int> maxd((size_t)nl, 0);
   bool ok = true;
   if (dir) {  // a backward row's dependencies are positions; the ring is indexed by backward slots
-    ok = hipMalloc((void **)&slot_of, sizeof(int) * (size_t)n) == hipSuccess;
+    ok = slot_of.try_alloc((size_t)n);
     if (ok) hipLaunchKernelGGL(invert_perm_kernel, dim3(std::min((n + 255) / 256, 65536)), dim3(256), 0, stream(), n,
                                K->b_row, slot_of);
   }
-  ok = ok && hipMalloc((void **)&lev_maxd, sizeof(int) * (size_t)nl) == hipSuccess &&
+  ok = ok && lev_maxd.try_alloc((size_t)nl) &&
        hipMemsetAsync(lev_maxd, 0, sizeof(int) * (size_t)nl, stream()) == hipSuccess;
   if (ok) {
     for (const auto &c : cand) {
@@ -1842,15 +1804,12 @@ void build_runs_w(psp_ssor *K, int dir) {
     }
     if (!rs.runs.empty()) {
       constexpr int DW = (W + 1) / 2;
-      ok = hipMalloc((void **)&rs.dpk, sizeof(unsigned) * (size_t)DW * rs.m) == hipSuccess &&
-           hipMalloc((void **)&rs.vp, sizeof(double2) * (size_t)DW * rs.m) == hipSuccess &&
-           hipMalloc((void **)&rs.dar, sizeof(double) * (size_t)rs.m) == hipSuccess &&
-           hipMalloc((void **)&rs.gd, sizeof(double2) * (size_t)rs.m) == hipSuccess &&
-           hipMalloc((void **)&rs.ticks, sizeof(int2) * ticks.size()) == hipSuccess &&
+      ok = rs.dpk.try_alloc((size_t)DW * rs.m) && rs.vp.try_alloc((size_t)DW * rs.m) && rs.dar.try_alloc((size_t)rs.m) &&
+           rs.gd.try_alloc((size_t)rs.m) && rs.ticks.try_alloc(ticks.size()) &&
            hipMemcpyAsync(rs.ticks, ticks.data(), sizeof(int2) * ticks.size(), hipMemcpyHostToDevice, stream()) ==
                hipSuccess;
       if (ok && !K->run_progress)
-        ok = hipMalloc((void **)&K->run_progress, 2 * sizeof(int)) == hipSuccess &&
+        ok = K->run_progress.try_alloc(2) &&
              hipMemsetAsync(K->run_progress, 0, 2 * sizeof(int), stream()) == hipSuccess;
       if (ok) {
         for (const psp_ssor::Run &r : rs.runs)
@@ -1861,15 +1820,10 @@ void build_runs_w(psp_ssor *K, int dir) {
       }
     }
   }
-  (void)hipFree(slot_of);
-  (void)hipFree(lev_maxd);
+  slot_of.reset();  // (before a failed run set gives its arrays back: the order decides the next direction's addresses)
+  lev_maxd.reset();
   if (!ok) {
     (void)hipGetLastError();
-    (void)hipFree(rs.dpk);
-    (void)hipFree(rs.vp);
-    (void)hipFree(rs.dar);
-    (void)hipFree(rs.gd);
-    (void)hipFree(rs.ticks);
     rs = psp_ssor::RunSet();
   }
 }
@@ -1877,13 +1831,12 @@ void build_runs_w(psp_ssor *K, int dir) {
 // ---- bricks (see ssor_brick_kernel): the plan of one direction, made before anything is committed
 struct BrickPlan {
   int nb = 0;
-  int *rows = nullptr;            // device: rows in (brick, level, row) order = the direction's slot order
+  DevArray<int> rows;             // device: rows in (brick, level, row) order = the direction's slot order
   std::vector<int> brick_start;   // slot ranges by processing index (nb + 1)
   std::vector<int2> ticks;
   std::vector<int> tick_brick;    // per (padded) tick: the brick it belongs to
   std::vector<int4> info, pred;
   std::vector<int> halo_base;     // nb + 1
-  ~BrickPlan() { (void)hipFree(rows); }
 };
 
 struct GridShape {
@@ -1894,8 +1847,8 @@ struct GridShape {
 bool detect_grid(const psp_sss *S, GridShape *g) {
   const int n = S->n;
   if (n < 8 || S->nnz_lower < 1) return false;
-  int *mm = nullptr;
-  if (hipMalloc((void **)&mm, 5 * sizeof(int)) != hipSuccess) return false;
+  DevArray<int> mm;
+  if (!mm.try_alloc(5)) return false;
   const int init[5] = {0x7fffffff, 0, 0x7fffffff, 0, 0};
   int h[5] = {0, 0, 0, 0, 0};
   const dim3 grid((n + 255) / 256), block(256);
@@ -1920,7 +1873,6 @@ bool detect_grid(const psp_sss *S, GridShape *g) {
          hipStreamSynchronize(stream()) == hipSuccess && h[4] == 0;
   }
   (void)hipGetLastError();
-  (void)hipFree(mm);
   return ok;
 }
 
@@ -1937,35 +1889,24 @@ bool plan_bricks(const psp_sss *S, const GridShape &g, int dir, const int *level
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return wave(a) < wave(b); });
   if (dir) std::reverse(order.begin(), order.end());
   for (int i = 0; i < nb; ++i) rank[(size_t)order[(size_t)i]] = i;
-  int *d_rank = nullptr, *d_iota = nullptr, *d_slot = nullptr, *d_bstart = nullptr, *d_flag = nullptr, *d_starts = nullptr,
-      *d_cnt = nullptr, *d_ext = nullptr;
-  unsigned long long *d_key = nullptr, *d_key2 = nullptr;
-  void *tmp = nullptr;
-  bool ok = true;
+  DevArray<char> tmp;  // (in reverse, as in build_schedule: d_rank is freed first, tmp last)
+  DevArray<int> d_ext, d_cnt, d_starts, d_flag, d_bstart, d_slot;
+  DevArray<unsigned long long> d_key2, d_key;
+  DevArray<int> d_iota, d_rank;
   const dim3 grid((n + 255) / 256), block(256);
-  auto A = [&](void **p, size_t bytes) { ok = ok && hipMalloc(p, bytes ? bytes : 1) == hipSuccess; };
-  A((void **)&d_rank, sizeof(int) * (size_t)nb);
-  A((void **)&d_iota, sizeof(int) * (size_t)n);
-  A((void **)&P->rows, sizeof(int) * (size_t)n);
-  A((void **)&d_key, sizeof(unsigned long long) * (size_t)n);
-  A((void **)&d_key2, sizeof(unsigned long long) * (size_t)n);
-  A((void **)&d_slot, sizeof(int) * (size_t)n);
-  A((void **)&d_bstart, sizeof(int) * ((size_t)nb + 1));
-  A((void **)&d_flag, sizeof(int) * (size_t)n);
-  A((void **)&d_starts, sizeof(int) * (size_t)n);
-  A((void **)&d_cnt, sizeof(int) * 2);
-  A((void **)&d_ext, sizeof(int) * (size_t)nb);
+  bool ok = d_rank.try_alloc((size_t)nb) && d_iota.try_alloc((size_t)n) && P->rows.try_alloc((size_t)n) &&
+            d_key.try_alloc((size_t)n) && d_key2.try_alloc((size_t)n) && d_slot.try_alloc((size_t)n) &&
+            d_bstart.try_alloc((size_t)nb + 1) && d_flag.try_alloc((size_t)n) && d_starts.try_alloc((size_t)n) &&
+            d_cnt.try_alloc(2) && d_ext.try_alloc((size_t)nb);
   ok = ok && hipMemcpyAsync(d_rank, rank.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, stream()) == hipSuccess;
   int nbits = 1;
   while ((1 << nbits) < nb) ++nbits;
   if (ok) {
     hipLaunchKernelGGL(brick_key_kernel, grid, block, 0, stream(), n, nx, ny, nxy, ba, bb, d_rank, level, d_key, d_iota);
-    size_t bytes = 0;
-    ok = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_key, d_key2, d_iota, P->rows, n, 0, 32 + nbits, stream()) ==
-         hipSuccess;
-    A(&tmp, bytes);
-    ok = ok && hipcub::DeviceRadixSort::SortPairs(tmp, bytes, d_key, d_key2, d_iota, P->rows, n, 0, 32 + nbits, stream()) ==
-                   hipSuccess;  // stable: rows ascending inside a (brick, level) group
+    ok = cub_two_calls(tmp, [&](void *t, size_t &bytes) {  // stable: rows ascending inside a (brick, level) group
+           return hipcub::DeviceRadixSort::SortPairs(t, bytes, d_key.get(), d_key2.get(), d_iota.get(), P->rows.get(), n, 0,
+                                                     32 + nbits, stream());
+         }) == hipSuccess;
   }
   int ngroups = 0;
   std::vector<int> starts, ext;
@@ -1980,13 +1921,10 @@ bool plan_bricks(const psp_sss *S, const GridShape &g, int dir, const int *level
   if (ok) {
     hipLaunchKernelGGL(brick_check_kernel, grid, block, 0, stream(), n, dir, S->ind, S->col, d_slot, nb, d_bstart, d_ext,
                        d_cnt + 1);
-    (void)hipFree(tmp);
-    tmp = nullptr;
-    size_t bytes = 0;
-    ok = hipcub::DeviceSelect::Flagged(nullptr, bytes, d_iota, d_flag, d_starts, d_cnt, n, stream()) == hipSuccess;
-    A(&tmp, bytes);
     // d_iota was the sort's input buffer and still holds 0 .. n-1
-    ok = ok && hipcub::DeviceSelect::Flagged(tmp, bytes, d_iota, d_flag, d_starts, d_cnt, n, stream()) == hipSuccess;
+    ok = cub_two_calls(tmp, [&](void *t, size_t &bytes) {
+           return hipcub::DeviceSelect::Flagged(t, bytes, d_iota.get(), d_flag.get(), d_starts.get(), d_cnt.get(), n, stream());
+         }) == hipSuccess;
     int cnt[2] = {0, 0};
     ok = ok && hipMemcpyAsync(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, stream()) == hipSuccess &&
          hipStreamSynchronize(stream()) == hipSuccess && cnt[1] == 0 && cnt[0] > 0;
@@ -2041,9 +1979,6 @@ bool plan_bricks(const psp_sss *S, const GridShape &g, int dir, const int *level
     }
   }
   (void)hipGetLastError();
-  for (void *q : {(void *)d_rank, (void *)d_iota, (void *)d_key, (void *)d_key2, (void *)d_slot, (void *)d_bstart,
-                  (void *)d_flag, (void *)d_starts, (void *)d_cnt, (void *)d_ext, tmp})
-    (void)hipFree(q);
   return ok;
 }
 
@@ -2066,25 +2001,16 @@ int finish_bricks_w(psp_ssor *K, int dir, const BrickPlan &P) {
   const int *pos = dir ? K->b_pos : K->f_pos;
   const double *val = dir ? K->b_val : K->f_val;
   const unsigned char *c8 = dir ? K->bc8 : K->fc8;
-  const int *rowmap = dir ? K->b_row : nullptr;
-  int *slot_of = nullptr, *d_bstart = nullptr, *d_ext = nullptr, *d_eoff = nullptr;
-  void *scan_tmp = nullptr;
-  int rc = PSP_OK;
+  const int *rowmap = dir ? K->b_row.get() : nullptr;
+  DevArray<char> scan_tmp;  // (in reverse: slot_of is freed first, scan_tmp last)
+  DevArray<int> d_eoff, d_ext, d_bstart, slot_of;
   bs.nbricks = nb;
   const int nhalo = P.halo_base[(size_t)nb];
-  bool ok = hipMalloc((void **)&bs.ticks, sizeof(int2) * P.ticks.size()) == hipSuccess &&
-            hipMalloc((void **)&bs.info, sizeof(int4) * (size_t)nb) == hipSuccess &&
-            hipMalloc((void **)&bs.pred, sizeof(int4) * (size_t)nb) == hipSuccess &&
-            hipMalloc((void **)&bs.halo_pos, sizeof(int) * ((size_t)nhalo + 1)) == hipSuccess &&  // (+1: padding ticks read one)
-            hipMalloc((void **)&bs.dpk, sizeof(unsigned) * (size_t)DW * n) == hipSuccess &&
-            hipMalloc((void **)&bs.vp, sizeof(double2) * (size_t)DW * n) == hipSuccess &&
-            hipMalloc((void **)&bs.dar, sizeof(double) * (size_t)n) == hipSuccess &&
-            hipMalloc((void **)&bs.gd, sizeof(double2) * (size_t)n) == hipSuccess &&
-            hipMalloc((void **)&bs.flags, sizeof(int) * flag_words(nb)) == hipSuccess &&
-            hipMalloc((void **)&d_bstart, sizeof(int) * ((size_t)nb + 1)) == hipSuccess &&
-            hipMalloc((void **)&d_ext, sizeof(int) * ((size_t)n + 1)) == hipSuccess &&
-            hipMalloc((void **)&d_eoff, sizeof(int) * ((size_t)n + 1)) == hipSuccess &&
-            (!dir || hipMalloc((void **)&slot_of, sizeof(int) * (size_t)n) == hipSuccess);
+  bool ok = bs.ticks.try_alloc(P.ticks.size()) && bs.info.try_alloc((size_t)nb) && bs.pred.try_alloc((size_t)nb) &&
+            bs.halo_pos.try_alloc((size_t)nhalo + 1) &&  // (+1: padding ticks read one)
+            bs.dpk.try_alloc((size_t)DW * n) && bs.vp.try_alloc((size_t)DW * n) && bs.dar.try_alloc((size_t)n) &&
+            bs.gd.try_alloc((size_t)n) && bs.flags.try_alloc(flag_words(nb)) && d_bstart.try_alloc((size_t)nb + 1) &&
+            d_ext.try_alloc((size_t)n + 1) && d_eoff.try_alloc((size_t)n + 1) && (!dir || slot_of.try_alloc((size_t)n));
   ok = ok &&
        hipMemcpyAsync(bs.ticks, P.ticks.data(), sizeof(int2) * P.ticks.size(), hipMemcpyHostToDevice, stream()) ==
            hipSuccess &&
@@ -2100,10 +2026,9 @@ int finish_bricks_w(psp_ssor *K, int dir, const BrickPlan &P) {
                          slot_of);
     hipLaunchKernelGGL(brick_extcnt_kernel<W>, dim3((n + 256) / 256), dim3(256), 0, stream(), n, c8, pos, slot_of, nb,
                        d_bstart, d_ext);
-    size_t bytes = 0;
-    ok = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_ext, d_eoff, n + 1, stream()) == hipSuccess &&
-         hipMalloc(&scan_tmp, bytes ? bytes : 1) == hipSuccess &&
-         hipcub::DeviceScan::ExclusiveSum(scan_tmp, bytes, d_ext, d_eoff, n + 1, stream()) == hipSuccess;
+    ok = cub_two_calls(scan_tmp, [&](void *t, size_t &bytes) {
+           return hipcub::DeviceScan::ExclusiveSum(t, bytes, d_ext.get(), d_eoff.get(), n + 1, stream());
+         }) == hipSuccess;
   }
   if (ok) {
     hipLaunchKernelGGL(brick_pack_kernel<W>, dim3((n + 255) / 256), dim3(256), 0, stream(), n, c8, pos, val, slot_of,
@@ -2112,13 +2037,10 @@ int finish_bricks_w(psp_ssor *K, int dir, const BrickPlan &P) {
   }
   if (ok && brick_pipe_wanted()) {  // never fails the handle: without tick_ext the sweeps wait for whole bricks
     const int nt = (int)P.ticks.size();
-    int *d_tb = nullptr, *d_tl = nullptr, *d_need = nullptr, *d_bad = nullptr;
+    DevArray<int> d_bad, d_need, d_tl, d_tb;
     int bad = 1;
-    bool pk = hipMalloc((void **)&d_tb, sizeof(int) * (size_t)nt) == hipSuccess &&
-              hipMalloc((void **)&d_tl, sizeof(int) * (size_t)n) == hipSuccess &&
-              hipMalloc((void **)&d_need, sizeof(int) * 3 * (size_t)nt) == hipSuccess &&
-              hipMalloc((void **)&d_bad, sizeof(int)) == hipSuccess &&
-              hipMalloc((void **)&bs.tick_ext, sizeof(int4) * (size_t)nt) == hipSuccess &&
+    bool pk = d_tb.try_alloc((size_t)nt) && d_tl.try_alloc((size_t)n) && d_need.try_alloc(3 * (size_t)nt) &&
+              d_bad.try_alloc(1) && bs.tick_ext.try_alloc((size_t)nt) &&
               hipMemcpyAsync(d_tb, P.tick_brick.data(), sizeof(int) * (size_t)nt, hipMemcpyHostToDevice, stream()) ==
                   hipSuccess &&
               hipMemsetAsync(d_need, 0, sizeof(int) * 3 * (size_t)nt, stream()) == hipSuccess &&
@@ -2135,21 +2057,10 @@ int finish_bricks_w(psp_ssor *K, int dir, const BrickPlan &P) {
     }
     if (!pk) {
       (void)hipGetLastError();
-      (void)hipFree(bs.tick_ext);
-      bs.tick_ext = nullptr;
+      bs.tick_ext.reset();
     }
-    (void)hipFree(d_tb);
-    (void)hipFree(d_tl);
-    (void)hipFree(d_need);
-    (void)hipFree(d_bad);
   }
-  if (!ok) rc = fail(PSP_ENOMEM, "ssor: the brick schedule could not be built");
-  (void)hipFree(slot_of);
-  (void)hipFree(d_bstart);
-  (void)hipFree(d_ext);
-  (void)hipFree(d_eoff);
-  (void)hipFree(scan_tmp);
-  return rc;
+  return ok ? PSP_OK : fail(PSP_ENOMEM, "ssor: the brick schedule could not be built");
 }
 
 int finish_bricks(psp_ssor *K, int dir, const BrickPlan &P) {
@@ -2288,7 +2199,7 @@ static int ssor_create_device(psp_sss_t *S, double omega, int steps, bool allow_
   K->S = S;
   int rc = PSP_OK;
   if (S->n > 0) {
-    int *rows_f = nullptr, *rows_b = nullptr, *lev_f = nullptr, *lev_b = nullptr;
+    DevArray<int> rows_f, rows_b, lev_f, lev_b;
     rc = build_schedule(S->full, 0, &rows_f, &K->ptr_f, &lev_f);
     if (rc == PSP_OK) rc = build_schedule(S->full, 1, &rows_b, &K->ptr_b, &lev_b);
     BrickPlan plan_f, plan_b;
@@ -2301,25 +2212,23 @@ static int ssor_create_device(psp_sss_t *S, double omega, int steps, bool allow_
       std::swap(rows_b, plan_b.rows);
       K->brick_mode = true;
     }
-    (void)hipFree(lev_f);
-    (void)hipFree(lev_b);
-    if (rc == PSP_OK) {
-      // backward slots are (level, row)-sorted rows; ptr_b indexes slots
-      rc = build_level_ordered(K, rows_f, rows_b);
-      rows_f = nullptr;  // owned by K now (pos2row), even on failure
-    }
-    (void)hipFree(rows_f);
-    (void)hipFree(rows_b);
+    lev_f.reset();
+    lev_b.reset();
+    // backward slots are (level, row)-sorted rows; ptr_b indexes slots
+    if (rc == PSP_OK) rc = build_level_ordered(K, std::move(rows_f), rows_b);
+    rows_f.reset();  // (still held when the schedules failed and the call above did not run)
+    rows_b.reset();
     if (rc == PSP_OK && K->brick_mode) {
       rc = finish_bricks(K, 0, plan_f);
       if (rc == PSP_OK) rc = finish_bricks(K, 1, plan_b);
       K->brick_pipe = rc == PSP_OK && K->brick_f.tick_ext && K->brick_b.tick_ext;
       if (rc == PSP_OK) {  // the brick sweeps stream their own copies: the slot-major triangle is not needed any more
-        for (void **q : {(void **)&K->f_pos, (void **)&K->f_val, (void **)&K->b_pos, (void **)&K->b_val, (void **)&K->fc8,
-                         (void **)&K->bc8}) {
-          (void)hipFree(*q);
-          *q = nullptr;
-        }
+        K->f_pos.reset();
+        K->f_val.reset();
+        K->b_pos.reset();
+        K->b_val.reset();
+        K->fc8.reset();
+        K->bc8.reset();
       }
       if (rc != PSP_OK) {  // the slot orders are the bricks' by now: start over on the level schedule
         (void)hipGetLastError();
@@ -2341,7 +2250,7 @@ static int ssor_create_device(psp_sss_t *S, double omega, int steps, bool allow_
     }
     if (rc == PSP_OK) {
       const size_t bf = sizeof(int) * K->ptr_f.size(), bb = sizeof(int) * K->ptr_b.size();
-      if (hipMalloc((void **)&K->dptr_f, bf) != hipSuccess || hipMalloc((void **)&K->dptr_b, bb) != hipSuccess ||
+      if (!K->dptr_f.try_alloc(K->ptr_f.size()) || !K->dptr_b.try_alloc(K->ptr_b.size()) ||
           hipMemcpy(K->dptr_f, K->ptr_f.data(), bf, hipMemcpyHostToDevice) != hipSuccess ||
           hipMemcpy(K->dptr_b, K->ptr_b.data(), bb, hipMemcpyHostToDevice) != hipSuccess)
         rc = fail(PSP_ENOMEM, "ssor: level table allocation failed");
@@ -2368,21 +2277,9 @@ int psp_ssor_destroy(psp_ssor_t *K) {
   if (K->exec) (void)hipGraphExecDestroy(K->exec);
   if (K->graph) (void)hipGraphDestroy(K->graph);
   if (K->cap_stream) (void)hipStreamDestroy(K->cap_stream);
-  for (void *p : {(void *)K->pos2row, (void *)K->row2pos, (void *)K->dptr_f, (void *)K->dptr_b, (void *)K->f_ptr,
-                  (void *)K->f_pos, (void *)K->f_val, (void *)K->b_row, (void *)K->b_ptr, (void *)K->b_pos,
-                  (void *)K->b_val, (void *)K->da, (void *)K->bp, (void *)K->xp, (void *)K->temp, (void *)K->fc8,
-                  (void *)K->bc8, (void *)K->run_f.dpk, (void *)K->run_f.dar, (void *)K->run_f.gd, (void *)K->run_f.ticks,
-                  (void *)K->run_f.vp, (void *)K->run_b.dpk, (void *)K->run_b.dar, (void *)K->run_b.gd,
-                  (void *)K->run_b.ticks, (void *)K->run_b.vp,
-                  (void *)K->run_progress})
-    (void)hipFree(p);
   if (K->brick_ev) (void)hipEventDestroy(K->brick_ev);
   if (K->brick_err_host) (void)hipHostFree(K->brick_err_host);
-  for (psp_ssor::BrickSet *b : {&K->brick_f, &K->brick_b})
-    for (void *p : {(void *)b->ticks, (void *)b->info, (void *)b->pred, (void *)b->halo_pos, (void *)b->dpk, (void *)b->vp,
-                    (void *)b->dar, (void *)b->gd, (void *)b->flags, (void *)b->tick_ext})
-      (void)hipFree(p);
-  delete K;
+  delete K;  // the device arrays go with their members
   return PSP_OK;
 }
 
@@ -2427,22 +2324,20 @@ int psp_ssor_precon(psp_ssor_t *K, const double *x_host, double *y_host) {
   if (K->n == 0) return PSP_OK;
   if (K->host) return psp::ssor_apply_host(K, x_host, y_host);
   PSP_TRY(ensure_device());
-  double *x = nullptr, *y = nullptr;
   const size_t bytes = sizeof(double) * (size_t)K->n;
-  PSP_HIP(hipMalloc((void **)&x, bytes));
-  if (hipMalloc((void **)&y, bytes) != hipSuccess) {
-    (void)hipFree(x);
-    return fail(PSP_ENOMEM, "psp_ssor_precon: device allocation failed");
-  }
   int rc = PSP_OK;
-  hipError_t e = hipMemcpyAsync(x, x_host, bytes, hipMemcpyHostToDevice, stream());
-  // steps == 0 leaves y untouched, so hand the caller's y through
-  if (e == hipSuccess) e = hipMemcpyAsync(y, y_host, bytes, hipMemcpyHostToDevice, stream());
-  if (e == hipSuccess) rc = ssor_apply_dev(K, x, y);
-  if (e == hipSuccess && rc == PSP_OK) e = hipMemcpyAsync(y_host, y, bytes, hipMemcpyDeviceToHost, stream());
-  if (e == hipSuccess) e = hipStreamSynchronize(stream());
-  (void)hipFree(x);
-  (void)hipFree(y);
+  hipError_t e;
+  {
+    DevArray<double> y, x;
+    PSP_TRY(x.alloc((size_t)K->n));
+    if (!y.try_alloc((size_t)K->n)) return fail(PSP_ENOMEM, "psp_ssor_precon: device allocation failed");
+    e = hipMemcpyAsync(x, x_host, bytes, hipMemcpyHostToDevice, stream());
+    // steps == 0 leaves y untouched, so hand the caller's y through
+    if (e == hipSuccess) e = hipMemcpyAsync(y, y_host, bytes, hipMemcpyHostToDevice, stream());
+    if (e == hipSuccess) rc = ssor_apply_dev(K, x, y);
+    if (e == hipSuccess && rc == PSP_OK) e = hipMemcpyAsync(y_host, y, bytes, hipMemcpyDeviceToHost, stream());
+    if (e == hipSuccess) e = hipStreamSynchronize(stream());
+  }
   if (rc != PSP_OK) return rc;
   if (e != hipSuccess) return fail(PSP_ENODEV, "psp_ssor_precon: %s", hipGetErrorString(e));
   return psp::ssor_error_check(K);

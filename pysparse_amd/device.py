@@ -930,3 +930,12 @@ def device_info():
     cu, mem = C.c_int(), C.c_int64()
     check(lib().psp_device_info(name, 256, C.byref(cu), C.byref(mem)))
     return name.value.decode(), cu.value, mem.value
+
+
+def debug_device_bytes():
+    """(live_bytes, allocations): the device memory that precon.ssor / precon.multigrid handles and their set-up hold now
+    through the library's owning array type -- and, while such a call runs, the staging of csr_mat's host-pointer diagonal
+    and transposed product --, and the allocations that type has made so far (psp_debug_device_bytes)."""
+    live, made = C.c_longlong(), C.c_longlong()
+    check(lib().psp_debug_device_bytes(C.byref(live), C.byref(made)))
+    return live.value, made.value

@@ -16,7 +16,7 @@ ends (5 / 7 points, built here and uploaded as a csr_mat), with the protocol of 
 
 Every case runs in a child process of its own under `timeout`; the first child that fails ends the run.
 
-    python tools/mg_interp_timing.py [--out profiles/mg_interp_timing.json] [--quick] [--grids 256^3,4096^2] [--fields block,smooth]
+    python tools/mg_interp_timing.py [--out profiles/mg_interp_timing.json] [--quick] [--grids 256^3,4096^2] [--fields block,smooth] [--creation-only]
 """
 import argparse
 import ctypes as C
@@ -118,7 +118,7 @@ def true_relres(L, check, A, xb, bb, rb, n):
     return (res2 / b2) ** 0.5
 
 
-def run_case(name, grid, field):
+def run_case(name, grid, field, creation_only=False):
     from pysparse_amd import device as dev
     from pysparse_amd._capi import check, lib
     L = lib()
@@ -146,6 +146,8 @@ def run_case(name, grid, field):
                       "tail_first_level": info["tail_first_level"], "launches_per_apply": info["launches_per_apply"]}
         out[label]["bytes"]["operator_per_fine_point"] = out[label]["bytes"]["operator"] / n
     out["operator"]["fallbacks"] = [handles["operator"].interp_fallbacks(l) for l in range(out["operator"]["levels"] - 1)]
+    if creation_only:
+        return out
     bb, xb = dev.DeviceBuffer(n), dev.DeviceBuffer(n)
     fill_random(L, check, bb, n)
     stream_bytes = max(4096, (8 * n) // 4096 * 4096)
@@ -200,12 +202,14 @@ def main():
     p.add_argument("--quick", action="store_true", help="two small grids: a rehearsal of the tool, not a measurement")
     p.add_argument("--grids", help="comma-separated subset of the grids; results are merged into --out")
     p.add_argument("--fields", default=",".join(FIELDS), help="comma-separated subset of block, smooth")
+    p.add_argument("--creation-only", action="store_true",
+                   help="stop after the handles exist: handle_creation_seconds and bytes, no cycles and no solves")
     p.add_argument("--case", help="(internal) run one grid:field in this process and print its JSON record")
     a = p.parse_args()
     cases = QUICK if a.quick else CASES
     if a.case:
         name, field = a.case.split(":")
-        print("RESULT " + json.dumps(run_case(name, cases[name][0], field)), flush=True)
+        print("RESULT " + json.dumps(run_case(name, cases[name][0], field, a.creation_only)), flush=True)
         return 0
     res = {"quick": a.quick, "cases": {}}
     if os.path.exists(a.out):
@@ -220,6 +224,8 @@ def main():
             cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--case", name + ":" + field]
             if a.quick:
                 cmd.append("--quick")
+            if a.creation_only:
+                cmd.append("--creation-only")
             r = subprocess.run(cmd, capture_output=True, text=True)
             sys.stdout.write(r.stdout)
             if r.returncode != 0:
